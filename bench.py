@@ -20,7 +20,13 @@ or is invented -- the only collectives are the barrier and the max-reduction of 
 --scenes K (config C3): K different synthetic scenes; --scene-map pose (every rank holds every scene,
 frame g -> rank g mod N) or scene (scene s -> rank s mod N), or both.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: inputs, warm-up, the K timed steps, the
+outputs if --dump-outputs DIR is given, and ONE JSON line from rank 0 with `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (= the milliseconds of one timed step) and the workload's `config`.  --dump-outputs writes the
+frames the timed path handed its caller in its last step (a fixed, seeded sample; see dump_outputs) as .npy files, so
+that two builds can be compared output for output: the inputs are the same from run to run.
+
+With --full the line also carries these objects, each measured or checked by passes of its own after the timed region:
   roofline       -- traversal kernel (render_persist).  `achieved` / `frac` = HBM bytes per launch from the
                     rocprofv3 counter passes committed under profiles/ (FETCH_SIZE + WRITE_SIZE, separate
                     passes, this workload) / this run's average launch duration (HIP events on the launch
@@ -56,6 +62,24 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
 WARM_FRAMES_REF = 100  # main_headless.cpp:469-479: 100 warm-up frames each advance the RNG
+
+
+def finite(o):  # strict JSON: no NaN / Infinity tokens in the driver's line
+    if isinstance(o, float):
+        return o if np.isfinite(o) else None
+    if isinstance(o, dict):
+        return {k: finite(v) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return [finite(v) for v in o]
+    if isinstance(o, (np.floating, np.integer)):
+        return finite(o.item())
+    return o
+
+
+def emit(out):
+    """the ONE JSON line of rank 0"""
+    print(json.dumps(finite(out), allow_nan=False))
+    sys.stdout.flush()
 
 
 def parse_args(argv=None):
@@ -131,6 +155,12 @@ def parse_args(argv=None):
                          "of the packed fp16 values the network actually produces: same pixels, twice the bytes")
     ap.add_argument("--exact-filter", action="store_true",
                     help="run the bit-exact guided filter (164 exps per pixel) instead of the factorised one")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, run everything else the line reports: the single-stream, full-outputs and "
+                         "bit-exact passes, the oracle spot check, the reference loop, the roofline counts, the copy bandwidth, "
+                         "PSNR, the CPU baseline and (N > 1) the final gather.  Off: set-up, warm-up, timed steps, outputs, line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, < 64 MB)")
     args = ap.parse_args(argv)
     if args.c4:
         args = ap.parse_args((list(argv) if argv is not None else sys.argv[1:]) + C4_ARGS)
@@ -148,6 +178,24 @@ def tree_cache_path(args, scene=0):
     tag = hashlib.sha1(open(os.path.join(ROOT, "rt-octree_amd", "synth.py"), "rb").read()).hexdigest()[:10]
     base = "/dev/shm" if os.path.isdir("/dev/shm") else "/tmp"
     return os.path.join(base, "rto_bench_tree_%s_%s.npz" % (key, tag))
+
+
+def parallel_sdf(sdf, threads):
+    """`sdf` evaluated over blocks of points on a thread pool (numpy releases the GIL inside its loops).  Every point's
+    distance depends on that point alone, so the values are the same bit for bit; generating the depth-10 bench tree
+    spends more than half its time in the SDF, and a plain run must not spend it on one core."""
+    if threads <= 1:
+        return sdf
+    from concurrent.futures import ThreadPoolExecutor
+
+    def blocked(p):
+        n = p.shape[0]
+        if n < (1 << 16):
+            return sdf(p)
+        step = -(-n // (4 * threads))
+        with ThreadPoolExecutor(threads) as ex:
+            return np.concatenate(list(ex.map(lambda s: sdf(p[s:s + step]), range(0, n, step))))
+    return blocked
 
 
 def workload_id(args, W, H):
@@ -367,7 +415,7 @@ def main():
             if s % world == rank and not os.path.exists(path):
                 t0 = time.time()
                 th = synth.make_tree(depth_limit=args.depth, basis_dim=args.basis, shell=args.shell, radius=args.radius,
-                                     sdf=synth.scene_variant(s), seed=20230418 + s)
+                                     sdf=parallel_sdf(synth.scene_variant(s), max(1, usable_cores() // world)), seed=20230418 + s)
                 if args.shuffle_nodes:
                     th = synth.shuffle_nodes(th, args.shuffle_nodes)
                 tmp = "%s.tmp%d.npz" % (path, rank)
@@ -558,6 +606,39 @@ def main():
         return elapsed, kt, {"render_ms": render_ms, "torch_ms": torch_ms, "filter_ms": filter_ms,
                              "fps": 1000.0 / all_ms if all_ms > 0 else 0.0, "frames": n_frames}, work
 
+    def dump_outputs(out_dir, work):
+        """--dump-outputs: what the timed pass `work` handed its caller in its last step -- each frame's `image` buffer (the
+        denoised image; the raw render with --no-denoise) -- for the frames of that step still held by the lanes (the last
+        launch group of each lane).  A fixed, seeded sample, at most 64 MB: every such frame at the same pixels
+        (images_sampled [F, P, 4], sample_pixels = y * W + x, sample_frames = (scene, pose) of each frame, in frame order) and
+        the last frame whole (image_last [H, W, 4]) where it fits."""
+        starts = np.cumsum([0] + [len(idx) for _, idx in work])
+        pick, frames = [], []
+        for g in range(max(0, len(work) - NL), len(work)):
+            sc, idx = work[g]
+            for k, pose in enumerate(idx):
+                if starts[g] + k >= n_frames - FS:  # (a frame of the last step)
+                    pick.append((g % NL, k))
+                    frames.append((sc, pose))
+        if not pick:
+            return
+        os.makedirs(out_dir, exist_ok=True)
+        budget = 60 << 20
+        whole = H * W * 4 * 4
+        keep_whole = whole <= budget // 2
+        P = int(min(8192, H * W, (budget - (whole if keep_whole else 0)) // (16 * len(pick))))
+        pix = np.sort(np.random.default_rng(20230418).choice(H * W, P, replace=False))
+        pix_t = torch.as_tensor(pix, device=dev)
+        imgs = {ln: torch.as_tensor(lanes[ln][0].batch_views()[2], device=dev) for ln in {ln for ln, _ in pick}}
+        torch.cuda.synchronize(dev)
+        sampled = np.stack([imgs[ln][k].reshape(H * W, 4).index_select(0, pix_t).cpu().numpy() for ln, k in pick])
+        np.save(os.path.join(out_dir, "images_sampled.npy"), sampled.astype(np.float32))
+        np.save(os.path.join(out_dir, "sample_pixels.npy"), pix.astype(np.float64))
+        np.save(os.path.join(out_dir, "sample_frames.npy"), np.asarray(frames, np.float64))
+        if keep_whole:
+            ln, k = pick[-1]
+            np.save(os.path.join(out_dir, "image_last.npy"), imgs[ln][k].cpu().numpy().astype(np.float32))
+
     # ---------------- warm-up + timed region(s) ----------------
     if denoise and not args.torch_net:
         for _, _, lnet, _ in lanes:  # the packed-map scratch at its final size: no allocation (= device sync) in a timed region
@@ -566,8 +647,11 @@ def main():
     all_lanes = lanes
     # (VERDICT r5 task 4) the headline passes overlap launch-group tails over NL streams; the per-kernel durations and the
     # Timer::report buckets come from a single-stream pass of the same frames, where no other kernel shares the chip
-    single = timed(maps[0], nl=1) if NL > 1 else None
+    single = timed(maps[0], nl=1) if (NL > 1 and args.full) else None
     elapsed, kt, tstats, work = timed(maps[0], nl=NL)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, work)
+    frames_per_launch = n_frames / max(kt["launches"], 1)
     value_single = None
     if single:
         value_single = n_frames * world / single[0]
@@ -577,6 +661,54 @@ def main():
         e2, _, t2, _ = timed(maps[1], nl=NL)
         alt = {"scene_map": maps[1], "value": n_frames * world / e2, "ms_per_step": e2 / args.steps * 1e3,
                "reference_timer_fps": t2["fps"]}
+
+    # ---------------- the headline line: all of a plain run, the first keys of a --full one ----------------
+    wid = workload_id(args, W, H)
+    total_frames = n_frames * world
+    head = {
+        "metric": "FPS @ 800x800 (Lego SPP=6) + PSNR vs ref; 1/2/4/8 GPU scaling",
+        "value": total_frames / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if not denoise else "f32 (traversal, filter) + f16 x f16 -> f32 (GuidanceNet conv, %s)" % ("MIOpen" if args.torch_net else "fused MFMA kernel"),
+        "data": "synthetic",
+    }
+    config = {
+        "workload": "configs[%s]: %slego-like synthetic PlenOctree %s (%d nodes, depth %d), %dx%d SPP=%d%s, 1 step = %d launch groups of %d frames, frames sharded %s"
+                    % ({"c2": "1", "c4": "3 stand-in", "c5": "4"}.get(wid, "2" if n_scenes > 1 else "1-like"),
+                       ("%d scenes, " % n_scenes) if n_scenes > 1 else "",
+                       tree.data_format, tree.capacity, tree.max_depth, W, H, args.spp,
+                       " + GuidanceNet(8,32,5,2,4) denoise" if denoise else " raw (no denoise)", max(1, args.groups_per_step), B,
+                       "scene s -> rank s mod N" if (maps[0] == "scene" and n_scenes > 1) else "frame g -> rank g mod N"),
+        "tree_nodes": int(tree.capacity), "tree_device_mb": tree.device_bytes / 1e6,
+        "frames_per_step": FS, "groups_per_step": max(1, args.groups_per_step), "frames_per_group": B, "frames_timed": total_frames, "frames_per_launch": frames_per_launch, "streams": len(lanes),
+        "scenes": n_scenes, "scene_map": maps[0], "filter": "exact" if args.exact_filter else "factorised", "maps": "fp16 packed" if packed_route else "fp32 planes",
+        "parallelism": "frames x%d" % world,
+        # which clause of the north star each figure claims (VERDICT r4 task 4)
+        "value_route": ("render stage bit-exact against oracle/ (fp32 aux planes / RGBA8 of the noisy frame: parity_spot); denoise "
+                        "stage = fused fp16 GuidanceNet + %s" % ("the bit-exact filter" if (args.exact_filter or not packed_route) else
+                        "FACTORISED filter on packed fp16 maps: the TOLERANCE route (north star: 'within 1e-4 PSNR otherwise'; "
+                        "150 dB against the exact filter, psnr.rgba8_bytes_differing_factorised_vs_exact)")) if denoise else
+                       "raw render, bit-exact against oracle/",
+        "lean_outputs": bool(lean),
+        "lean_level": (args.lean_level if lean else 0),  # 2: sparse -- the headline launches store nothing for the pixels of culled tiles
+        "world": world, "backend": (backend if world > 1 else None), "gpus_visible": n_dev,
+        "launcher": ("none" if world == 1 else "bench.py itself (child torch.distributed.run)"
+                     if os.environ.get("RTO_BENCH_SELF_LAUNCHED") else "external (torchrun)"),
+        "full": bool(args.full),
+    }
+    if not args.full:  # a plain run ends here: everything below measures or checks something beside the headline
+        if rank == 0:
+            emit(dict(head, config=config, alt_scene_map=alt))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     last_group, last_lane = work[-1], (len(work) - 1) % NL
 
     def snapshot_last_group():
@@ -834,7 +966,6 @@ def main():
     px = W * H
     alg_bytes_frame = (4 * units["levels"] + 2 * units["steps"] + 2 * (tree.data_dim - 1) * units["hit_leaves"]
                        + 48 * px * count_steps) / count_steps
-    frames_per_launch = n_frames / max(kt["launches"], 1)
     alg_bytes_launch = alg_bytes_frame * frames_per_launch
     t_launch = kt["traverse_ms"] * 1e-3
     alg_gbps = alg_bytes_launch / t_launch / 1e9 if t_launch > 0 else 0.0
@@ -857,7 +988,6 @@ def main():
     traffic = tcp = traffic_src = valu = None
     traffic_stale = None
     code_id = kernel_code_id()
-    wid = workload_id(args, W, H)
     pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     if wid and os.path.exists(pmc_path):
         try:
@@ -1117,7 +1247,6 @@ def main():
                                      "(tests/), whose estimator semantics are pinned by tests/test_expectation.py; NOT a "
                                      "comparison with frames of the CUDA reference (none exist offline)")
 
-    total_frames = n_frames * world
     # without a counter pass for this workload the line falls back to the MARCHED algorithmic figure (bytes the kernel has
     # to move for the work it does: <= what any memory system moved), never to the every-ray one (which may exceed the peak)
     use = achieved if achieved is not None else m_trav_gbps
@@ -1166,53 +1295,20 @@ def main():
         "tcp": tcp,
         "valu": valu,
     }
-    out = {
-        "metric": "FPS @ 800x800 (Lego SPP=6) + PSNR vs ref; 1/2/4/8 GPU scaling",
-        "value": total_frames / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "value_exact": exact_pass["value"] if exact_pass else None,
-        "value_full_outputs": full_pass["value"] if full_pass else None,
-        "value_single_stream": value_single,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if not denoise else "f32 (traversal, filter) + f16 x f16 -> f32 (GuidanceNet conv, %s)" % ("MIOpen" if args.torch_net else "fused MFMA kernel"),
-        "data": "synthetic",
-        "config": {
-            "workload": "configs[%s]: %slego-like synthetic PlenOctree %s (%d nodes, depth %d), %dx%d SPP=%d%s, 1 step = %d launch groups of %d frames, frames sharded %s"
-                        % ({"c2": "1", "c4": "3 stand-in", "c5": "4"}.get(wid, "2" if n_scenes > 1 else "1-like"),
-                           ("%d scenes, " % n_scenes) if n_scenes > 1 else "",
-                           tree.data_format, tree.capacity, tree.max_depth, W, H, args.spp,
-                           " + GuidanceNet(8,32,5,2,4) denoise" if denoise else " raw (no denoise)", max(1, args.groups_per_step), B,
-                           "scene s -> rank s mod N" if (maps[0] == "scene" and n_scenes > 1) else "frame g -> rank g mod N"),
-            "tree_nodes": int(tree.capacity), "tree_device_mb": tree.device_bytes / 1e6,
-            "frames_per_step": FS, "groups_per_step": max(1, args.groups_per_step), "frames_per_group": B, "frames_timed": total_frames, "frames_per_launch": frames_per_launch, "streams": len(lanes),
-            "scenes": n_scenes, "scene_map": maps[0], "filter": "exact" if args.exact_filter else "factorised", "maps": "fp16 packed" if packed_route else "fp32 planes",
-            "parallelism": "frames x%d" % world,
-            # which clause of the north star each figure claims (VERDICT r4 task 4)
-            "value_route": ("render stage bit-exact against oracle/ (fp32 aux planes / RGBA8 of the noisy frame: parity_spot); denoise "
-                            "stage = fused fp16 GuidanceNet + %s" % ("the bit-exact filter" if (args.exact_filter or not packed_route) else
-                            "FACTORISED filter on packed fp16 maps: the TOLERANCE route (north star: 'within 1e-4 PSNR otherwise'; "
-                            "150 dB against the exact filter, psnr.rgba8_bytes_differing_factorised_vs_exact)")) if denoise else
-                           "raw render, bit-exact against oracle/",
-            "value_exact": exact_pass["value"] if exact_pass else None,  # the same frames through the bit-exact filter route
-            "reference_loop_fps": ref_loop["fps"] if ref_loop else None,  # the reference's loop shape: one launch + one host wait per frame
-            "reference_loop_pipelined_wall_fps": (ref_loop.get("pipelined") or {}).get("wall_fps") if ref_loop else None,
-            "value_full_outputs": full_pass["value"] if full_pass else None,  # ... storing all 48 B per pixel like volrend.cu:187-212
-            "value_single_stream": value_single,  # the headline route on ONE stream (the pass the per-kernel durations come from)
-            "streams_note": ("`value`, `value_exact`, `value_full_outputs`: launch groups alternate over %d streams (contexts), the tail of "
-                             "one group's kernels overlaps the next group's head; roofline.*_ms and reference_timer: a single-stream "
-                             "pass of the same frames (`value_single_stream`)" % NL) if NL > 1 else "one stream",
-            "lean_outputs": bool(lean),
-            "lean_level": (args.lean_level if lean else 0),  # 2: sparse -- the headline launches store nothing for the pixels of culled tiles
-            "world": world, "backend": (backend if world > 1 else None), "gpus_visible": n_dev,
-            "launcher": ("none" if world == 1 else "bench.py itself (child torch.distributed.run)"
-                         if os.environ.get("RTO_BENCH_SELF_LAUNCHED") else "external (torchrun)"),
-        },
+    out = dict(head, value_exact=exact_pass["value"] if exact_pass else None,
+               value_full_outputs=full_pass["value"] if full_pass else None, value_single_stream=value_single)
+    out["config"] = dict(
+        config,
+        value_exact=exact_pass["value"] if exact_pass else None,  # the same frames through the bit-exact filter route
+        reference_loop_fps=ref_loop["fps"] if ref_loop else None,  # the reference's loop shape: one launch + one host wait per frame
+        reference_loop_pipelined_wall_fps=(ref_loop.get("pipelined") or {}).get("wall_fps") if ref_loop else None,
+        value_full_outputs=full_pass["value"] if full_pass else None,  # ... storing all 48 B per pixel like volrend.cu:187-212
+        value_single_stream=value_single,  # the headline route on ONE stream (the pass the per-kernel durations come from)
+        streams_note=("`value`, `value_exact`, `value_full_outputs`: launch groups alternate over %d streams (contexts), the tail of "
+                      "one group's kernels overlaps the next group's head; roofline.*_ms and reference_timer: a single-stream "
+                      "pass of the same frames (`value_single_stream`)" % NL) if NL > 1 else "one stream",
+    )
+    out.update({
         "reference_timer": {  # Timer::report formula (render_context.hpp:190-206), rank 0, per frame
             "render_ms": tstats["render_ms"], "torch_ms": tstats["torch_ms"], "filter_ms": tstats["filter_ms"],
             "fps": tstats["fps"], "frames": tstats["frames"]},
@@ -1225,20 +1321,8 @@ def main():
         "roofline": roof,
         "psnr": psnr,
         "cpu_baseline": cpu,
-    }
-    def finite(o):  # strict JSON: no NaN / Infinity tokens in the driver's line
-        if isinstance(o, float):
-            return o if np.isfinite(o) else None
-        if isinstance(o, dict):
-            return {k: finite(v) for k, v in o.items()}
-        if isinstance(o, (list, tuple)):
-            return [finite(v) for v in o]
-        if isinstance(o, (np.floating, np.integer)):
-            return finite(o.item())
-        return o
-
-    print(json.dumps(finite(out), allow_nan=False))
-    sys.stdout.flush()
+    })
+    emit(out)
     if world > 1:
         dist.destroy_process_group()
 

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--batch", "4", "--groups-per-step", "1", "--size", "160",
-           "--depth", "6", "--cpu-frames", "1", "--psnr-frames", "2", "--ref-loop-frames", "4"]
+           "--depth", "6", "--cpu-frames", "1", "--psnr-frames", "2", "--ref-loop-frames", "4", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -76,6 +77,39 @@ def test_bench_line_has_the_contract_fields():
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
 
 
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """without --full the line holds the headline only (no pass of its own beside the timed one), and --dump-outputs writes
+    the frames of the last timed step -- float .npy files under 64 MB -- bit for bit the same from run to run"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--groups-per-step", "2",
+           "--size", "96", "--depth", "5"]
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / ("run%d" % k)
+        r = subprocess.run(cmd + ["--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["value"] > 0
+        assert abs(d["ms_per_step"] * d["value"] - 8000.0) < 8.0 and d["config"]["frames_timed"] == 24 and d["config"]["full"] is False
+        for key in ("roofline", "cpu_baseline", "parity_spot", "reference_loop", "psnr", "value_exact", "value_single_stream"):
+            assert key not in d, key
+        files = {f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+        assert set(files) == {"images_sampled.npy", "sample_pixels.npy", "sample_frames.npy", "image_last.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        img, pix, fr, last = (files[f] for f in ("images_sampled.npy", "sample_pixels.npy", "sample_frames.npy", "image_last.npy"))
+        # the last step = frames 16..23 (two launch groups of 4 on the two lanes), each at the same 8192 pixels
+        assert img.shape == (8, 8192, 4) and fr.tolist() == [[0.0, float(p)] for p in range(16, 24)] and last.shape == (96, 96, 4)
+        assert np.array_equal(last.reshape(-1, 4)[pix.astype(np.int64)], img[-1]) and np.isfinite(img).all() and np.any(img != 0)
+        dumps.append(files)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f].view(np.uint8), dumps[1][f].view(np.uint8)), f
+
+
 def test_counter_based_roofline_for_the_baseline_workloads():
     """profiles/pmc_traffic.json (what bench.py reads for `roofline.achieved`): counter passes for c2 / c5 / c4 and the
     gather ceilings; the counter-based HBM fraction of the default workload is far below the algorithmic one."""
@@ -134,7 +168,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--groups-per-step", "1",
-           "--size", "128", "--depth", "5", "--cpu-frames", "0", "--psnr-frames", "0", "--ref-loop-frames", "2"]
+           "--size", "128", "--depth", "5", "--cpu-frames", "0", "--psnr-frames", "0", "--ref-loop-frames", "2", "--full"]
     env = dict(os.environ, RTO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -183,7 +217,7 @@ def test_bench_gpus_2_without_torchrun_measures_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RTO_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--groups-per-step", "1",
-           "--size", "128", "--depth", "5", "--cpu-frames", "0", "--psnr-frames", "0", "--ref-loop-frames", "0"]
+           "--size", "128", "--depth", "5", "--cpu-frames", "0", "--psnr-frames", "0", "--ref-loop-frames", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 R=${1:-2}; shift; [ "$1" = "--" ] && shift
 for r in $(seq 1 $R); do
   for T in 832 1832 2832 3832 4832; do
-    python3 bench.py --tuning refill=$T --cpu-frames 0 --psnr-frames 0 --ref-loop-frames 0 --streams 1 --no-exact-pass --no-full-pass --count-frames 0 \
+    python3 bench.py --full --tuning refill=$T --cpu-frames 0 --psnr-frames 0 --ref-loop-frames 0 --streams 1 --no-exact-pass --no-full-pass --count-frames 0 \
       --spot-pixels 16 --steps 6 --warmup 2 --groups-per-step 1 "$@" 2>/dev/null | python3 -c "
 import json, sys
 for l in sys.stdin:

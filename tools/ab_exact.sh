@@ -4,7 +4,7 @@
 R=${1:-2}; shift
 for r in $(seq 1 $R); do
   for L in "$@"; do
-    RTO_LIB=$PWD/$L python3 bench.py --cpu-frames 0 --psnr-frames 0 --ref-loop-frames 0 --no-full-pass --count-frames 0 --spot-pixels 16 \
+    RTO_LIB=$PWD/$L python3 bench.py --full --cpu-frames 0 --psnr-frames 0 --ref-loop-frames 0 --no-full-pass --count-frames 0 --spot-pixels 16 \
       --streams 1 --steps 4 --warmup 1 --groups-per-step 2 2>/dev/null | python3 -c "
 import json, sys
 for l in sys.stdin:

@@ -15,7 +15,7 @@ for a in it:
     else:
         vals.append(int(a))
 for D in vals or [2, 4, 8]:
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-frames", "0", "--psnr-frames", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-frames", "0", "--psnr-frames", "0",
            "--count-frames", "0", "--spot-pixels", "0", "--no-exact-pass", "--ref-loop-frames", "96", "--ref-loop-inflight", str(D)] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
