@@ -47,7 +47,7 @@ extern "C" {
 #define RTO_OK 0
 #define RTO_E_INVALID -1     /* bad argument */
 #define RTO_E_SPP -2         /* spp not in {1,2,3,4,6,8,16,32} (volrend.cu:266-278) */
-#define RTO_E_UNSUPPORTED -3 /* feature outside the headless path (probe, SG/ASG) */
+#define RTO_E_UNSUPPORTED -3 /* feature outside the headless path (GUI probe), or a combination not built (e.g. SG/ASG + QUANT_DIRECT) */
 #define RTO_E_HIP -4         /* HIP runtime error / no device */
 #define RTO_E_IO -5          /* file missing / malformed */
 #define RTO_E_FORMAT -6      /* npz content violates the tree schema (n3tree.cpp:283-291,345) */
@@ -166,12 +166,23 @@ int rto_tree_from_arrays(const int32_t* child, const uint16_t* data, int64_t cap
 int rto_tree_from_arrays_ex(const int32_t* child, const uint16_t* data, int64_t capacity, int N,
                             int data_dim, const char* data_format, const float scale[3],
                             const float offset[3], int device, int flags, rto_tree** out);
+/* the same with the lobes of an SG / ASG tree (the npz's extra_data, n3tree.cpp:350-353; TreeSpec::extra,
+ * data_spec.hpp:30): extra_floats = basis_dim * 4 floats {lambda, mu_x, mu_y, mu_z} per lobe (SG) or basis_dim * 11
+ * {lambda_x, lambda_y, mu_x[3], mu_y[3], mu_z[3]} (ASG), all finite, else RTO_E_FORMAT.  Ignored for SH and RGBA trees.
+ * An SG / ASG tree uploaded without lobes (extra = NULL) loads, and every launch of it returns RTO_E_FORMAT. */
+int rto_tree_from_arrays_extra(const int32_t* child, const uint16_t* data, int64_t capacity, int N,
+                               int data_dim, const char* data_format, const float scale[3],
+                               const float offset[3], int device, int flags, const float* extra,
+                               int64_t extra_floats, rto_tree** out);
 /* main_headless.cpp:400-405 (llff): switch the NDC warp on. width <= 0 turns it off. */
 int rto_tree_set_ndc(rto_tree* t, float ndc_width, float ndc_height, float ndc_focal);
 int rto_tree_get_info(const rto_tree* t, rto_tree_info* info);
 /* Host-only: runs the same npz parsing + N3Tree::load_npz decode as rto_tree_load_npz (no device
  * needed) and writes a JSON description into json_out: schema fields plus FNV-1a-64 checksums of
- * the child[] and (decoded) data[] arrays.  Returns RTO_E_INVALID if `cap` is too small. */
+ * the child[] and (decoded) data[] arrays, and for an SG / ASG tree "extra_shape" / "extra_fnv1a64" of its
+ * lobes (null without lobes, and for SH / RGBA trees, whose extra_data is ignored).  Malformed lobes -- not
+ * float32, not basis_dim * 4 (SG) / * 11 (ASG) values shaped [basis_dim, 4 / 11] or flat, not finite -- give
+ * RTO_E_FORMAT here and in rto_tree_load_npz.  Returns RTO_E_INVALID if `cap` is too small. */
 int rto_tree_probe_npz(const char* path, char* json_out, size_t cap);
 void rto_tree_free(rto_tree* t);
 
@@ -459,6 +470,12 @@ int rto_probe_math(int fn, uint32_t first_bits, uint32_t stride, uint32_t count,
  * halves selected by cnt 1 .. 16) or first_bits + 4099 i (mode 3; times halves 2048 (cnt - 1) .. 2048 cnt - 1: all 65536 over
  * cnt 1 .. 32), in both packed positions. */
 int rto_probe_sigmoid(int mode, uint32_t first_bits, uint64_t count, int cnt_lo, int cnt_hi, uint64_t* out3);
+/* Test hook: host_out[i][0..24] = the basis the kernels evaluate for the tree and options at view direction dirs[i][3] (the
+ * ray's unit direction before the rot_dirs rotation; rt_core.cuh:277-284, lumisphere.hpp:14-80) -- rotation, basis and the
+ * basis_minmax mask -- computed on the device by the kernels' own code.  path 0: the run-time form (generic and fast kernels,
+ * the shading kernel's mode 0); path 1: the per-basis-size form the shading kernel uses for its record modes (SG / ASG any
+ * basis_dim, SH 4 / 9 / 16 / 25, else RTO_E_UNSUPPORTED), whose entries from basis_dim on are 0. */
+int rto_probe_basis(const rto_tree* tree, const rto_options* options, const float* dirs, int64_t n, int path, float* host_out);
 
 #ifdef __cplusplus
 }

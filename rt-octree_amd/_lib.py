@@ -63,6 +63,9 @@ SYMBOLS = {
     "rto_tree_from_arrays_ex": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p,
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                           C.POINTER(_P)]),
+    "rto_tree_from_arrays_extra": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p,
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                             _P, C.c_int64, C.POINTER(_P)]),
     "rto_tree_set_ndc": (C.c_int, [_P, C.c_float, C.c_float, C.c_float]),
     "rto_tree_get_info": (C.c_int, [_P, C.POINTER(CTreeInfo)]),
     "rto_tree_probe_npz": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
@@ -128,6 +131,7 @@ SYMBOLS = {
     "rto_probe_thresholds": (C.c_int, [C.c_uint32, C.c_uint32, _P]),
     "rto_probe_math": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     "rto_probe_sigmoid": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "rto_probe_basis": (C.c_int, [_P, C.POINTER(COptions), _P, C.c_int64, C.c_int, _P]),
     "rto_timer_reset": (C.c_int, [_P, _P]),
     "rto_timer_start": (C.c_int, [_P, C.c_int]),
     "rto_timer_stop": (C.c_int, [_P, C.c_int]),

@@ -250,6 +250,26 @@ bool HostTree::open(const std::string& path, bool keep_quantized) {
     }
     if ((int64_t)ch.shape[0] < capacity) throw std::runtime_error("tree.npz: child has fewer nodes than data");
 
+    // ---- SG / ASG lobes n3tree.cpp:350-353 (the reference reinterprets the raw bytes as float: anything else is refused) ----
+    if (lobe_floats(data_format.format) && z.has("extra_data")) {
+        const NpyArray& e = z.at("extra_data");
+        const int64_t want = (int64_t)data_format.basis_dim * lobe_floats(data_format.format);
+        if (!(e.kind == 'f' && e.word_size == 4))
+            throw std::runtime_error("tree.npz: extra_data must be float32 (found " + e.descr + ")");
+        const bool flat = e.shape.size() == 1;
+        const bool rows = e.shape.size() == 2 && !e.fortran_order && (int64_t)e.shape[0] == data_format.basis_dim &&
+                          (int64_t)e.shape[1] == lobe_floats(data_format.format);
+        if (!flat && !rows)
+            throw std::runtime_error("tree.npz: extra_data of a " + data_format.to_string() + " tree must be C-ordered [" +
+                                     std::to_string(data_format.basis_dim) + "," + std::to_string(lobe_floats(data_format.format)) +
+                                     "] or flat");
+        const std::string bad = check_lobes(data_format, e.as<float>(), (int64_t)e.num_vals());
+        if (!bad.empty()) throw std::runtime_error("tree.npz: " + bad);
+        extra = e.as<float>();
+        extra_floats = want;
+        extra_shape = e.shape;
+    }
+
     // ---- NDC side file n3tree.cpp:131-148 ----
     const std::string pb_path = path.substr(0, path.size() - 4) + "_poses_bounds.npy";
     use_ndc = bool(std::ifstream(pb_path));
@@ -259,6 +279,18 @@ bool HostTree::open(const std::string& path, bool keep_quantized) {
         unpack_llff(pb, *this);
     }
     return true;
+}
+
+int lobe_floats(int format) { return format == RTO_FMT_SG ? 4 : format == RTO_FMT_ASG ? 11 : 0; }
+
+std::string check_lobes(const DataFormat& fmt, const float* extra, int64_t n) {
+    const int64_t want = (int64_t)fmt.basis_dim * lobe_floats(fmt.format);
+    if (n != want)
+        return "extra_data of a " + fmt.to_string() + " tree must hold " + std::to_string(want) + " floats (" +
+               std::to_string(fmt.basis_dim) + " lobes of " + std::to_string(lobe_floats(fmt.format)) + "), found " + std::to_string(n);
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(extra[i])) return "extra_data value " + std::to_string(i) + " is not finite";
+    return "";
 }
 
 int tree_max_depth(const int32_t* child, int64_t capacity, int N) {

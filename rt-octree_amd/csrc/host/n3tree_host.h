@@ -40,6 +40,13 @@ struct HostTree {
     const uint16_t* q_sigma = nullptr;     // fp16 [capacity*N^3]
     const uint16_t* q_retained = nullptr;  // fp16 [n_retain][capacity*N^3][3]
 
+    // SG / ASG lobes: extra_data of the file (n3tree.cpp:350-353), float32, basis_dim x 4 (SG) or x 11 (ASG) values, shaped
+    // [basis_dim, 4 / 11] or flat (extra_shape as stored).  nullptr when the file has none -- or when the tree is SH / RGBA,
+    // whose extra_data the reference loads and never reads: it is not read here either
+    const float* extra = nullptr;
+    int64_t extra_floats = 0;
+    std::vector<size_t> extra_shape;
+
     // keep-alives
     std::shared_ptr<NpzFile> npz;
     std::vector<uint16_t> decoded;  // quantised trees are expanded here
@@ -52,5 +59,11 @@ struct HostTree {
 // deepest leaf level (number of child[] loads to reach it), validating every offset on the way;
 // throws std::runtime_error on an out-of-range child
 int tree_max_depth(const int32_t* child, int64_t capacity, int N);
+
+// floats per lobe record of an SG (4) / ASG (11) basis (lumisphere.hpp:14-37); 0 for SH and RGBA
+int lobe_floats(int format);
+// "" when `extra` (n floats) holds valid lobes for the format -- basis_dim * lobe_floats(format) finite values --
+// else what is wrong with them
+std::string check_lobes(const DataFormat& fmt, const float* extra, int64_t n);
 
 }  // namespace rto

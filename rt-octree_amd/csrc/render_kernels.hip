@@ -184,12 +184,9 @@ RTO_DEV void sh_basis(int basis_dim, const float* dir, float* out) {
     }
 }
 
-// basis for the ray + the basis_minmax mask (rt_core.cuh:277-284)
-RTO_DEV void ray_basis(const TreeDev& tree, const OptDev& opt, const float* vdir_in, float* basis_fn) {
-#pragma unroll
-    for (int i = 0; i < RTO_BASIS_MAX_DEV; ++i) basis_fn[i] = 0.f;
-    float vdir[3] = {vdir_in[0], vdir_in[1], vdir_in[2]};
-    if (opt.rot_on) {  // rodrigues (volrend.cu:58-73): only the view direction of the SH lookup turns
+// rodrigues (volrend.cu:58-73): only the view direction of the basis lookup turns
+RTO_DEV void rotate_vdir(const OptDev& opt, float* vdir) {
+    if (opt.rot_on) {
         const float* k = opt.rot_k;
         const float cross[3] = {k[1] * vdir[2] - k[2] * vdir[1], k[2] * vdir[0] - k[0] * vdir[2],
                                 k[0] * vdir[1] - k[1] * vdir[0]};
@@ -198,10 +195,48 @@ RTO_DEV void ray_basis(const TreeDev& tree, const OptDev& opt, const float* vdir
         for (int i = 0; i < 3; ++i)  // float + float, then + (float * float) * double in double, one rounding
             vdir[i] = (float)((double)(vdir[i] * opt.rot_cos + cross[i] * opt.rot_sin) + (double)(k[i] * dot) * opt.rot_omc);
     }
-    if (tree.format == 1 /*SH*/) sh_basis(tree.basis_dim, vdir, basis_fn);
+}
+
+// basis function i of an SG / ASG tree (LOBES = kFmtSG / kFmtASG) for the rotated view direction d; fB = (float)basis_dim
+template <int LOBES>
+RTO_DEV float lobe_basis(const TreeDev& tree, int i, const float* d, float fB) {
+    const RTO_CONST float* lobes = (const RTO_CONST float*)tree.extra;
+    if constexpr (LOBES == kFmtSG)
+        return sg_lobe(d, lobes + 4 * i, fB);
+    else
+        return asg_lobe(d, lobes + 11 * i, fB);
+}
+
+// basis for the ray + the basis_minmax mask (rt_core.cuh:277-284).  LOBES = 0: SH and RGBA trees (the format is read at run
+// time); kFmtSG / kFmtASG: a tree of that format -- a template argument, so that the SH instantiations carry no lobe code
+template <int LOBES = 0>
+RTO_DEV void ray_basis(const TreeDev& tree, const OptDev& opt, const float* vdir_in, float* basis_fn) {
+#pragma unroll
+    for (int i = 0; i < RTO_BASIS_MAX_DEV; ++i) basis_fn[i] = 0.f;
+    float vdir[3] = {vdir_in[0], vdir_in[1], vdir_in[2]};
+    rotate_vdir(opt, vdir);
+    if constexpr (LOBES != 0) {
+        const int B = tree.basis_dim;
+        const float fB = (float)B;  // (maybe_precalc_basis divides by the int basis_dim)
+#pragma unroll
+        for (int i = 0; i < RTO_BASIS_MAX_DEV; ++i)
+            if (i < B) basis_fn[i] = lobe_basis<LOBES>(tree, i, vdir, fB);
+    } else {
+        if (tree.format == kFmtSH) sh_basis(tree.basis_dim, vdir, basis_fn);
+    }
 #pragma unroll
     for (int i = 0; i < RTO_BASIS_MAX_DEV; ++i)
         if (i < opt.basis_minmax[0] || i > opt.basis_minmax[1]) basis_fn[i] = 0.f;
+}
+
+// ray_basis for any tree, the format read at run time (the generic kernel, the basis probe)
+RTO_DEV void ray_basis_any(const TreeDev& tree, const OptDev& opt, const float* vdir_in, float* basis_fn) {
+    if (tree.format == kFmtSG)
+        ray_basis<kFmtSG>(tree, opt, vdir_in, basis_fn);
+    else if (tree.format == kFmtASG)
+        ray_basis<kFmtASG>(tree, opt, vdir_in, basis_fn);
+    else
+        ray_basis(tree, opt, vdir_in, basis_fn);
 }
 
 // ray_basis for a tree KNOWN to hold B SH basis functions per channel (the shading kernel's record layouts): the same values in
@@ -210,20 +245,27 @@ RTO_DEV void ray_basis(const TreeDev& tree, const OptDev& opt, const float* vdir
 template <int B>
 RTO_DEV void ray_basis_sh(const OptDev& opt, const float* vdir_in, float* basis_fn) {
     float vdir[3] = {vdir_in[0], vdir_in[1], vdir_in[2]};
-    if (opt.rot_on) {  // (as in ray_basis)
-        const float* k = opt.rot_k;
-        const float cross[3] = {k[1] * vdir[2] - k[2] * vdir[1], k[2] * vdir[0] - k[0] * vdir[2],
-                                k[0] * vdir[1] - k[1] * vdir[0]};
-        const float dot = k[0] * vdir[0] + k[1] * vdir[1] + k[2] * vdir[2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            vdir[i] = (float)((double)(vdir[i] * opt.rot_cos + cross[i] * opt.rot_sin) + (double)(k[i] * dot) * opt.rot_omc);
-    }
+    rotate_vdir(opt, vdir);
     float full[RTO_BASIS_MAX_DEV];
     sh_basis(B, vdir, full);  // (B is a constant: the switch folds)
 #pragma unroll
     for (int i = 0; i < B; ++i) basis_fn[i] = full[i];
     if (opt.basis_minmax[0] > 0 || opt.basis_minmax[1] < B - 1) {  // (uniform; the default options mask nothing)
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+            if (i < opt.basis_minmax[0] || i > opt.basis_minmax[1]) basis_fn[i] = 0.f;
+    }
+}
+
+// The same for an SG / ASG tree KNOWN to hold B lobes (LOBES = kFmtSG / kFmtASG; the shading kernel's record layouts, B = 9 /
+// 16 / 25): ray_basis<LOBES>'s values in basis_fn[0 .. B-1], each lobe record at a constant offset of the kernel argument
+template <int LOBES, int B>
+RTO_DEV void ray_basis_lobes(const TreeDev& tree, const OptDev& opt, const float* vdir_in, float* basis_fn) {
+    float vdir[3] = {vdir_in[0], vdir_in[1], vdir_in[2]};
+    rotate_vdir(opt, vdir);
+#pragma unroll
+    for (int i = 0; i < B; ++i) basis_fn[i] = lobe_basis<LOBES>(tree, i, vdir, (float)B);
+    if (opt.basis_minmax[0] > 0 || opt.basis_minmax[1] < B - 1) {
 #pragma unroll
         for (int i = 0; i < B; ++i)
             if (i < opt.basis_minmax[0] || i > opt.basis_minmax[1]) basis_fn[i] = 0.f;
@@ -382,7 +424,7 @@ __global__ void __launch_bounds__(256) render_generic(const TreeDev tree, const 
             }
             if (sh_nums != 0) {
                 float basis_fn[RTO_BASIS_MAX_DEV];
-                ray_basis(tree, opt, vdir, basis_fn);
+                ray_basis_any(tree, opt, vdir, basis_fn);
                 for (uint32_t i = 0; i < sh_nums; i++)
                     shade_leaf(tree, tree.data + tree_vals[i] * tree.data_dim, basis_fn, cnts[i], out);
                 constexpr float INV_SPP = 1.0f / SPP;
@@ -663,305 +705,22 @@ RTO_DEV uint32_t wide_entry_of(const TreeDev& tree, uint32_t ix, uint32_t iy, ui
 // register-stack form -- the node a step starts from is chosen by where the ray is and which coordinate bits changed
 // (rto_march_leaf.inc), positions are kept scaled by 2^24 (kPos24), the step's power-of-two factors come from the level bits of
 // the leaf word -- seven dependent instructions fewer on the chain a lone frame's longest rays wait for
+// The body (rto_render_fast.inc) serves two kernels: render_fast for SH and RGBA trees and render_fast_lobes for SG / ASG trees
+// (LOBES = kFmtSG / kFmtASG, see ray_basis), so that the SH kernels keep their names and their code.
 template <int SPP, bool STATS, bool WIDE, int STACK = 0>
 __global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast(const TreeDev tree, const CamDev cam, const OptDev opt,
                                                     const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
                                                     const TileMap tm, const FrameOut fo) {
-    extern __shared__ uint32_t s_stack[];  // [max_depth][256] ancestor node indices, level-major
+    constexpr int LOBES = 0;
+#include "rto_render_fast.inc"
+}
 
-    int tx, ty;
-    if (!block_tile(tm, blockIdx.x, tx, ty)) return;
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int x = tx * kTileW + wave * 8 + (lane & 7);
-    const int y = ty * kTileH + (lane >> 3);
-    if (x >= cam.width || y >= cam.height) return;
-    const int64_t SIZE = (int64_t)cam.width * cam.height;
-    const int idx = y * cam.width + x;
-
-    float out[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!STATS && fo.cull_marks) {  // (wave-uniform: a wave is one 8x8 tile)
-        const uint32_t t = (uint32_t)(y >> 3) * ((uint32_t)(cam.width + 7) >> 3) + (uint32_t)(x >> 3);
-        if (!(((fo.cull_marks[t >> 5] >> (t & 31u)) | fo.cull_marks[fo.cull_mask_words - 1]) & 1u)) {
-            write_pixel(fo, SIZE, idx, opt.background_brightness, out);  // no ray of this tile meets density: background
-            return;
-        }
-    }
-    float dir[3], vdir[3], cen[3], invdir[3];
-    ray_setup(x, y, cam, tree, dir, vdir, cen);
-    float delta_scale, tmin, tmax;
-    unsigned long long st_steps = 0, st_levels = 0, st_hits = 0, st_inbox = 0, st_grid = 0, st_words = 0, st_wide = 0;
-    if (ray_enter(tree, opt, dir, cen, 1e9f, invdir, delta_scale, tmin, tmax)) {
-        if (STATS) st_inbox = 1;
-        Pcg32 rng = rng_base;
-        pcg_advance_tab(rng, (uint32_t)(idx * SPP), jump);
-
-        // thresholds, ascending; dst[0] is always the next one to cross (consumed ones shift out)
-        float dst[SPP + 1];
-#pragma unroll
-        for (int n = 0; n < SPP; ++n) {
-            float tv = -det_log_one_minus(pcg_next_float(rng));
-#pragma unroll
-            for (int i = 0; i < n; ++i) {  // static-index insertion: same sorted array
-                const float lo = __builtin_fminf(dst[i], tv), hi = __builtin_fmaxf(dst[i], tv);  // (see sample_kernel)
-                dst[i] = lo;
-                tv = hi;
-            }
-            dst[n] = tv;
-        }
-        dst[SPP] = 3.402823466e+38f;
-
-        uint32_t hits[SPP];
-#pragma unroll
-        for (int i = 0; i < SPP; ++i) hits[i] = 0;
-        uint32_t spp = 0, sh_nums = 0;
-        float src = 0;
-        float t = tmin;
-
-        uint32_t pix = 0, piy = 0, piz = 0;
-        int prev_lvl = 0;
-        uint32_t* stack = s_stack + tid;
-        const int G = tree.top_levels;  // 0: no top grid
-        if (WIDE && G == 0) stack[0] = 0u;
-        uint32_t stk0 = 0u, stk1 = 0u;
-        const bool regstack = WIDE && (tree.max_depth - G + 1) / 2 <= 2;  // (uniform) pairs of levels below the grid
-        const float exit_add[3] = {invdir[0] > 0.f ? invdir[0] : 0.f, invdir[1] > 0.f ? invdir[1] : 0.f, invdir[2] > 0.f ? invdir[2] : 0.f};
-        static_assert(STACK == 0 || (WIDE && !STATS), "the register-stack restart is for the two-level image");
-        // STACK == 1: the node / bit offset / bits per axis the NEXT step starts from (render_persist's rs.node, rs.woff, rs.wb)
-        uint32_t cnode = 0u, coff = 24u - (uint32_t)G, cb = (uint32_t)G;
-        const uint32_t tgrid = 1u << (24 - G);
-        if constexpr (STACK == 1) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {  // (kPos24)
-                cen[i] *= kPos24;
-                dir[i] *= kPos24;
-            }
-        }
-
-        while (t < tmax) {
-            // (round 5: the arithmetic forms of the batched kernel's march step -- one v_med3 per clamp, v_fract, the exit
-            //  time as t1 + (invdir > 0 ? invdir : 0), no 1e4 start of the minimum: see rto_march_leaf.inc for why each is the
-            //  same number -- a lone frame waits for the DEPENDENT chain of its longest ray, a third of which is this arithmetic:
-            //  0.307 -> 0.295 ms per lone 800x800 SPP-6 frame, profiles/r5_w_ab_fast.txt)
-            float pos[3];
-            uint32_t ix, iy, iz;
-            if constexpr (STACK == 1) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) pos[i] = clamp_unit24(cen[i] + t * dir[i]);
-                ix = (uint32_t)pos[0];
-                iy = (uint32_t)pos[1];
-                iz = (uint32_t)pos[2];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) pos[i] = clamp_unit(cen[i] + t * dir[i]);
-                ix = (uint32_t)(pos[0] * 16777216.f);
-                iy = (uint32_t)(pos[1] * 16777216.f);
-                iz = (uint32_t)(pos[2] * 16777216.f);
-            }
-            // levels whose child digit is unchanged since the previous step
-            const uint32_t diff = (ix ^ pix) | (iy ^ piy) | (iz ^ piz);
-            int lvl = 0;
-            if constexpr (STACK != 1) {
-                lvl = __clz((int)diff) - 8;
-                lvl = lvl < prev_lvl ? lvl : prev_lvl;
-            }
-            uint32_t node, w, slot;
-            bool have_w = false;
-            if constexpr (STACK == 1) {
-                // (see rto_march_leaf.inc: the same node while the bits above its index bits are unchanged; back to the grid when a
-                //  bit at or above 24 - G differs; else, from the second pair, the first pair's node)
-                const bool stay = (diff >> (coff + cb)) == 0u, to_grid = diff >= tgrid;
-                node = to_grid ? 0u : (stay ? cnode : stk0);
-                uint32_t off = to_grid ? 24u - (uint32_t)G : (stay ? coff : 22u - (uint32_t)G);
-                uint32_t b = to_grid ? (uint32_t)G : cb;
-                for (;;) {
-                    slot = (node << b) | __builtin_amdgcn_ubfe(ix, off, b);
-                    slot = (slot << b) | __builtin_amdgcn_ubfe(iy, off, b);
-                    slot = (slot << b) | __builtin_amdgcn_ubfe(iz, off, b);
-                    w = *(const uint32_t*)((const char*)tree.widew + (uint32_t)(slot << 2));  // (< 2^29 entries: a 32-bit byte offset)
-                    if (nodew_is_leaf(w)) break;
-                    stk0 = off == 24u - (uint32_t)G ? w : stk0;  // (the first pair's node: the one ancestor a later step may need)
-                    node = w;  // the wide node two levels down
-                    off -= 2u;
-                    b = 2u;
-                }
-                cnode = node;
-                coff = off;
-                cb = b;
-                (void)have_w;
-                (void)stk1;
-            } else if constexpr (WIDE) {
-                // the two-level image (rto_abi.cpp build_wide_image; round 4): one load per TWO levels below the grid -- a lone
-                // frame waits for the dependent-load chains of its longest rays, and this shortens every one of them
-                // (node, off): (0, 24 - G) = the top grid, whose cells are indexed by G bits per axis; else the wide node of the
-                // pair (G + 2 pr, G + 2 pr + 1), two bits per axis from bit 22 - G - 2 pr on.  One array holds both.
-                // With two pairs of levels below the grid at most (regstack: a tree of depth <= G + 4) the ancestor stack is two
-                // registers: no LDS round trip on the dependent chain of a step.
-                int pr = -1;
-                node = 0u;
-                if (lvl >= G) {
-                    pr = (lvl - G) >> 1;
-                    node = regstack ? (pr ? stk1 : stk0) : stack[pr * 256];
-                    if (node == 0u) pr = -1;  // (no grid levels, first step: the stack still holds the 0 it was given)
-                }
-                for (;;) {
-                    const uint32_t b = node ? 2u : (uint32_t)G, msk = (1u << b) - 1u;
-                    const uint32_t off = node ? (uint32_t)(22 - G - 2 * pr) : 24u - (uint32_t)G;
-                    slot = (((node << b | ((ix >> off) & msk)) << b | ((iy >> off) & msk)) << b) | ((iz >> off) & msk);
-                    w = *(const uint32_t*)((const char*)tree.widew + (uint32_t)(slot << 2));  // (< 2^29 entries: a 32-bit byte offset)
-                    if (nodew_is_leaf(w)) break;
-                    node = w;  // the wide node two levels down
-                    ++pr;
-                    if (regstack) {
-                        stk0 = pr == 0 ? node : stk0;
-                        stk1 = pr == 0 ? stk1 : node;
-                    } else {
-                        stack[pr * 256] = node;
-                    }
-                }
-                (void)have_w;
-                lvl = (int)((w >> kWideLevelShift) & 31u);  // a leaf word of the wide image carries its level
-            } else {
-            if (lvl < G) {
-                // restart above the shortcut levels: ONE 8-byte lookup replaces the walk over node levels
-                // 0..G-1 (a chain of dependent loads -- what a lone frame's long rays wait for) and
-                // already carries the word of the slot where that walk ends
-                const uint32_t gs = 24u - (uint32_t)G;
-                const uint32_t key = (((ix >> gs) << G | (iy >> gs)) << G) | (iz >> gs);
-                const uint2 e = tree.topgrid[key];
-                slot = e.x & kGridSlotMask;
-                lvl = (int)(e.x >> kGridSlotBits);
-                node = slot >> 3;
-                w = e.y;
-                have_w = true;
-                if (STATS) ++st_grid;
-            } else {
-                node = lvl ? stack[lvl * 256] : 0u;
-            }
-            int st_pair = -1;  // STATS: the pair of levels whose wide node the two-level image would have loaded last
-            for (;;) {
-                if (!have_w) {
-                    const int sh = 23 - lvl;
-                    const uint32_t ci = (((ix >> sh) & 1u) << 2) | (((iy >> sh) & 1u) << 1) | ((iz >> sh) & 1u);
-                    slot = node * 8u + ci;
-                    w = tree.nodew[slot];
-                    if (STATS) {
-                        ++st_words;
-                        // render_persist on the two-level image loads ONE entry per pair of levels (G + 2p, G + 2p + 1)
-                        const int pr = (lvl - G) >> 1;
-                        if (pr != st_pair) ++st_wide;
-                        st_pair = pr;
-                    }
-                }
-                have_w = false;
-                if (nodew_is_leaf(w)) break;
-                node += w;  // two's complement add of the relative offset
-                ++lvl;
-                stack[lvl * 256] = node;
-            }
-            }
-            pix = ix;
-            piy = iy;
-            piz = iz;
-            prev_lvl = lvl;
-            if (STATS) {
-                ++st_steps;
-                st_levels += (unsigned)(lvl + 1);
-            }
-
-            // cube_sz = 2^(lvl+1) and its reciprocal straight from exponent bits; x / 2^k == x * 2^-k
-            // bit for bit (a pure exponent shift, or the same single rounding into the denormals)
-            float cube_sz, inv_cube;
-            if constexpr (STACK == 1) {  // (positions scaled by 2^24: 2^(level + 1 - 24); the level at the word's exponent bits)
-                const uint32_t lvl_bits = w & kWideLevelMask;
-                cube_sz = __uint_as_float(lvl_bits + ((uint32_t)(128 - 24) << 23));
-                inv_cube = __uint_as_float(((uint32_t)126 << 23) - lvl_bits);
-            } else {
-                cube_sz = __uint_as_float((uint32_t)(128 + lvl) << 23);
-                inv_cube = __uint_as_float((uint32_t)(126 - lvl) << 23);
-            }
-            float ex[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) ex[i] = -__builtin_amdgcn_fractf(pos[i] * cube_sz) * invdir[i] + exit_add[i];
-            const float t_subcube = __builtin_fminf(__builtin_fminf(ex[0], ex[1]), ex[2]) * inv_cube;
-            const float delta_t = t_subcube + opt.step_size;
-            const float sigma = half_bits_to_float((uint16_t)(w & 0xffffu));
-            if (sigma > opt.sigma_thresh) {
-                const float delta = delta_t * delta_scale * sigma;
-                if (src + delta >= dst[0]) {
-                    uint32_t cnt = 0;
-                    do {
-                        ++cnt;
-                        ++spp;
-#pragma unroll
-                        for (int i = 0; i < SPP; ++i) dst[i] = dst[i + 1];
-                    } while (src + delta >= dst[0]);
-                    // (the counting instantiation walks the one-level image; a tree whose records follow the two-level image's
-                    //  entries needs the leaf's entry there: found by that image's walk -- this kernel is never timed)
-                    const uint32_t h = hit_pack<SPP>(!WIDE && tree.rec_by_entry ? wide_entry_of(tree, ix, iy, iz) : slot, cnt);
-#pragma unroll
-                    for (int i = 0; i < SPP; ++i) hits[i] = (i == (int)sh_nums) ? h : hits[i];
-                    ++sh_nums;
-                    if (spp == SPP) break;
-                }
-                src += delta;
-            }
-            t += delta_t;
-        }
-
-        if (STATS) st_hits = sh_nums;
-        if (sh_nums != 0) {
-            float basis_fn[RTO_BASIS_MAX_DEV];
-            ray_basis(tree, opt, vdir, basis_fn);
-#pragma unroll
-            for (int i = 0; i < SPP; ++i) {
-                if (i < (int)sh_nums) {
-                    uint32_t slot = hit_slot<SPP>(hits[i]);
-                    if constexpr (WIDE)
-                        if (!tree.rec_by_entry) slot = wide_to_slot(tree, slot);  // hit index of the wide image -> the leaf's slot
-                    const float cnt = (float)hit_count<SPP>(hits[i]);
-                    if (tree.format == 1 && tree.data_dim == 28)
-                        shade_leaf_packed<28>(tree, slot, basis_fn, cnt, out);
-                    else if (tree.format == 1 && tree.data_dim == 49)
-                        shade_leaf_packed<49>(tree, slot, basis_fn, cnt, out);
-                    else if (tree.format == 1 && tree.data_dim == 76)
-                        shade_leaf_packed<76>(tree, slot, basis_fn, cnt, out);
-                    else
-                        shade_leaf(tree, tree.data + (uint64_t)slot * tree.data_dim, basis_fn, cnt, out);
-                }
-            }
-            constexpr float INV_SPP = 1.0f / SPP;
-            out[0] *= INV_SPP;
-            out[1] *= INV_SPP;
-            out[2] *= INV_SPP;
-            out[3] *= INV_SPP;
-        }
-    }
-    write_pixel(fo, SIZE, idx, opt.background_brightness, out);
-    if (STATS) {  // order as orc_stats: rays, rays_in_box, steps, levels, hit_leaves, hit_rays
-        atomicAdd(fo.stats + 0, 1ULL);
-        atomicAdd(fo.stats + 1, st_inbox);
-        atomicAdd(fo.stats + 2, st_steps);
-        atomicAdd(fo.stats + 3, st_levels);
-        atomicAdd(fo.stats + 4, st_hits);
-        atomicAdd(fo.stats + 5, st_hits ? 1ULL : 0ULL);
-        // the same ray as the batched path sees it: marched only if its 8x8 tile is marked (mark_tiles_kernel); one
-        // top-grid entry or one traversal-image word per node visit is exactly what render_persist loads (same restart rule)
-        bool marched = true;
-        if (fo.stat_marks) {
-            const uint32_t t = (uint32_t)(y >> 3) * ((uint32_t)(cam.width + 7) >> 3) + (uint32_t)(x >> 3);
-            marched = ((fo.stat_marks[t >> 5] >> (t & 31u)) | fo.stat_marks[fo.stat_mask_words - 1]) & 1u;
-        }
-        if (marched) {
-            atomicAdd(fo.stats + 6, 1ULL);
-            atomicAdd(fo.stats + 7, st_steps);
-            atomicAdd(fo.stats + 8, st_grid);
-            atomicAdd(fo.stats + 9, st_words);
-            atomicAdd(fo.stats + 10, st_hits);
-            atomicAdd(fo.stats + 11, st_inbox);
-            atomicAdd(fo.stats + 12, st_wide);
-        }
-    }
+// the single-frame kernel of an SG / ASG tree (LOBES = kFmtSG / kFmtASG): the same body under its own name
+template <int SPP, bool STATS, bool WIDE, int STACK, int LOBES>
+__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_lobes(const TreeDev tree, const CamDev cam, const OptDev opt,
+                                                          const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
+                                                          const TileMap tm, const FrameOut fo) {
+#include "rto_render_fast.inc"
 }
 
 // ------------------------------------------------------------------ persistent kernel (N == 2)
@@ -1784,7 +1543,8 @@ constexpr int kShadeCap = RTO_SHADE_CAP;
 
 // contribution of one hit leaf: rgb[c] = cnt * sigmoid(<basis, coeffs_c>) (or cnt * rgb for RGBA trees)
 // MODE (host-chosen, so that each instantiation carries one leaf layout's registers only):
-// 0 any dense tree; 28 / 49 / 76 dense SH9 / SH16 / SH25 records; -B quantised SH<B>, not expanded
+// 0 any dense tree; 28 / 49 / 76 dense SH9 / SH16 / SH25 records (or SG / ASG records of the same data_dim: the layout does
+// not depend on the basis); -B quantised SH<B>, not expanded
 template <int MODE>
 RTO_DEV void leaf_contrib(const TreeDev& tree, uint32_t slot, const float* basis_fn, float cnt, float* o) {
     o[0] = o[1] = o[2] = o[3] = 0.f;  // 0 + x == x: the helpers' "+=" yields the bare term
@@ -1831,7 +1591,8 @@ constexpr int kShadeWaves = RTO_SHADE_WG_WAVES;
 __host__ __device__ constexpr uint32_t shade_blocks_per_band(int W, int block_px) {
     return (uint32_t)((RTO_SHADE_BAND_ROWS > 0 ? RTO_SHADE_BAND_ROWS : 1) * W + block_px - 1) / (uint32_t)block_px;
 }
-template <int SPP, int P, int MODE>
+// LOBES: 0 for SH and RGBA trees, kFmtSG / kFmtASG for a tree of that format (with MODE 0 / 28 / 49 / 76)
+template <int SPP, int P, int MODE, int LOBES = 0>
 __global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kernel(const TreeDev tree, const OptDev opt, const FrameBatch fb,
                                                                               const uint32_t* __restrict__ hits0) {
     __shared__ uint32_t s_h[kShadeWaves][kShadeCap];       // packed hit entry
@@ -1980,12 +1741,14 @@ __global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kerne
             // (view direction + basis once per hit PIXEL, parked in LDS, removes ~200 of these ~430 instructions per entry and was
             //  built twice -- round 4 and round 6, tools/experiments/r6_shade_basis_table.patch -- and lost both times: 1.54 vs
             //  1.48 ms on C2, 1.24 vs 1.02 on C5: this arithmetic runs while the entry's record is in flight and costs nothing)
-            if constexpr (MODE > 0)  // (the launcher picks MODE from the tree: SH, data_dim = MODE)
+            if constexpr (LOBES != 0 && MODE > 0)  // SG / ASG tree, data_dim = MODE
+                ray_basis_lobes<LOBES, (MODE - 1) / 3>(tree, opt, vdir, basis_fn);
+            else if constexpr (MODE > 0)  // (the launcher picks MODE from the tree: SH, data_dim = MODE)
                 ray_basis_sh<(MODE - 1) / 3>(opt, vdir, basis_fn);
             else if constexpr (MODE < 0)  // quantised SH tree, -MODE basis functions
                 ray_basis_sh<-MODE>(opt, vdir, basis_fn);
             else
-                ray_basis(tree, opt, vdir, basis_fn);
+                ray_basis<LOBES>(tree, opt, vdir, basis_fn);
             float o[4];
             leaf_contrib<MODE>(tree, hit_slot<SPP>(he), basis_fn, (float)hit_count<SPP>(he), o);
             s_c[wv][j] = o[0];
@@ -2145,22 +1908,41 @@ TileMap make_tile_map(int width, int height, int strip_rows) {
     return tm;
 }
 
+template <int SPP, int LOBES>
+static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                        const FrameOut& fo, int strip_rows, hipStream_t stream) {
+    const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
+    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
+    const dim3 grid(8 * tm.per_xcd), block(256);
+#define RTO_FAST(ST, WI, SK)                                                                                                         \
+    if constexpr (LOBES == 0)                                                                                                        \
+        hipLaunchKernelGGL((render_fast<SPP, ST, WI, SK>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);             \
+    else                                                                                                                             \
+        hipLaunchKernelGGL((render_fast_lobes<SPP, ST, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo)
+    if (fo.stats) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
+        RTO_FAST(true, false, 0);
+    } else if (tree.widew) {
+        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {  // two pairs of levels below the grid at most
+            RTO_FAST(false, true, 1);
+        } else {
+            RTO_FAST(false, true, 0);
+        }
+    } else {
+        RTO_FAST(false, false, 0);
+    }
+#undef RTO_FAST
+}
+
 template <int SPP>
 static hipError_t launch_spp(int kernel, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
                              const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, hipStream_t stream) {
     if (kernel == 2) {
-        const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
-        const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
-        const dim3 grid(8 * tm.per_xcd), block(256);
-        if (fo.stats)  // (the counting instantiation walks the one-level image: its units are defined on that walk)
-            hipLaunchKernelGGL((render_fast<SPP, true, false>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
-        else if (tree.widew)
-            if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2)  // two pairs of levels below the grid at most
-                hipLaunchKernelGGL((render_fast<SPP, false, true, 1>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
-            else
-                hipLaunchKernelGGL((render_fast<SPP, false, true>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
+        if (tree.format == kFmtSG)
+            launch_fast<SPP, kFmtSG>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
+        else if (tree.format == kFmtASG)
+            launch_fast<SPP, kFmtASG>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
         else
-            hipLaunchKernelGGL((render_fast<SPP, false, false>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
+            launch_fast<SPP, 0>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
     } else {
         const int64_t size = (int64_t)cam.width * cam.height;
         hipLaunchKernelGGL(render_generic<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam,
@@ -2207,6 +1989,22 @@ hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev&
 #ifndef RTO_WPS_DEFAULT
 #define RTO_WPS_DEFAULT 8
 #endif
+// the shading kernel of an SG / ASG tree (LOBES = kFmtSG / kFmtASG): the SH modes of the same record layouts
+template <int SPP, int SP, int LOBES>
+static void launch_shade_lobes(const dim3 sgrid, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb, const uint32_t* hits,
+                               hipStream_t stream) {
+#define RTO_SHADE_L(M) hipLaunchKernelGGL((shade_kernel<SPP, SP, M, LOBES>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, hits)
+    if (tree.data_dim == 28)
+        RTO_SHADE_L(28);
+    else if (tree.data_dim == 49)
+        RTO_SHADE_L(49);
+    else if (tree.data_dim == 76)
+        RTO_SHADE_L(76);
+    else
+        RTO_SHADE_L(0);
+#undef RTO_SHADE_L
+}
+
 template <int SPP, int REFILL, int WPS, bool WIDE>
 static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                     const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
@@ -2297,6 +2095,10 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
             RTO_SHADE(-16);
         else
             RTO_SHADE(-25);
+    } else if (tree.format == kFmtSG) {
+        launch_shade_lobes<SPP, SP, kFmtSG>(sgrid, tree, opt, fb, hits, stream);
+    } else if (tree.format == kFmtASG) {
+        launch_shade_lobes<SPP, SP, kFmtASG>(sgrid, tree, opt, fb, hits, stream);
     } else if (tree.format == 1 && tree.data_dim == 28)
         RTO_SHADE(28);
     else if (tree.format == 1 && tree.data_dim == 49)
@@ -2383,6 +2185,65 @@ hipError_t debug_shade_phases(unsigned long long* out, bool reset) {  // out: kS
     return e;
 }
 #endif
+
+// ------------------------------------------------------------------ basis probe (rto_probe_basis)
+// out[i][0..24] = the basis the kernels compute for the view direction dirs[i] (before the rot_dirs rotation): PATH 0 the run-time
+// ray_basis of the generic / fast kernels and shade_kernel<..., 0>, PATH 1 the per-B forms of the shading kernel's record modes
+// (ray_basis_sh<B> / ray_basis_lobes<LOBES, B>; entries from B on are 0)
+template <int PATH, int LOBES, int B>
+__global__ void __launch_bounds__(256) basis_probe_kernel(const TreeDev tree, const OptDev opt, const float* __restrict__ dirs, int64_t n,
+                                                          float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float vdir[3] = {dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
+    float basis_fn[RTO_BASIS_MAX_DEV];
+#pragma unroll
+    for (int k = 0; k < RTO_BASIS_MAX_DEV; ++k) basis_fn[k] = 0.f;
+    if constexpr (PATH == 0)
+        ray_basis_any(tree, opt, vdir, basis_fn);
+    else if constexpr (LOBES == 0)
+        ray_basis_sh<B>(opt, vdir, basis_fn);
+    else
+        ray_basis_lobes<LOBES, B>(tree, opt, vdir, basis_fn);
+#pragma unroll
+    for (int k = 0; k < RTO_BASIS_MAX_DEV; ++k) out[i * RTO_BASIS_MAX_DEV + k] = basis_fn[k];
+}
+
+template <int LOBES, int B = 1>
+static hipError_t launch_probe_lobes(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, float* out, hipStream_t stream) {
+    if (tree.basis_dim == B) {
+        hipLaunchKernelGGL((basis_probe_kernel<1, LOBES, B>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tree, opt, dirs, n, out);
+        return hipGetLastError();
+    }
+    if constexpr (B < RTO_BASIS_MAX_DEV)
+        return launch_probe_lobes<LOBES, B + 1>(tree, opt, dirs, n, out, stream);
+    else
+        return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe_basis(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, int path, float* out, hipStream_t stream) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+#define RTO_PROBE(P, L, B) hipLaunchKernelGGL((basis_probe_kernel<P, L, B>), grid, dim3(256), 0, stream, tree, opt, dirs, n, out)
+    if (path == 0) {
+        RTO_PROBE(0, 0, 0);
+    } else if (tree.format == kFmtSG) {
+        return launch_probe_lobes<kFmtSG>(tree, opt, dirs, n, out, stream);
+    } else if (tree.format == kFmtASG) {
+        return launch_probe_lobes<kFmtASG>(tree, opt, dirs, n, out, stream);
+    } else if (tree.format == kFmtSH) {  // (the basis sizes the shading kernel has per-B forms for)
+        switch (tree.basis_dim) {
+            case 4: RTO_PROBE(1, 0, 4); break;
+            case 9: RTO_PROBE(1, 0, 9); break;
+            case 16: RTO_PROBE(1, 0, 16); break;
+            case 25: RTO_PROBE(1, 0, 25); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef RTO_PROBE
+    return hipGetLastError();
+}
 
 hipError_t launch_write_frames(const FrameDesc* host, int n, FrameDesc* dev_table, hipStream_t stream) {
     for (int f0 = 0; f0 < n; f0 += kFrameChunk) {

@@ -101,6 +101,7 @@ struct rto_tree {
     void* d_qrec = nullptr;
     void* d_qcolors = nullptr;
     void* d_qsigma = nullptr;
+    void* d_extra = nullptr;  // SG / ASG lobes (TreeDev::extra)
     bool quant = false;  // rendered from the codebooks; only the batched path can shade it
     bool fast_ok = false;
     // Footprint (VERDICT r2 task 8): a dense SH9 / SH16 tree that renders through the fast / batched kernels reads only
@@ -497,9 +498,12 @@ bool build_wide_image(const int32_t* child, int64_t capacity, int max_depth, int
     return true;
 }
 
+// extra / extra_floats: the lobes of an SG / ASG tree (nullptr: none -- the tree loads, its launches are refused); ignored
+// for SH and RGBA trees, as by the reference
 int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, int N, int data_dim,
                 const rto::DataFormat& fmt, const float scale[3], const float offset[3], int device,
-                rto_tree** out, const rto::HostTree* quant = nullptr, int flags = 0) {
+                rto_tree** out, const rto::HostTree* quant = nullptr, int flags = 0, const float* extra = nullptr,
+                int64_t extra_floats = 0) {
     if (!child || (!data && !quant) || capacity <= 0 || N < 1 || data_dim < 1 || !out)
         return set_err(RTO_E_INVALID, "rto_tree: null array or non-positive size");
     if (quant && (N != 2 || fmt.format != RTO_FMT_SH ||
@@ -514,6 +518,12 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
             return set_err(RTO_E_FORMAT, "rto_tree: basis_dim above " + std::to_string(RTO_BASIS_MAX));
     } else if (data_dim < 4) {
         return set_err(RTO_E_FORMAT, "rto_tree: RGBA trees need data_dim >= 4");
+    }
+    const bool lobes = rto::lobe_floats(fmt.format) != 0;
+    if (!lobes) extra = nullptr;
+    if (extra) {
+        const std::string bad = rto::check_lobes(fmt, extra, extra_floats);
+        if (!bad.empty()) return set_err(RTO_E_FORMAT, "rto_tree: " + bad);
     }
     int max_depth = 0;
     try {
@@ -697,9 +707,17 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
         }
     }
 
-    if (t->fast_ok && !quant && fmt.format == RTO_FMT_SH && (fmt.basis_dim == 9 || fmt.basis_dim == 16) &&
+    if (extra) {
+        const size_t eb = (size_t)extra_floats * sizeof(float);
+        if (hipMalloc(&t->d_extra, eb) != hipSuccess || hipMemcpy(t->d_extra, extra, eb, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(RTO_E_HIP, "lobe (extra_data) upload failed");
+        dev_bytes += eb;
+    }
+
+    // (SG / ASG records have the layout of SH records of the same basis size: only the basis the coefficients meet differs)
+    if (t->fast_ok && !quant && (fmt.format == RTO_FMT_SH || lobes) && (fmt.basis_dim == 9 || fmt.basis_dim == 16) &&
         !(flags & RTO_TREE_COMPACT)) {
-        // aligned copy of the SH coefficients for the shading kernels (+ 64 / 128 B per slot)
+        // aligned copy of the coefficients for the shading kernels (+ 64 / 128 B per slot)
         const int rec = 3 * fmt.basis_dim * 2 <= 64 ? 32 : 64;  // = shrec_halves()
         int64_t n_rec = n_slots;
         if (flags & RTO_TREE_COMPACT_RECORDS) {
@@ -786,7 +804,10 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
     d.shrec = (const uint16_t*)t->d_shrec;
     d.recidx = (const uint32_t*)t->d_recidx;
     d.qrec = (const uint16_t*)t->d_qrec;
-    d.qcolors = (const uint2*)t->d_qcolors;
+    if (quant)
+        d.qcolors = (const uint2*)t->d_qcolors;
+    else
+        d.extra = (const float*)t->d_extra;  // (shares qcolors' place in TreeDev)
     d.q_retain = quant ? quant->n_retain : 0;
     d.q_rec = q_rec;
     d.data = (const uint16_t*)t->d_data;
@@ -828,6 +849,16 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
 // child[] / data[] of a tree that dropped them at upload, back on the device for the generic kernel (same leaf values:
 // tests/test_render_parity.py::test_generic_kernel_on_a_tree_without_reference_arrays)
 bool tree_fits_spp(const rto_tree* tree, int spp) { return fast_path_for_spp(tree, spp, 0, nullptr) != 0; }
+
+// an SG / ASG tree loaded without its lobes: the reference would read a null device pointer (data_spec.hpp:44)
+bool missing_lobes(const rto_tree* tree) { return rto::lobe_floats(tree->dev.format) != 0 && !tree->d_extra; }
+std::string tree_format_name(const rto_tree* tree) {
+    rto::DataFormat f;
+    f.format = tree->dev.format;
+    f.basis_dim = tree->dev.basis_dim;
+    return f.to_string();
+}
+const char* const missing_lobes_msg = "an SG / ASG tree needs its lobes: the tree has no extra_data (npz key) / extra (rto_tree_from_arrays_extra)";
 
 int fast_path_for_spp(const rto_tree* tree, int spp, int wide_bits, rto::TreeDev* td) {
     if (td) *td = tree->dev;
@@ -1014,7 +1045,7 @@ int rto_tree_load_npz_ex(const char* path, int device, int flags, rto_tree** out
     }
     std::fprintf(stdout, "INFO: Scale %f %f %f\n", h.scale[0], h.scale[1], h.scale[2]);  // n3tree.cpp:264
     int rc = upload_tree(h.child, h.data, h.capacity, h.N, h.data_dim, h.data_format, h.scale, h.offset, device, out,
-                         h.quantized ? &h : nullptr, flags);
+                         h.quantized ? &h : nullptr, flags, h.extra, h.extra_floats);
     if (rc != RTO_OK) return rc;
     if (h.use_ndc) rto_tree_set_ndc(*out, h.ndc_width, h.ndc_height, h.ndc_focal);
     return RTO_OK;
@@ -1044,16 +1075,27 @@ int rto_tree_probe_npz(const char* path, char* json_out, size_t cap) {
     } catch (const std::exception& e) {
         return set_err(RTO_E_FORMAT, e.what());
     }
+    // the lobes of an SG / ASG tree as the file stores them (null: none, or an SH / RGBA tree, whose extra_data is ignored)
+    std::string extra_shape = "null", extra_fnv = "null";
+    if (h.extra) {
+        extra_shape = "[";
+        for (size_t i = 0; i < h.extra_shape.size(); ++i) extra_shape += (i ? ", " : "") + std::to_string(h.extra_shape[i]);
+        extra_shape += "]";
+        char hex[24];
+        std::snprintf(hex, sizeof(hex), "\"%016llx\"", (unsigned long long)fnv(h.extra, (size_t)h.extra_floats * 4));
+        extra_fnv = hex;
+    }
     char buf[1024];
     const int n = std::snprintf(
         buf, sizeof(buf),
         "{\"capacity\": %lld, \"N\": %d, \"data_dim\": %d, \"data_format\": \"%s\", \"basis_dim\": %d, "
         "\"scale\": [%.9g, %.9g, %.9g], \"offset\": [%.9g, %.9g, %.9g], \"use_ndc\": %d, \"max_depth\": %d, "
-        "\"quantized\": %d, \"child_fnv1a64\": \"%016llx\", \"data_fnv1a64\": \"%016llx\"}",
+        "\"quantized\": %d, \"child_fnv1a64\": \"%016llx\", \"data_fnv1a64\": \"%016llx\", \"extra_shape\": %s, "
+        "\"extra_fnv1a64\": %s}",
         (long long)h.capacity, h.N, h.data_dim, h.data_format.to_string().c_str(), h.data_format.basis_dim,
         h.scale[0], h.scale[1], h.scale[2], h.offset[0], h.offset[1], h.offset[2], (int)h.use_ndc, max_depth,
         (int)!h.decoded.empty(), (unsigned long long)fnv(h.child, n_slots * 4),
-        (unsigned long long)fnv(h.data, n_slots * (size_t)h.data_dim * 2));
+        (unsigned long long)fnv(h.data, n_slots * (size_t)h.data_dim * 2), extra_shape.c_str(), extra_fnv.c_str());
     if (n < 0 || (size_t)n + 1 > cap) return set_err(RTO_E_INVALID, "rto_tree_probe_npz: output buffer too small");
     std::memcpy(json_out, buf, (size_t)n + 1);
     return RTO_OK;
@@ -1068,7 +1110,14 @@ int rto_tree_from_arrays(const int32_t* child, const uint16_t* data, int64_t cap
 int rto_tree_from_arrays_ex(const int32_t* child, const uint16_t* data, int64_t capacity, int N, int data_dim,
                             const char* data_format, const float scale[3], const float offset[3], int device, int flags,
                             rto_tree** out) {
+    return rto_tree_from_arrays_extra(child, data, capacity, N, data_dim, data_format, scale, offset, device, flags, nullptr, 0, out);
+}
+
+int rto_tree_from_arrays_extra(const int32_t* child, const uint16_t* data, int64_t capacity, int N, int data_dim,
+                               const char* data_format, const float scale[3], const float offset[3], int device, int flags,
+                               const float* extra, int64_t extra_floats, rto_tree** out) {
     if (!scale || !offset) return set_err(RTO_E_INVALID, "rto_tree_from_arrays: null scale/offset");
+    if (!extra && extra_floats != 0) return set_err(RTO_E_INVALID, "rto_tree_from_arrays_extra: null extra with extra_floats != 0");
     rto::DataFormat fmt;
     if (data_format && data_format[0]) {
         fmt.parse(data_format);
@@ -1079,7 +1128,8 @@ int rto_tree_from_arrays_ex(const int32_t* child, const uint16_t* data, int64_t 
         fmt.format = RTO_FMT_SH;
         fmt.basis_dim = (data_dim - 1) / 3;
     }
-    return upload_tree(child, data, capacity, N, data_dim, fmt, scale, offset, device, out, nullptr, flags & ~RTO_TREE_QUANT_DIRECT);
+    return upload_tree(child, data, capacity, N, data_dim, fmt, scale, offset, device, out, nullptr, flags & ~RTO_TREE_QUANT_DIRECT,
+                       extra, extra_floats);
 }
 
 int rto_tree_set_ndc(rto_tree* t, float w, float h, float focal) {
@@ -1112,9 +1162,36 @@ void rto_tree_free(rto_tree* t) {
     if (t->d_shrec) (void)hipFree(t->d_shrec);
     if (t->d_recidx) (void)hipFree(t->d_recidx);
     if (t->d_occ) (void)hipFree(t->d_occ);
-    for (void* p : {t->d_qrec, t->d_qcolors, t->d_qsigma})
+    for (void* p : {t->d_qrec, t->d_qcolors, t->d_qsigma, t->d_extra})
         if (p) (void)hipFree(p);
     delete t;
+}
+
+int rto_probe_basis(const rto_tree* tree, const rto_options* o, const float* dirs, int64_t n, int path, float* host_out) {
+    if (!tree || !o || !dirs || !host_out || n <= 0 || (path != 0 && path != 1))
+        return set_err(RTO_E_INVALID, "rto_probe_basis: null argument, n <= 0 or path not 0 / 1");
+    if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
+    if (n > (int64_t(1) << 31) - 256) return set_err(RTO_E_INVALID, "rto_probe_basis: n above 2^31 - 256");
+    DeviceGuard guard(tree->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    const rto::OptDev od = make_opt_dev(o);
+    const size_t in_b = (size_t)n * 3 * sizeof(float), out_b = (size_t)n * RTO_BASIS_MAX * sizeof(float);
+    float *d_dirs = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void**)&d_dirs, in_b);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_b);
+    if (e == hipSuccess) e = hipMemcpy(d_dirs, dirs, in_b, hipMemcpyHostToDevice);
+    bool no_form = false;
+    if (e == hipSuccess) {
+        e = rto::launch_probe_basis(tree->dev, od, d_dirs, n, path, d_out, nullptr);
+        no_form = e == hipErrorInvalidValue;
+    }
+    if (e == hipSuccess) e = hipMemcpy(host_out, d_out, out_b, hipMemcpyDeviceToHost);
+    if (d_dirs) (void)hipFree(d_dirs);
+    if (d_out) (void)hipFree(d_out);
+    if (no_form)
+        return set_err(RTO_E_UNSUPPORTED, "rto_probe_basis: the shading kernel has no per-B form for " + tree_format_name(tree));
+    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("rto_probe_basis: ") + hipGetErrorString(e));
+    return RTO_OK;
 }
 
 int rto_ctx_create(int width, int height, int device, rto_ctx** out) {
@@ -1568,8 +1645,7 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
                                           "density only: sigma_thresh must be >= 0");
     if (o->enable_probe)
         return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature (volrend.cu:100-134), not on the headless path");
-    if (tree->dev.format == RTO_FMT_SG || tree->dev.format == RTO_FMT_ASG)
-        return set_err(RTO_E_UNSUPPORTED, "SG/ASG bases are untested upstream (lumisphere.hpp:14-37) and not built");
+    if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
     if (!(cam->fx != 0.f) || !(cam->fy != 0.f)) return set_err(RTO_E_INVALID, "camera focal length is zero");
 
     int kernel = ctx->kernel;
@@ -1721,8 +1797,7 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
         return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps coefficient records for leaves of positive "
                                           "density only: sigma_thresh must be >= 0");
     if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature, not on the headless path");
-    if (tree->dev.format == RTO_FMT_SG || tree->dev.format == RTO_FMT_ASG)
-        return set_err(RTO_E_UNSUPPORTED, "SG/ASG bases are untested upstream and not built");
+    if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     ctx->marks_n = 0;  // whatever happens below, the tile marks of an earlier launch no longer describe this context's frames

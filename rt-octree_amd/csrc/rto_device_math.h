@@ -255,6 +255,29 @@ RTO_DEV void sigmoid_cnt3(const float* t, float cnt, float* o) {
     }
 }
 
+// ---- SG / ASG lobes (lumisphere.hpp:14-37, maybe_precalc_basis) ----
+// A lobe record lives in device memory that no kernel writes; read through the constant address space, a lobe at a
+// wave-uniform address becomes scalar loads (s_load_*) instead of one vector load per lane.
+#define RTO_CONST __attribute__((address_space(4)))
+
+// _dot3 (cuda/common.cuh:47-51): u0*v0 + u1*v1 + u2*v2, left to right, every product rounded
+RTO_DEV float lobe_dot3(const float* d, const RTO_CONST float* m) { return d[0] * m[0] + d[1] * m[1] + d[2] * m[2]; }
+
+// SG lobe {lambda, mu}: expf(lambda * (dot(d, mu) - 1)) / B.  expf is det_expf over its FULL range: lambda * (dot - 1) reaches
+// far below -87 (a sharp lobe seen from the side), where the result is a subnormal or 0 exactly as orc_det_expf gives it
+RTO_DEV float sg_lobe(const float* d, const RTO_CONST float* p, float fB) {
+    return det_expf(p[0] * (lobe_dot3(d, p + 1) - 1.f)) / fB;
+}
+
+// ASG lobe {lambda_x, lambda_y, mu_x, mu_y, mu_z}: S * expf(-lambda_x dx^2 - lambda_y dy^2) / B with S = dot(d, mu_z) (not
+// clamped: negative behind the lobe), dx = dot(d, mu_x), dy = dot(d, mu_y); the mu are used as stored (not normalised)
+RTO_DEV float asg_lobe(const float* d, const RTO_CONST float* p, float fB) {
+    const float S = lobe_dot3(d, p + 8);
+    const float dot_x = lobe_dot3(d, p + 2);
+    const float dot_y = lobe_dot3(d, p + 5);
+    return S * det_expf(-p[0] * dot_x * dot_x - p[1] * dot_y * dot_y) / fB;
+}
+
 // fp32-only deterministic exp for the filter taps; mirrors oracle/rto_oracle.c orc_fexp (every
 // multiply-add an explicit, correctly rounded fma: v_fma_f32 here, fmaf there)
 RTO_DEV float fexp_f32(float x) {

@@ -8,6 +8,8 @@
 namespace rto {
 
 #define RTO_BASIS_MAX_DEV 25  // render_options.hpp:7 VOLREND_GLOBAL_BASIS_MAX
+// TreeDev::format (= RTO_FMT_* of rto.h, data_format.hpp:8-14)
+constexpr int kFmtRGBA = 0, kFmtSH = 1, kFmtSG = 2, kFmtASG = 3;
 
 // Leaf tag of the traversal image `nodew` (see build_nodew_kernel in render_kernels.hip):
 //   internal slot: the reference's child[] value (relative node offset, |v| < 2^30)
@@ -90,7 +92,15 @@ struct TreeDev {
     const float4* occ_cells;
     int n_occ_cells;  // (0 with occ_cells != nullptr: a tree without density; occ_cells == nullptr: no culling)
     const uint16_t* qrec;
-    const uint2* qcolors;  // [n_basis - q_retain][65536]
+    // One field, two uses that never meet (quantised trees render directly only as SH): TreeDev travels as a kernel argument,
+    // and a new member would move every later argument of every kernel -- the SH kernels keep their code byte for byte.
+    union {
+        const uint2* qcolors;  // [n_basis - q_retain][65536]
+        // SG / ASG trees: the lobes (the reference's TreeSpec::extra, data_spec.hpp:30, lumisphere.hpp:14-37), basis_dim
+        // records of 4 floats {lambda, mu} (SG) or 11 {lambda_x, lambda_y, mu_x, mu_y, mu_z} (ASG); nullptr: the tree has
+        // none, and every launch of it is refused
+        const float* extra;
+    };
     int q_retain;
     int q_rec;
 };

@@ -64,6 +64,10 @@ hipError_t launch_pack_quant(const uint16_t* qmap, const uint16_t* retained, int
 
 hipError_t launch_rgba8(const float* rgba, uint8_t* out, int64_t n_pixels, hipStream_t stream);
 
+// rto_probe_basis: out[n][RTO_BASIS_MAX_DEV] = the basis of the view directions dirs[n][3] (device pointers) as the kernels
+// compute it; path 0 the run-time ray_basis, 1 the per-B forms of the shading kernel (hipErrorInvalidValue where none exists)
+hipError_t launch_probe_basis(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, int path, float* out, hipStream_t stream);
+
 #ifdef RTO_DBG_COUNTERS
 hipError_t debug_shade_phases(unsigned long long* out16, bool reset);  // tools/dbg_shade_phases.py
 #endif

@@ -82,8 +82,9 @@ def scene_variant(k):
 class SynthTree:
     """Host arrays of a synthetic PlenOctree, in the reference's layout."""
 
-    def __init__(self, child, data, scale, offset, data_format, depth_limit, stats):
+    def __init__(self, child, data, scale, offset, data_format, depth_limit, stats, extra=None):
         self.child, self.data = child, data
+        self.extra = extra  # SG / ASG lobes (npz key extra_data), float32 [basis_dim, 4 / 11]; None for SH / RGBA
         self.scale = np.asarray(scale, np.float32)
         self.offset = np.asarray(offset, np.float32)
         self.data_format = data_format
@@ -103,6 +104,8 @@ class SynthTree:
         kw = dict(data_dim=np.int64(self.data_dim), data_format=np.array(self.data_format),
                   invradius3=self.scale.astype(np.float32), offset=self.offset.astype(np.float32),
                   child=self.child, data=self.data)
+        if self.extra is not None:
+            kw["extra_data"] = self.extra
         (np.savez_compressed if compressed else np.savez)(path, **kw)
         return path
 
@@ -348,7 +351,41 @@ def shuffle_nodes(tree, seed=1):
     data_new[new_of_old] = tree.data
     stats = dict(tree.stats, shuffled_seed=int(seed))
     return SynthTree(child_new.reshape(cap, 2, 2, 2), data_new, tree.scale, tree.offset, tree.data_format,
-                     tree.depth_limit, stats)
+                     tree.depth_limit, stats, tree.extra)
+
+
+def _unit_vectors(rng, n):
+    v = rng.standard_normal((n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def with_lobes(tree, kind, seed=1, lambda_max=2000.0):
+    """The tree as an SG or ASG PlenOctree (lumisphere.hpp:14-37): same topology, sigma and coefficients (basis_dim =
+    the tree's), a random lobe per basis function in `extra`.  SG lobe {lambda, mu}: mu a random unit vector.  ASG lobe
+    {lambda_x, lambda_y, mu_x, mu_y, mu_z}: a random orthonormal frame.  The sharpnesses spread from 0 to lambda_max
+    (0, then log-uniform from 0.1): the sharp lobes underflow expf to subnormals and 0 over most directions."""
+    assert kind in ("SG", "ASG")
+    B = (tree.data_dim - 1) // 3
+    rng = np.random.default_rng(seed)
+
+    def sharpness(n):
+        lam = np.exp(rng.uniform(np.log(0.1), np.log(lambda_max), n))
+        lam[0] = 0.0
+        lam[-1] = lambda_max
+        return rng.permutation(lam)
+
+    if kind == "SG":
+        extra = np.concatenate([sharpness(B)[:, None], _unit_vectors(rng, B)], 1)
+    else:
+        frames = []
+        for _ in range(B):
+            q, r = np.linalg.qr(rng.standard_normal((3, 3)))
+            q = q * np.sign(np.diag(r))  # columns: mu_x, mu_y, mu_z
+            frames.append(q.T.reshape(9))
+        extra = np.concatenate([sharpness(B)[:, None], sharpness(B)[:, None], np.array(frames)], 1)
+    stats = dict(tree.stats, lobes=kind, lobe_seed=int(seed))
+    return SynthTree(tree.child, tree.data, tree.scale, tree.offset, "%s%d" % (kind, B), tree.depth_limit, stats,
+                     np.ascontiguousarray(extra, np.float32))
 
 
 # ------------------------------------------------------------------ cameras

@@ -137,9 +137,10 @@ class N3Tree:
 
     @classmethod
     def from_arrays(cls, child, data, scale, offset, data_format="", device=0, compact=False, keep_reference=False,
-                    compact_records=False, no_culling=False):
+                    compact_records=False, no_culling=False, extra_data=None):
         """child int32 [capacity,N,N,N]; data float16 (or uint16 bits) [capacity,N,N,N,data_dim];
-        scale = invradius3, offset (n3tree.cpp:257-267)."""
+        scale = invradius3, offset (n3tree.cpp:257-267).  extra_data: the lobes of an SG / ASG tree, float32
+        [basis_dim, 4] (SG) / [basis_dim, 11] (ASG) or flat (n3tree.cpp:350-353); ignored for SH / RGBA trees."""
         child = np.ascontiguousarray(child, dtype=np.int32)
         data = np.ascontiguousarray(data)
         if data.dtype == np.float16:
@@ -153,9 +154,17 @@ class N3Tree:
         of = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(offset, np.float32), (3,))])
         t = cls(device=device, compact=compact, keep_reference=keep_reference, compact_records=compact_records,
                 no_culling=no_culling)
+        extra_ptr, extra_n = None, 0
+        if extra_data is not None:
+            extra_data = np.asarray(extra_data)
+            if extra_data.dtype != np.float32:  # (the reference reinterprets the bytes as float: n3tree.cpp:351)
+                raise RtoError(-6, "extra_data must be float32")
+            extra_data = np.ascontiguousarray(extra_data)
+            extra_ptr, extra_n = C.c_void_p(extra_data.ctypes.data), extra_data.size
         h = C.c_void_p(0)
-        check(lib().rto_tree_from_arrays_ex(C.c_void_p(child.ctypes.data), C.c_void_p(data.ctypes.data), cap, N, dd,
-                                            data_format.encode("ascii"), sc, of, device, t._flags(), C.byref(h)))
+        check(lib().rto_tree_from_arrays_extra(C.c_void_p(child.ctypes.data), C.c_void_p(data.ctypes.data), cap, N, dd,
+                                               data_format.encode("ascii"), sc, of, device, t._flags(), extra_ptr, extra_n,
+                                               C.byref(h)))
         t._h = h
         t._refresh()
         return t

@@ -1,0 +1,424 @@
+"""SG and ASG PlenOctrees (lumisphere.hpp:14-37): the lobes (npz key extra_data) load, upload and shade on the GPU.
+The pixels are pinned bit for bit to sg_asg_ref, an independent numpy restatement of the view direction, the lobe basis,
+the library's expf and the shading of a leaf; which leaf a pixel hit comes from the CPU oracle (an RGBA tree over the same
+child[] and sigma whose colours spell the leaf slot)."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import orc
+import rt_octree_amd as R
+import sg_asg_ref as ref
+from helpers import assert_bits_equal, oracle_threads
+from rt_octree_amd import _lib, synth
+
+E_UNSUPPORTED, E_FORMAT = -3, -6
+HERE = os.path.dirname(os.path.abspath(__file__))
+BIN = os.path.join(os.path.dirname(HERE), "rt-octree_amd", "bin", "volrend_headless")
+
+
+def _probe(path):
+    buf = C.create_string_buffer(4096)
+    rc = R.lib().rto_tree_probe_npz(os.fsencode(str(path)), buf, 4096)
+    return rc, (json.loads(buf.value.decode()) if rc == 0 else None)
+
+
+def _fnv(b):
+    x = 1469598103934665603
+    for c in b:
+        x = ((x ^ c) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return "%016x" % x
+
+
+def _lobed(kind, B, depth=4, seed=5, lobe_seed=9):
+    return synth.with_lobes(synth.make_tree(depth_limit=depth, basis_dim=B, seed=seed), kind, seed=lobe_seed)
+
+
+def _save(tree, path, **replace):
+    kw = dict(data_dim=np.int64(tree.data_dim), data_format=np.array(tree.data_format), invradius3=tree.scale,
+              offset=tree.offset, child=tree.child, data=tree.data)
+    if tree.extra is not None:
+        kw["extra_data"] = tree.extra
+    kw.update(replace)
+    kw = {k: v for k, v in kw.items() if v is not None}
+    np.savez(str(path), **kw)
+    return str(path)
+
+
+# ------------------------------------------------------------------ CPU: loader, probe, restatement
+
+
+@pytest.mark.parametrize("kind,B", [("SG", 16), ("ASG", 9), ("SG", 7)])
+def test_npz_round_trip_reports_lobes(tmp_path, kind, B):
+    t = _lobed(kind, B, depth=3)
+    rc, info = _probe(t.save_npz(str(tmp_path / "tree.npz")))
+    assert rc == 0, R.lib().rto_last_error()
+    assert info["data_format"] == "%s%d" % (kind, B)
+    assert info["extra_shape"] == [B, ref.LOBE_FLOATS[kind]]
+    assert info["extra_fnv1a64"] == _fnv(t.extra.tobytes())
+    flat = _save(t, tmp_path / "flat.npz", extra_data=t.extra.reshape(-1))
+    rc, info_flat = _probe(flat)
+    assert rc == 0 and info_flat["extra_shape"] == [B * ref.LOBE_FLOATS[kind]]
+    assert info_flat["extra_fnv1a64"] == info["extra_fnv1a64"]
+    rc, bare = _probe(_save(t, tmp_path / "bare.npz", extra_data=None))  # loads without lobes (launches are refused)
+    assert rc == 0 and bare["extra_shape"] is None and bare["extra_fnv1a64"] is None
+
+
+def test_malformed_lobes_are_refused(tmp_path):
+    t = _lobed("ASG", 4, depth=3)
+    nan = t.extra.copy()
+    nan[2, 5] = np.nan
+    inf = t.extra.copy()
+    inf[0, 0] = np.inf
+    cases = {
+        "float64": t.extra.astype(np.float64),
+        "float16": t.extra.astype(np.float16),
+        "count": t.extra.reshape(-1)[:-1],
+        "rows": t.extra[:3],
+        "shape": t.extra.reshape(2, 22),
+        "sg_layout": np.zeros((4, 4), np.float32),
+        "fortran": np.asfortranarray(t.extra),
+        "nan": nan,
+        "inf": inf,
+        "3d": t.extra.reshape(4, 11, 1),
+    }
+    for name, bad in cases.items():
+        rc, _ = _probe(_save(t, tmp_path / ("%s.npz" % name), extra_data=bad))
+        assert rc == E_FORMAT, (name, rc)
+        assert "extra_data" in R.lib().rto_last_error().decode(), name
+
+
+def test_sh_tree_ignores_extra_data(tmp_path):
+    t = synth.make_tree(depth_limit=3, basis_dim=9, seed=2)
+    _, plain = _probe(t.save_npz(str(tmp_path / "plain.npz")))
+    for name, extra in (("f32", np.ones((9, 4), np.float32)), ("f64", np.full(5, np.nan))):  # (never read, never checked)
+        rc, info = _probe(_save(t, tmp_path / ("%s.npz" % name), extra_data=extra))
+        assert rc == 0
+        assert info["data_fnv1a64"] == plain["data_fnv1a64"] and info["child_fnv1a64"] == plain["child_fnv1a64"]
+        assert info["extra_shape"] is None
+
+
+def test_from_arrays_refuses_malformed_lobes_before_the_device():
+    t = _lobed("SG", 4, depth=3)
+    with pytest.raises(R.RtoError) as e:
+        R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra[:3])
+    assert e.value.code == E_FORMAT
+    with pytest.raises(R.RtoError) as e:
+        R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra.astype(np.float64))
+    assert e.value.code == E_FORMAT
+
+
+def test_det_expf_restatement_matches_the_oracle():
+    L = orc.lib()
+    rng = np.random.default_rng(0)
+    xs = np.concatenate([np.linspace(-110, 95, 20001, dtype=np.float32), rng.uniform(-104, -87, 20000).astype(np.float32),
+                         np.array([-103.97208404541016, -103.972084, 88.72283935546875, 88.722845, 0.0, -0.0, np.inf, -np.inf,
+                                   np.nan, 1e-30, -1e-30], np.float32)])
+    want = np.array([L.orc_det_expf(float(x)) for x in xs], np.float32)
+    got = ref.det_expf(xs)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    sub = (got > 0) & (got < np.finfo(np.float32).tiny)
+    assert sub.sum() > 1000 and (got == 0).sum() > 100  # the sweep reaches the subnormal results and underflow
+
+
+@pytest.mark.parametrize("kind", ["SG", "ASG"])
+def test_restatement_agrees_with_float64_closed_form(kind):
+    rng = np.random.default_rng(3)
+    B = 9
+    lobes = _lobed(kind, B, depth=3, lobe_seed=4).extra.astype(np.float64)
+    lobes[:, 0] = rng.uniform(0, 20, B)  # (moderate sharpness: float32 rounding of lambda*(dot-1) stays small)
+    if kind == "ASG":
+        lobes[:, 1] = rng.uniform(0, 20, B)
+    d = rng.standard_normal((5000, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    got = ref.lobe_basis(kind, lobes.astype(np.float32), d.astype(np.float32)).astype(np.float64)
+    d = d.astype(np.float32).astype(np.float64)
+    lob = lobes.astype(np.float32).astype(np.float64)
+    if kind == "SG":
+        want = np.exp(lob[:, 0] * (d @ lob[:, 1:4].T - 1.0)) / B
+    else:
+        S, dx, dy = d @ lob[:, 8:11].T, d @ lob[:, 2:5].T, d @ lob[:, 5:8].T
+        want = S * np.exp(-lob[:, 0] * dx * dx - lob[:, 1] * dy * dy) / B
+    assert np.max(np.abs(got - want)) < 2e-6
+
+
+def test_with_lobes_spreads_lambda_to_underflow():
+    for kind in ("SG", "ASG"):
+        t = _lobed(kind, 16, depth=3)
+        assert t.extra.dtype == np.float32 and t.extra.shape == (16, ref.LOBE_FLOATS[kind])
+        assert t.extra[:, 0].min() == 0 and t.extra[:, 0].max() >= 1999
+        d = np.eye(3, dtype=np.float32)
+        b = ref.lobe_basis(kind, t.extra, np.concatenate([d, -d]))
+        assert (b == 0).any()
+        mu = t.extra[:, 1:4] if kind == "SG" else t.extra[:, 2:11].reshape(-1, 3)
+        assert np.allclose(np.linalg.norm(mu, axis=1), 1, atol=1e-6)
+
+
+# ------------------------------------------------------------------ GPU: basis probe
+
+
+def _options(**kw):
+    return R.RenderOptions(**kw)
+
+
+def _probe_basis(dt, opt, dirs, path):
+    dirs = np.ascontiguousarray(dirs, np.float32)
+    out = np.empty((dirs.shape[0], 25), np.float32)
+    co = opt.to_c()
+    _lib.check(R.lib().rto_probe_basis(dt._h, C.byref(co), C.c_void_p(dirs.ctypes.data), dirs.shape[0], path,
+                                       C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def _directions(n, seed):
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n, 3)).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    axes = np.concatenate([np.eye(3), -np.eye(3)]).astype(np.float32)
+    diag = np.array([[1, 1, 0], [0, -1, 1], [1, 1, 1], [-1, 1, -1]], np.float32)
+    diag /= np.linalg.norm(diag, axis=1, keepdims=True)
+    return np.concatenate([axes, diag, d]).astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["SG", "ASG"])
+@pytest.mark.parametrize("B", [4, 9, 16, 25, 7])
+def test_probe_basis_equals_restatement(kind, B):
+    t = _lobed(kind, B, depth=3, lobe_seed=B)
+    dt = R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra)
+    dirs = _directions(100_000, seed=B + 31 * len(kind))
+    variants = [dict(), dict(rot_dirs=[0.3, -1.1, 0.7]), dict(basis_minmax=[1, B - 2])]
+    subnormal = zeros = 0
+    for kw in variants:
+        want = ref.basis(kind, t.extra, dirs, **kw)
+        subnormal += int(((want != 0) & (np.abs(want) < np.finfo(np.float32).tiny)).sum())
+        zeros += int((want[:, :B] == 0).sum())
+        for path in (0, 1):
+            got = _probe_basis(dt, _options(**kw), dirs, path)
+            assert_bits_equal(got, want, "%s%d path %d %r" % (kind, B, path, kw))
+    assert subnormal > 0 and zeros > 0  # the sharp lobes reach subnormal results and underflow
+    dt.free()
+
+
+@pytest.mark.gpu
+def test_probe_basis_refuses_a_tree_without_lobes():
+    t = _lobed("SG", 4, depth=3)
+    dt = R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format)
+    dirs = _directions(10, 0)
+    out = np.empty((dirs.shape[0], 25), np.float32)
+    co = _options().to_c()
+    rc = R.lib().rto_probe_basis(dt._h, C.byref(co), C.c_void_p(dirs.ctypes.data), dirs.shape[0], 0, C.c_void_p(out.ctypes.data))
+    assert rc == E_FORMAT
+    dt.free()
+
+
+# ------------------------------------------------------------------ GPU: whole frames against the restatement
+
+
+def _slot_tree(t):
+    """RGBA tree on t's child[] and sigma whose r, g, b are the digits (base 2048, exact in fp16) of the leaf slot"""
+    n = t.capacity * 8
+    slot = np.arange(n, dtype=np.int64)
+    rgb = np.stack([slot % 2048, (slot // 2048) % 2048, slot // (2048 * 2048)], 1).astype(np.float16)
+    data = np.concatenate([rgb, t.data.reshape(n, -1)[:, -1:]], 1).reshape(t.capacity, 2, 2, 2, 4)
+    return orc.HostTree(t.child, data, t.scale, t.offset, "RGBA")
+
+
+def _expected_frame(t, W, H, fx, transform12, rng_frame, bg=1.0, **optkw):
+    """aux [8,H,W], image [H,W,4] of t at SPP 1 from the oracle's hit leaf and the restated shading"""
+    cam = orc.camera(W, H, fx, fx, transform12)
+    aux_s, _, _ = orc.render_frame(_slot_tree(t), cam, orc.default_options(spp=1, background_brightness=bg, **optkw),
+                                   orc.rng(frame=rng_frame), threads=oracle_threads())
+    hit = aux_s[3].reshape(-1) == 1.0
+    assert set(np.unique(aux_s[3])) <= {0.0, 1.0}
+    digits = aux_s[:3].reshape(3, -1)[:, hit].astype(np.int64)
+    slot = digits[0] + 2048 * (digits[1] + 2048 * digits[2])
+    ys, xs = np.divmod(np.flatnonzero(hit), W)
+    vdir = ref.pixel_vdir(W, H, fx, fx, transform12, xs, ys)
+    kind = "".join(c for c in t.data_format if c.isalpha())
+    basis_fn = ref.basis(kind, t.extra, vdir, **optkw)
+    D = t.data_dim
+    coeffs = t.data.reshape(-1, D)[slot, : D - 1].astype(np.float32)
+    rgb = ref.shade_leaf(basis_fn, coeffs)
+    px = np.full((H * W, 4), np.float32(0))
+    px[:, :3] = np.float32(bg)
+    px[hit, :3] = rgb
+    px[hit, 3] = 1.0
+    aux = np.concatenate([px.T, (px * px).T]).reshape(8, H, W)
+    image = np.concatenate([px[:, :3], np.ones((H * W, 1), np.float32)], 1).reshape(H, W, 4)
+    return aux.astype(np.float32), image.astype(np.float32), int(hit.sum())
+
+
+FRAME_TREES = [("SG", 16), ("ASG", 9), ("SG", 7), ("ASG", 25), ("SG", 4), ("ASG", 16)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,B", FRAME_TREES)
+def test_frames_at_spp1_equal_the_restatement(kind, B):
+    W, H = 96, 72
+    t = _lobed(kind, B, depth=6, seed=7, lobe_seed=B)
+    dt = R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra)
+    fx = synth.blender_focal(W)
+    poses = synth.orbit_poses(5)
+    optsets = [dict(), dict(rot_dirs=[0.2, 0.5, -0.4], basis_minmax=[0, B - 3])] if kind == "SG" and B == 16 else [dict()]
+    for optkw in optsets:
+        cams, want = [], []
+        for i in (1, 3):
+            cam = R.Camera(W, H, fx, fx)
+            cam.set_c2w(poses[i])
+            cams.append(cam)
+            aux, image, hits = _expected_frame(t, W, H, fx, cam.transform.reshape(-1), rng_frame=i, **optkw)
+            assert hits > 500
+            want.append((aux, image))
+        ctx = R.RenderContext(W, H)
+        for kernel in (R.KERNEL_GENERIC, R.KERNEL_FAST, R.KERNEL_AUTO):
+            for (aux, image), cam, i in zip(want, cams, (1, 3)):
+                ctx.rng_seed()
+                for _ in range(i):
+                    ctx.rng_advance()
+                ctx.set_kernel(kernel)
+                R.launch_renderer(dt, cam, R.RenderOptions(spp=1, denoise=False, **optkw), ctx)
+                assert_bits_equal(ctx.download_aux(), aux, "%s%d kernel %d aux" % (kind, B, kernel))
+                assert_bits_equal(ctx.download_image(), image, "%s%d kernel %d image" % (kind, B, kernel))
+        bctx = R.RenderContext(W, H, frames=2)
+        bctx.rng_seed()
+        R.launch_renderer_batch(dt, cams, R.RenderOptions(spp=1, denoise=False, **optkw), bctx, rng_jumps=[1, 3])
+        for f, (aux, image) in enumerate(want):
+            bctx.select_frame(f)
+            assert_bits_equal(bctx.download_aux(), aux, "%s%d batched frame %d aux" % (kind, B, f))
+            assert_bits_equal(bctx.download_image(), image, "%s%d batched frame %d image" % (kind, B, f))
+    dt.free()
+
+
+# ------------------------------------------------------------------ GPU: the kernels agree at every SPP
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,B", [("SG", 16), ("ASG", 9), ("ASG", 7)])
+def test_kernels_agree_at_every_spp(kind, B):
+    W, H = 80, 64
+    t = _lobed(kind, B, depth=6, seed=7, lobe_seed=B + 1)
+    dt = R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra)
+    fx = synth.blender_focal(W)
+    cams = []
+    for p in synth.orbit_poses(3):
+        c = R.Camera(W, H, fx, fx)
+        c.set_c2w(p)
+        cams.append(c)
+    ctx = R.RenderContext(W, H)
+    bctx = R.RenderContext(W, H, frames=3)
+    for spp in (1, 2, 3, 4, 6, 8, 16, 32):
+        opt = R.RenderOptions(spp=spp, denoise=False)
+        bctx.rng_seed()
+        R.launch_renderer_batch(dt, cams, opt, bctx, rng_jumps=[4, 0, 2])
+        for f, jumps in enumerate((4, 0, 2)):
+            outs = []
+            for kernel in (R.KERNEL_GENERIC, R.KERNEL_FAST):
+                ctx.rng_seed()
+                for _ in range(jumps):
+                    ctx.rng_advance()
+                ctx.set_kernel(kernel)
+                R.launch_renderer(dt, cams[f], opt, ctx)
+                outs.append((ctx.download_aux(), ctx.download_image()))
+            bctx.select_frame(f)
+            outs.append((bctx.download_aux(), bctx.download_image()))
+            for a, im in outs[1:]:
+                assert_bits_equal(a, outs[0][0], "%s%d spp %d frame %d aux" % (kind, B, spp, f))
+                assert_bits_equal(im, outs[0][1], "%s%d spp %d frame %d image" % (kind, B, spp, f))
+    dt.free()
+
+
+@pytest.mark.gpu
+def test_sparse_lean_outputs_denoise_like_lean():
+    import torch
+    from rt_octree_amd import denoiser
+    W, H, n = 160, 120, 3
+    t = _lobed("SG", 16, depth=6, seed=7)
+    dt = R.N3Tree.from_arrays(t.child, t.data, t.scale, t.offset, t.data_format, extra_data=t.extra)
+    torch.manual_seed(3)
+    net = denoiser.FusedGuidanceNet(denoiser.GuidanceNetCompact.from_full(denoiser.GuidanceNet(8, 32, 5, 2, 4)).eval())
+    fx = synth.blender_focal(W)
+    cams = []
+    for p in synth.orbit_poses(n):
+        c = R.Camera(W, H, fx, fx)
+        c.set_c2w(p)
+        cams.append(c)
+    images = []
+    for level in (1, 2):
+        ctx = R.RenderContext(W, H, frames=n)
+        ctx.set_lean_outputs(level)
+        ctx.rng_seed()
+        R.launch_renderer_batch(dt, cams, R.RenderOptions(spp=6, denoise=True), ctx)
+        ctx.select_frame(0)
+        net.denoise(ctx, n=n)
+        torch.cuda.synchronize()
+        images.append(torch.as_tensor(ctx.batch_views()[2], device="cuda:0")[:n].cpu().numpy().copy())
+    assert_bits_equal(images[1], images[0], "sparse lean vs lean, denoised")
+    dt.free()
+
+
+# ------------------------------------------------------------------ GPU: CLI, refusals
+
+
+@pytest.mark.gpu
+def test_cli_renders_an_sg_tree_like_the_python_api(tmp_path):
+    from PIL import Image
+    W, H = 96, 64
+    t = _lobed("SG", 9, depth=6, seed=7)
+    tp = t.save_npz(str(tmp_path / "tree.npz"))
+    poses = synth.orbit_poses(2)
+    pp = synth.write_transforms_json(str(tmp_path / "transforms_test.json"), poses)
+    op = synth.write_opt_json(str(tmp_path / "opt.json"), denoise=False, spp=6)
+    out = str(tmp_path / "out")
+    r = subprocess.run([BIN, tp, pp, "--options", op, "-w", str(W), "-h", str(H), "-o", out, "--warmup", "2"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    dt = R.N3Tree(tp)
+    ctx = R.RenderContext(W, H)
+    fx = synth.blender_focal(W)
+    cam = R.Camera(W, H, fx, fx)
+    for i in range(2):
+        cam.set_c2w(poses[i])
+        ctx.rng_seed()
+        for _ in range(2 + i):
+            ctx.rng_advance()
+        R.launch_renderer(dt, cam, R.RenderOptions(spp=6, denoise=False), ctx)
+        got = np.array(Image.open(os.path.join(out, "r_%d.png" % i)))
+        assert np.array_equal(got, ctx.download_rgba8()), i
+    dt.free()
+
+
+@pytest.mark.gpu
+def test_tree_without_lobes_and_quant_direct_are_refused(tmp_path):
+    t = _lobed("SG", 4, depth=4)
+    bare = R.N3Tree(_save(t, tmp_path / "bare.npz", extra_data=None))  # loads
+    cam = R.Camera(32, 24, 40.0, 40.0)
+    cam.set_c2w(synth.orbit_poses(1)[0])
+    ctx = R.RenderContext(32, 24)
+    for kernel in (R.KERNEL_GENERIC, R.KERNEL_FAST):
+        ctx.set_kernel(kernel)
+        with pytest.raises(R.RtoError) as e:
+            R.launch_renderer(bare, cam, R.RenderOptions(spp=1), ctx)
+        assert e.value.code == E_FORMAT and "extra_data" in e.value.msg
+    with pytest.raises(R.RtoError) as e:
+        R.launch_renderer_batch(bare, [cam], R.RenderOptions(spp=1), ctx)
+    assert e.value.code == E_FORMAT
+    bare.free()
+    # a quantised SG file: expanded it renders, kept quantised it is not built
+    sh = synth.make_tree(depth_limit=4, basis_dim=4, seed=5)
+    qp = str(tmp_path / "q.npz")
+    sh.save_quant_npz(qp, n_retain=1)
+    z = dict(np.load(qp))
+    z["data_format"] = np.array("SG4")
+    z["extra_data"] = t.extra
+    np.savez(qp, **z)
+    dense = R.N3Tree(qp)
+    R.launch_renderer(dense, cam, R.RenderOptions(spp=1), ctx)
+    dense.free()
+    with pytest.raises(R.RtoError) as e:
+        R.N3Tree(qp, quant_direct=True)
+    assert e.value.code == E_UNSUPPORTED
