@@ -217,7 +217,8 @@ int rto_ctx_set_kernel(rto_ctx* c, int kernel);
  * with stealing; 0 = a single queue), "tile_major" / "tile_block" (queue order), "queue_bands" (the XCD queues take bands of this many
  * 8-pixel tile rows, band j -> queue j % 8; 0 = angular wedges around the image centre; default 3), "cull" (1 = skip the tiles whose rays provably meet no density, the default; 0 = march every ray), "blocks_per_cu" (0 = as many
  * workgroups of the persistent traversal kernel per CU as fit, else a cap 1..8: the kernel's true occupancy knob --
- * `refill`'s waves/SIMD only sets the register budget). */
+ * `refill`'s waves/SIMD only sets the register budget); rto_launch_rays: "ray_order" (0 = workgroup b takes rays 256 b .. 256 b + 255,
+ * 1 = each XCD takes one contiguous range of the rays). */
 int rto_ctx_set_tuning(rto_ctx* c, const char* key, int value);
 /* Lean outputs of the batched render -> denoise route (round 5; off by default).  The reference's kernel stores, per pixel,
  * 8 aux planes and an RGBA32F image (volrend.cu:187-212: 48 bytes) -- of which its own denoise stage reads aux planes 0..3
@@ -299,6 +300,34 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
  * loop (main_headless.cpp:485-506).  ctx.rng itself is not modified.  Needs an N == 2 tree. */
 int rto_launch_renderer_batch(const rto_tree* tree, const rto_camera* cams, const int64_t* rng_jumps, int n,
                               const rto_options* options, rto_ctx* ctx, void* stream);
+
+/* ---- rays from the caller (no reference counterpart) ---- */
+/* A batch of arbitrary rays.  All pointers are device memory on the tree's device, float32, contiguous. */
+typedef struct rto_rays {
+    const float* origins;    /* [n][3] world space */
+    const float* dirs;       /* [n][3] world space; need not be unit length */
+    const float* t_max;      /* [n] or NULL (= 1e9f): world distance along the unit direction where the ray stops (a depth
+                                surface, volrend.cu:146-152 with offscreen = false); +inf = no limit */
+    const float* background; /* [n][3] or NULL (= options->background_brightness): the colour composited behind the ray
+                                (volrend.cu:161-185 with offscreen = false) */
+    int64_t n;               /* >= 0 */
+    int64_t first_ray;       /* >= 0: RNG index of ray 0 */
+} rto_rays;
+
+/* out[i] = (r, g, b, alpha) of ray i: its colour composited over its backdrop, alpha = accumulated opacity (aux plane 3 of a
+ * frame).  `out` is [n][4] float32 device memory, 16-byte aligned.  Asynchronous on `stream`: no host sync and no host-to-device
+ * copy per call.  Uses ctx for the RNG (ctx.rng advanced by (first_ray + i) * spp; ctx.rng itself is not modified), the jump
+ * table, the device and the kernel choice (rto_ctx_set_kernel); ctx's frame buffers and size play no part.
+ * Ray i is traced as the frame kernels trace a pixel whose ray_setup produced normalize3(dirs[i]) and centre origins[i] (the NDC
+ * warp of an NDC tree included), with tmax_bg = t_max[i]: a ray built as a camera pixel's (rto_launch_renderer) gives that
+ * pixel's aux planes 0..3 bit for bit.  Splitting a batch into calls with matching first_ray gives the same results.
+ * A degenerate ray -- non-finite origin, a direction that is zero, NaN, infinite or whose squared length under- / overflows,
+ * t_max <= 0 or NaN -- returns its backdrop with alpha 0.
+ * RTO_E_INVALID: a null argument, n < 0, first_ray < 0, null origins / dirs with n > 0, out not 16-byte aligned, tree and ctx
+ * on different devices; RTO_E_SPP; RTO_E_UNSUPPORTED: enable_probe, or a tree loaded with RTO_TREE_QUANT_DIRECT (its codebook
+ * shading lives only in the batched kernels); RTO_E_FORMAT: an SG / ASG tree without lobes.  n == 0 launches nothing. */
+int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_options* options, rto_ctx* ctx, float* out,
+                    void* stream);
 
 /* denoiser::filtering(stream, weight_map[L,H,W], guidance_map[L,H,W], img_in, img_out)
  * (filtering.cu:701-717).  All pointers are device pointers; img_in/img_out are [H][W][4] f32

@@ -36,6 +36,12 @@ class CCamera(C.Structure):
                 ("transform", C.c_float * 12)]
 
 
+class CRays(C.Structure):
+    """rto_rays (include/rto.h): device pointers to the ray buffers"""
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("t_max", C.c_void_p), ("background", C.c_void_p),
+                ("n", C.c_int64), ("first_ray", C.c_int64)]
+
+
 class CTreeInfo(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64), ("N", C.c_int), ("data_dim", C.c_int), ("format", C.c_int),
@@ -100,6 +106,7 @@ SYMBOLS = {
     "rto_wide_image_probe": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
     "rto_launch_renderer": (C.c_int, [_P, C.POINTER(CCamera), C.POINTER(COptions), _P, _P]),
     "rto_launch_renderer_batch": (C.c_int, [_P, C.POINTER(CCamera), C.POINTER(C.c_int64), C.c_int, C.POINTER(COptions), _P, _P]),
+    "rto_launch_rays": (C.c_int, [_P, C.POINTER(CRays), C.POINTER(COptions), _P, _P, _P]),
     "rto_filtering_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rto_filtering_batch_mode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
     "rto_filtering_train_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

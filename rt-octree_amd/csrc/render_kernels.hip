@@ -58,6 +58,22 @@ RTO_DEV void normalize3(float* d) {
     d[2] *= invnorm;
 }
 
+// volrend.cu:35-56,142-144: a ray's (dir, cen) in world space -> tree space (the NDC warp, then offset + scale * cen)
+RTO_DEV void ray_to_tree(const TreeDev& tree, float* dir, float* cen) {
+    if (tree.ndc_width > 0) {  // maybe_world2ndc :35-56
+        const float t = -(1.f + cen[2]) / dir[2];
+        for (int i = 0; i < 3; ++i) cen[i] = cen[i] + t * dir[i];
+        dir[0] = -((2 * tree.ndc_focal) / tree.ndc_width) * (dir[0] / dir[2] - cen[0] / cen[2]);
+        dir[1] = -((2 * tree.ndc_focal) / tree.ndc_height) * (dir[1] / dir[2] - cen[1] / cen[2]);
+        dir[2] = -2 / cen[2];
+        cen[0] = -((2 * tree.ndc_focal) / tree.ndc_width) * (cen[0] / cen[2]);
+        cen[1] = -((2 * tree.ndc_focal) / tree.ndc_height) * (cen[1] / cen[2]);
+        cen[2] = 1 + 2 / cen[2];
+        normalize3(dir);
+    }
+    for (int i = 0; i < 3; ++i) cen[i] = tree.offset[i] + tree.scale[i] * cen[i];
+}
+
 // volrend.cu:23-56,138-144: pixel -> (dir, vdir, cen) in tree space
 RTO_DEV void ray_setup(int x, int y, const CamDev& cam, const TreeDev& tree, float* dir, float* vdir,
                        float* cen) {
@@ -73,18 +89,46 @@ RTO_DEV void ray_setup(int x, int y, const CamDev& cam, const TreeDev& tree, flo
     vdir[0] = dir[0];
     vdir[1] = dir[1];
     vdir[2] = dir[2];
-    if (tree.ndc_width > 0) {  // maybe_world2ndc :35-56
-        const float t = -(1.f + cen[2]) / dir[2];
-        for (int i = 0; i < 3; ++i) cen[i] = cen[i] + t * dir[i];
-        dir[0] = -((2 * tree.ndc_focal) / tree.ndc_width) * (dir[0] / dir[2] - cen[0] / cen[2]);
-        dir[1] = -((2 * tree.ndc_focal) / tree.ndc_height) * (dir[1] / dir[2] - cen[1] / cen[2]);
-        dir[2] = -2 / cen[2];
-        cen[0] = -((2 * tree.ndc_focal) / tree.ndc_width) * (cen[0] / cen[2]);
-        cen[1] = -((2 * tree.ndc_focal) / tree.ndc_height) * (cen[1] / cen[2]);
-        cen[2] = 1 + 2 / cen[2];
-        normalize3(dir);
+    ray_to_tree(tree, dir, cen);
+}
+
+// rto_launch_rays: ray i of the batch -> (dir, vdir, cen) in tree space, the way ray_setup turns a pixel's (M xyz, centre)
+// into them, and its depth limit and backdrop.  false: a degenerate ray, which is not traced (its result is the backdrop with
+// alpha 0) -- a direction normalize3 cannot normalise (zero, NaN, infinite, or a squared length that under- / overflows),
+// a non-finite origin or NDC image of it, a t_max that is not > 0 (NaN included)
+RTO_DEV bool ray_from_batch(const RayBatch& rb, uint32_t i, const TreeDev& tree, float bg_default, float* dir, float* vdir,
+                            float* cen, float& tmax_bg, float* bg) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        dir[c] = rb.dirs[3 * (uint64_t)i + c];
+        cen[c] = rb.origins[3 * (uint64_t)i + c];
+        bg[c] = rb.background ? rb.background[3 * (uint64_t)i + c] : bg_default;
     }
-    for (int i = 0; i < 3; ++i) cen[i] = tree.offset[i] + tree.scale[i] * cen[i];
+    tmax_bg = rb.t_max ? rb.t_max[i] : 1e9f;
+    normalize3(dir);
+    vdir[0] = dir[0];
+    vdir[1] = dir[1];
+    vdir[2] = dir[2];
+    ray_to_tree(tree, dir, cen);
+    bool ok = tmax_bg > 0.f && (dir[0] != 0.f || dir[1] != 0.f || dir[2] != 0.f);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ok = ok && __builtin_isfinite(dir[c]) && __builtin_isfinite(cen[c]);
+    return ok;
+}
+
+// block b's ray for thread tid (RayBatch::per_xcd); >= rb.n: none
+RTO_DEV uint32_t ray_index(const RayBatch& rb, uint32_t b, int tid) {
+    const uint32_t chunk = rb.per_xcd ? (b & 7u) * rb.per_xcd + (b >> 3) : b;
+    return chunk * 256u + (uint32_t)tid;
+}
+
+// volrend.cu:161-185 with offscreen = false, per ray: the result composited over the ray's backdrop, alpha = accumulated opacity
+RTO_DEV void write_ray(const RayBatch& rb, uint32_t i, const float* bg, float* out) {
+    const float nalpha = 1.f - out[3];
+    out[0] += bg[0] * nalpha;
+    out[1] += bg[1] * nalpha;
+    out[2] += bg[2] * nalpha;
+    rb.out[i] = make_float4(out[0], out[1], out[2], out[3]);
 }
 
 // rt_core.cuh:206-222: scale dir, invdir, slab test.  returns false when the ray misses the box.
@@ -360,82 +404,16 @@ RTO_DEV int64_t query_from_root(const TreeDev& tree, float* xyz, float& cube_sz)
 template <int SPP>
 __global__ void __launch_bounds__(256) render_generic(const TreeDev tree, const CamDev cam, const OptDev opt,
                                                        const Pcg32 rng_base, const FrameOut fo) {
-    const int64_t SIZE = (int64_t)cam.width * cam.height;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= SIZE) return;
-    const int x = idx % cam.width, y = idx / cam.width;
-    float out[4] = {0.f, 0.f, 0.f, 0.f};
+#include "rto_render_generic.inc"
+}
 
-    if (tree.N > 0) {  // enable_draw volrend.cu:98
-        float dir[3], vdir[3], cen[3], invdir[3];
-        ray_setup(x, y, cam, tree, dir, vdir, cen);
-        Pcg32 rng = rng_base;
-        pcg_advance(rng, (int64_t)(idx * SPP));  // volrend.cu:157
-        float delta_scale, tmin, tmax;
-        if (ray_enter(tree, opt, dir, cen, 1e9f, invdir, delta_scale, tmin, tmax)) {
-            // sample_dst rt_core.cuh:67-193
-            float dst[SPP + 1];
-            for (int n = 1; n <= SPP; ++n) {
-                const float tv = -det_log_one_minus(pcg_next_float(rng));
-                if (n == 1) {
-                    dst[0] = tv;
-                } else if (tv <= dst[0]) {
-                    for (int i = n - 1; i > 0; i--) dst[i] = dst[i - 1];
-                    dst[0] = tv;
-                } else {
-                    int i = n - 1;
-                    while (dst[i - 1] > tv) {
-                        dst[i] = dst[i - 1];
-                        i--;
-                    }
-                    dst[i] = tv;
-                }
-            }
-            dst[SPP] = 3.402823466e+38f;
-
-            int64_t tree_vals[SPP];
-            float cnts[SPP];
-            for (int i = 0; i < SPP; ++i) cnts[i] = 0.f;
-            uint32_t spp = 0, sh_nums = 0;
-            float src = 0;
-            float t = tmin;
-            while (t < tmax) {  // rt_core.cuh:241-270
-                float pos[3] = {cen[0] + t * dir[0], cen[1] + t * dir[1], cen[2] + t * dir[2]};
-                float cube_sz;
-                const int64_t leaf = query_from_root(tree, pos, cube_sz);
-                const float t_subcube = dda_unit(pos, invdir) / cube_sz;
-                const float delta_t = t_subcube + opt.step_size;
-                const float sigma = half_bits_to_float(tree.data[leaf * tree.data_dim + tree.data_dim - 1]);
-                if (sigma > opt.sigma_thresh) {
-                    const float delta = delta_t * delta_scale * sigma;
-                    if (src + delta >= dst[spp]) {
-                        float& cnt = cnts[sh_nums];
-                        tree_vals[sh_nums] = leaf;
-                        ++sh_nums;
-                        do {
-                            ++cnt;
-                            ++spp;
-                        } while (src + delta >= dst[spp]);
-                        if (spp == SPP) break;
-                    }
-                    src += delta;
-                }
-                t += delta_t;
-            }
-            if (sh_nums != 0) {
-                float basis_fn[RTO_BASIS_MAX_DEV];
-                ray_basis_any(tree, opt, vdir, basis_fn);
-                for (uint32_t i = 0; i < sh_nums; i++)
-                    shade_leaf(tree, tree.data + tree_vals[i] * tree.data_dim, basis_fn, cnts[i], out);
-                constexpr float INV_SPP = 1.0f / SPP;
-                out[0] *= INV_SPP;
-                out[1] *= INV_SPP;
-                out[2] *= INV_SPP;
-                out[3] *= INV_SPP;
-            }
-        }
-    }
-    write_pixel(fo, SIZE, idx, opt.background_brightness, out);
+// rto_launch_rays on any tree the fast kernel does not take (N != 2, hit entries too wide) and RTO_KERNEL_GENERIC
+template <int SPP>
+__global__ void __launch_bounds__(256) render_rays_generic(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
+                                                            const RayBatch rays) {
+#define RTO_GENERIC_RAYS 1
+#include "rto_render_generic.inc"
+#undef RTO_GENERIC_RAYS
 }
 
 // ------------------------------------------------------------------ traversal image
@@ -721,6 +699,17 @@ __global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_
                                                           const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
                                                           const TileMap tm, const FrameOut fo) {
 #include "rto_render_fast.inc"
+}
+
+// rto_launch_rays on an N == 2 tree: the same body with the rays of the batch for the camera's pixels -- one thread per ray, no
+// tile map and no culling marks (both are per camera tile), each ray's own depth limit and backdrop, a float4 per ray
+template <int SPP, bool WIDE, int STACK, int LOBES>
+__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_rays(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
+                                                    const PcgJumpEntry* __restrict__ jump, const RayBatch rays) {
+    constexpr bool STATS = false;
+#define RTO_FAST_RAYS 1
+#include "rto_render_fast.inc"
+#undef RTO_FAST_RAYS
 }
 
 // ------------------------------------------------------------------ persistent kernel (N == 2)
@@ -1949,6 +1938,62 @@ static hipError_t launch_spp(int kernel, const TreeDev& tree, const CamDev& cam,
                            opt, rng, fo);
     }
     return hipGetLastError();
+}
+
+template <int SPP, int LOBES>
+static void launch_rays_fast(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump, const RayBatch& rb,
+                             const dim3 grid, hipStream_t stream) {
+    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
+#define RTO_RAYS(WI, SK) hipLaunchKernelGGL((render_rays<SPP, WI, SK, LOBES>), grid, dim3(256), lds, stream, tree, opt, rng, jump, rb)
+    if (tree.widew) {  // (launch_fast's choice)
+        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
+            RTO_RAYS(true, 1);
+        } else {
+            RTO_RAYS(true, 0);
+        }
+    } else {
+        RTO_RAYS(false, 0);
+    }
+#undef RTO_RAYS
+}
+
+template <int SPP>
+static hipError_t launch_rays_spp(int kernel, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                                  const RayBatch& rb_in, bool xcd_order, hipStream_t stream) {
+    RayBatch rb = rb_in;
+    const uint32_t blocks = (uint32_t)(((uint64_t)rb.n + 255) / 256);
+    rb.per_xcd = xcd_order ? (blocks + 7) / 8 : 0u;
+    const dim3 grid(xcd_order ? 8 * rb.per_xcd : blocks);
+    if (kernel == 2) {
+        if (tree.format == kFmtSG)
+            launch_rays_fast<SPP, kFmtSG>(tree, opt, rng, jump, rb, grid, stream);
+        else if (tree.format == kFmtASG)
+            launch_rays_fast<SPP, kFmtASG>(tree, opt, rng, jump, rb, grid, stream);
+        else
+            launch_rays_fast<SPP, 0>(tree, opt, rng, jump, rb, grid, stream);
+    } else {
+        hipLaunchKernelGGL(render_rays_generic<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                       const RayBatch& rb, bool xcd_order, hipStream_t stream) {
+    if (rb.n == 0) return hipSuccess;
+    if ((uint64_t)rb.n * (uint64_t)spp >= (uint64_t(1) << 32)) return hipErrorInvalidValue;  // (the RNG offset of a ray is 32-bit)
+    switch (spp) {
+#ifndef RTO_DEV_SPP6_ONLY
+        case 1: return launch_rays_spp<1>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 2: return launch_rays_spp<2>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 3: return launch_rays_spp<3>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 4: return launch_rays_spp<4>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 8: return launch_rays_spp<8>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 16: return launch_rays_spp<16>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        case 32: return launch_rays_spp<32>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+#endif
+        case 6: return launch_rays_spp<6>(kernel, tree, opt, rng, jump, rb, xcd_order, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_t* mask, int mask_words, hipStream_t stream) {

@@ -118,6 +118,10 @@ struct rto_tree {
 #ifndef RTO_QUEUE_BANDS_DEFAULT
 #define RTO_QUEUE_BANDS_DEFAULT 3
 #endif
+// rto_launch_rays: which rays a workgroup takes (RayBatch::per_xcd); see DESIGN.md "Rays from the caller"
+#ifndef RTO_RAY_ORDER_DEFAULT
+#define RTO_RAY_ORDER_DEFAULT 0
+#endif
 struct rto_ctx {
     int device = 0;
     int width = 0, height = 0;
@@ -169,6 +173,7 @@ struct rto_ctx {
     bool jump_valid = false;
     int kernel = RTO_KERNEL_AUTO;
     int strip_rows = 1;
+    int ray_order = RTO_RAY_ORDER_DEFAULT;  // tuning "ray_order" (rto_launch_rays): 0 = block b takes rays 256 b .., 1 = a contiguous range per XCD
     int refill = 0;  // 0 = the default instantiation; 100 * waves/SIMD + idle-lane threshold picks an A/B one
     bool tile_order_on = true;
     bool stats_on = false;
@@ -1516,6 +1521,9 @@ int rto_ctx_set_tuning(rto_ctx* c, const char* key, int value) {
         c->occ.cap = value;
     } else if (k == "batch_fallback") {  // test hook: 1 = batched launches take the per-frame generic fallback (as a tree with too
         c->batch_fallback = value;       // many leaf slots for the SPP does), 2 = as if the device refused the traversal kernel's LDS
+    } else if (k == "ray_order") {  // rto_launch_rays: 0 = consecutive blocks of 256 rays, 1 = one contiguous range of rays per XCD
+        if (value < 0 || value > 1) return set_err(RTO_E_INVALID, "ray_order must be 0 or 1");
+        c->ray_order = value;
     } else if (k == "strip_rows") {
         if (value < 1) return set_err(RTO_E_INVALID, "strip_rows must be >= 1");
         c->strip_rows = value;
@@ -1738,6 +1746,62 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
 int rto_launch_renderer_batch(const rto_tree* tree, const rto_camera* cams, const int64_t* rng_jumps, int n,
                               const rto_options* o, rto_ctx* ctx, void* stream_) {
     return launch_batch_at(tree, cams, rng_jumps, n, o, ctx, stream_, 0);
+}
+
+int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_options* o, rto_ctx* ctx, float* out, void* stream_) {
+    if (!tree || !rays || !o || !ctx || !out) return set_err(RTO_E_INVALID, "rto_launch_rays: null argument");
+    if (rays->n < 0 || rays->first_ray < 0) return set_err(RTO_E_INVALID, "rto_launch_rays: n and first_ray must be >= 0");
+    if (rays->n > 0 && (!rays->origins || !rays->dirs)) return set_err(RTO_E_INVALID, "rto_launch_rays: null origins / dirs");
+    if ((uintptr_t)out % 16 != 0) return set_err(RTO_E_INVALID, "rto_launch_rays: out must be 16-byte aligned");
+    if (tree->quant)
+        return set_err(RTO_E_UNSUPPORTED, "a quantised tree loaded with RTO_TREE_QUANT_DIRECT is shaded by the batched kernels only: "
+                                          "rto_launch_rays needs an expanded tree");
+    if (!spp_supported(o->spp))
+        return set_err(RTO_E_SPP, "spp == " + std::to_string(o->spp) + " not supported. (supported: 1,2,3,4,6,8,16,32)");
+    if (tree->device != ctx->device) return set_err(RTO_E_INVALID, "tree and context live on different devices");
+    if (tree->d_recidx && !(o->sigma_thresh >= 0.f))
+        return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps coefficient records for leaves of positive "
+                                          "density only: sigma_thresh must be >= 0");
+    if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature, not on the headless path");
+    if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
+
+    int kernel = ctx->kernel;
+    rto::TreeDev tdev;
+    const bool fast_here = fast_path_for_spp(tree, o->spp, ctx->test_wide_bits, &tdev) != 0;
+    if (kernel == RTO_KERNEL_AUTO) kernel = fast_here ? RTO_KERNEL_FAST : RTO_KERNEL_GENERIC;
+    if (kernel == RTO_KERNEL_FAST && !fast_here)
+        return set_err(RTO_E_UNSUPPORTED, "fast kernel needs an N == 2 tree of depth <= 24 whose leaf slots fit 31 - ceil(log2 spp) bits");
+    if (rays->n == 0) return RTO_OK;
+
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = kernel == RTO_KERNEL_FAST ? ensure_jump_table(ctx, stream) : ensure_reference_arrays(tree);  // (once per RNG stream / tree)
+    if (rc != RTO_OK) return rc;
+    const rto::OptDev od = make_opt_dev(o);
+    // a launch takes fewer than 2^32 / spp rays (the kernels' RNG offset i * spp is 32-bit; the grid's last blocks stay below 2^32 too)
+    const int64_t per_launch = (int64_t)((0xffffffffull / (uint64_t)o->spp - 4096) & ~255ull);
+    for (int64_t i0 = 0; i0 < rays->n; i0 += per_launch) {
+        const int64_t n = std::min(per_launch, rays->n - i0);
+        rto::RayBatch rb;
+        rb.origins = rays->origins + 3 * i0;
+        rb.dirs = rays->dirs + 3 * i0;
+        rb.t_max = rays->t_max ? rays->t_max + i0 : nullptr;
+        rb.background = rays->background ? rays->background + 3 * i0 : nullptr;
+        rb.out = reinterpret_cast<float4*>(out) + i0;
+        rb.n = (uint32_t)n;
+        rb.per_xcd = 0;
+        // ray i0 + i draws from ctx.rng advanced by (first_ray + i0 + i) * spp: the host takes (first_ray + i0) * spp (mod 2^64,
+        // the generator's period), the kernel i * spp
+        const rto::PcgJumpEntry j = pcg_jump(ctx->rng.inc, (uint64_t)(rays->first_ray + i0) * (uint64_t)o->spp);
+        rto::Pcg32 rng = ctx->rng;
+        rng.state = j.mult * ctx->rng.state + j.plus;
+        // (the generic kernel reads tree->dev itself: child[] / data[] may just have been rebuilt by ensure_reference_arrays)
+        const hipError_t e = rto::launch_rays(kernel, o->spp, kernel == RTO_KERNEL_FAST ? tdev : tree->dev, od, rng, ctx->jump, rb,
+                                              ctx->ray_order != 0, stream);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("ray launch failed: ") + hipGetErrorString(e));
+    }
+    return RTO_OK;
 }
 
 // The frames of a batched call rendered one by one with the generic kernel (render_generic: any N, any depth, any slot

@@ -192,6 +192,18 @@ struct FrameOut {
     const uint32_t* cull_marks;
     int cull_mask_words;
 };
+// The rays of one render_rays / render_rays_generic launch (rto_launch_rays): ray i is origins[i], dirs[i], t_max[i] and
+// background[i], its result goes to out[i].  The host offsets the pointers by the launch's first ray and keeps n * spp < 2^32.
+struct RayBatch {
+    const float* origins;     // [n][3] world space
+    const float* dirs;        // [n][3] world space, any length
+    const float* t_max;       // [n] or nullptr (1e9f)
+    const float* background;  // [n][3] or nullptr (options.background_brightness)
+    float4* out;              // [n]: r, g, b after compositing, alpha
+    uint32_t n;
+    uint32_t per_xcd;         // 0: block b takes rays 256 b ..; else workgroups per XCD: each XCD takes one contiguous range
+};
+
 // stats[0..5] = SURVEY 8d's units over EVERY ray (orc_stats order: rays, rays_in_box, steps, levels of a root-restart walk,
 // hit leaves, rays with a hit); stats[6..11] = the same frame as the batched path works through it: rays of marked tiles,
 // their march steps, top-grid entries loaded (8 B each), traversal-image words loaded (4 B each), hit entries written,

@@ -32,6 +32,12 @@ TileMap make_tile_map(int width, int height, int strip_rows);
 hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
                          const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, hipStream_t stream);
 
+// rto_launch_rays: the rb.n rays of rb (rb.n * spp < 2^32, else hipErrorInvalidValue) with the fast (2: render_rays) or the generic
+// (1: render_rays_generic) kernel; ray i draws its samples from rng advanced by i * spp.  xcd_order: each XCD takes one contiguous
+// range of the rays (RayBatch::per_xcd) instead of every eighth block of 256
+hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                       const RayBatch& rb, bool xcd_order, hipStream_t stream);
+
 // tile marks of ONE frame for the single-frame kernel's culling (FrameOut::cull_marks): zeroes `mask` ((tiles + 31) / 32 + 1
 // words) on the stream and projects the tree's culling cells into the camera
 hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_t* mask, int mask_words, hipStream_t stream);

@@ -1,8 +1,18 @@
 // rto_render_fast.inc -- body of the single-frame fast kernel, included by render_kernels.hip into render_fast (LOBES = 0: SH and
-// RGBA trees) and render_fast_lobes (LOBES = kFmtSG / kFmtASG).  In scope: the kernel parameters and SPP, STATS, WIDE, STACK,
-// LOBES.
+// RGBA trees), render_fast_lobes (LOBES = kFmtSG / kFmtASG) and render_rays (RTO_FAST_RAYS defined to 1 around the include: the
+// rays of rto_launch_rays instead of a camera's pixels).  In scope: the kernel parameters and SPP, STATS, WIDE, STACK, LOBES.
+// (The ray source is switched by the preprocessor, not by if constexpr: the frame kernels' text -- and so their code -- is
+// exactly what it was before the ray kernel existed.)
     extern __shared__ uint32_t s_stack[];  // [max_depth][256] ancestor node indices, level-major
 
+#if RTO_FAST_RAYS
+    const int tid = threadIdx.x;
+    const uint32_t ray = ray_index(rays, blockIdx.x, tid);
+    if (ray >= rays.n) return;
+    float out[4] = {0.f, 0.f, 0.f, 0.f};
+    float dir[3], vdir[3], cen[3], invdir[3], tmax_bg, bg[3];
+    const bool live = ray_from_batch(rays, ray, tree, opt.background_brightness, dir, vdir, cen, tmax_bg, bg);  // (false: degenerate)
+#else
     int tx, ty;
     if (!block_tile(tm, blockIdx.x, tx, ty)) return;
     const int tid = threadIdx.x;
@@ -23,12 +33,19 @@
     }
     float dir[3], vdir[3], cen[3], invdir[3];
     ray_setup(x, y, cam, tree, dir, vdir, cen);
+#endif
     float delta_scale, tmin, tmax;
     unsigned long long st_steps = 0, st_levels = 0, st_hits = 0, st_inbox = 0, st_grid = 0, st_words = 0, st_wide = 0;
+#if RTO_FAST_RAYS
+    if (live && ray_enter(tree, opt, dir, cen, tmax_bg, invdir, delta_scale, tmin, tmax)) {
+        Pcg32 rng = rng_base;
+        pcg_advance_tab(rng, ray * (uint32_t)SPP, jump);  // (the host keeps n * SPP < 2^32)
+#else
     if (ray_enter(tree, opt, dir, cen, 1e9f, invdir, delta_scale, tmin, tmax)) {
         if (STATS) st_inbox = 1;
         Pcg32 rng = rng_base;
         pcg_advance_tab(rng, (uint32_t)(idx * SPP), jump);
+#endif
 
         // thresholds, ascending; dst[0] is always the next one to cross (consumed ones shift out)
         float dst[SPP + 1];
@@ -272,6 +289,10 @@
             out[3] *= INV_SPP;
         }
     }
+#if RTO_FAST_RAYS
+    write_ray(rays, ray, bg, out);
+    (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
+#else
     write_pixel(fo, SIZE, idx, opt.background_brightness, out);
     if (STATS) {  // order as orc_stats: rays, rays_in_box, steps, levels, hit_leaves, hit_rays
         atomicAdd(fo.stats + 0, 1ULL);
@@ -297,3 +318,4 @@
             atomicAdd(fo.stats + 12, st_wide);
         }
     }
+#endif

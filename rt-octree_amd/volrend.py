@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COptions, CTreeInfo, RtoError, check, lib
+from ._lib import CCamera, COptions, CRays, CTreeInfo, RtoError, check, lib
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
@@ -435,8 +435,9 @@ class RenderContext:
 def launch_renderer(tree, cam, options, ctx, stream=None, offscreen=True):
     """volrend::launch_renderer(tree, cam, options, ctx, stream, offscreen)
     (renderer_kernel.hpp:11-16).  Asynchronous on `stream`.  Unsupported spp raises like the
-    reference's std::runtime_error("spp == N not supported.") (volrend.cu:275-277)."""
-    if not offscreen:
+    reference's std::runtime_error("spp == N not supported.") (volrend.cu:275-277).  offscreen=False (GL
+    interop) raises; the volume composited over the caller's depth and colour, per ray, is render_rays."""
+    if not offscreen:  # (per-ray depth limits and backdrops, the compositing of offscreen = false: render_rays)
         raise RtoError(-3, "only the offscreen (headless) path is built; GL interop is out of scope")
     cc, co = cam.to_c(), options.to_c()
     check(lib().rto_launch_renderer(tree._h, C.byref(cc), C.byref(co), ctx._h, _stream_ptr(stream)))
@@ -453,6 +454,73 @@ def launch_renderer_batch(tree, cams, options, ctx, stream=None, rng_jumps=None)
         jumps = (C.c_int64 * n)(*[int(j) for j in rng_jumps])
     co = options.to_c()
     check(lib().rto_launch_renderer_batch(tree._h, arr, jumps, n, C.byref(co), ctx._h, _stream_ptr(stream)))
+
+
+def camera_rays(cam):
+    """(origins, dirs) of a Camera's pixels, row-major: float32 [H*W, 3] numpy arrays.  dirs[i] is M xyz(x, y) as the frame
+    kernels compute it before normalising (float32, left to right, no FMA; volrend.cu:23-34), so render_rays of these rays
+    returns aux planes 0..3 of launch_renderer bit for bit; add t_max / background to composite the camera's view over a depth
+    and colour image."""
+    W, H = cam.width, cam.height
+    f = np.float32
+    x = np.arange(W, dtype=np.int64).astype(f)[None, :]
+    y = np.arange(H, dtype=np.int64).astype(f)[:, None]
+    with np.errstate(all="ignore"):
+        xyz0 = np.broadcast_to((x - f(0.5) * f(W)) / f(cam.fx), (H, W))
+        xyz1 = np.broadcast_to(-(y - f(0.5) * f(H)) / f(cam.fy), (H, W))
+        xyz2 = f(-1.0)
+        m = np.asarray(cam.transform, f).reshape(-1)
+        dirs = np.empty((H, W, 3), f)
+        for c in range(3):
+            dirs[..., c] = m[c] * xyz0 + m[3 + c] * xyz1 + m[6 + c] * xyz2
+    origins = np.broadcast_to(m[9:12], (H * W, 3)).copy()
+    return origins, dirs.reshape(H * W, 3)
+
+
+def _ray_tensor(a, name, cols, n, device):
+    """a contiguous float32 torch tensor [n, cols] (or [n]) on `device`: torch tensors are taken as they are, numpy arrays copied over"""
+    import torch
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+    if not isinstance(a, torch.Tensor):
+        raise TypeError("%s must be a torch tensor or a numpy array" % name)
+    want = (n, cols) if cols else (n,)
+    if a.dtype != torch.float32 or not a.is_contiguous() or tuple(a.shape) != want:
+        raise RtoError(-1, "%s must be a contiguous float32 tensor of shape %s" % (name, list(want)))
+    if a.device != device:
+        raise RtoError(-1, "%s lives on %s, the tree on %s" % (name, a.device, device))
+    return a
+
+
+def render_rays(tree, origins, dirs, options, ctx, t_max=None, background=None, first_ray=0, out=None, stream=None):
+    """rto_launch_rays: colour and opacity of n arbitrary rays.  origins / dirs [n, 3], t_max [n] (world distance along the unit
+    direction; None = 1e9), background [n, 3] (None = options.background_brightness): contiguous float32 torch tensors on the
+    tree's device, or numpy arrays (copied over).  Returns out, a float32 [n, 4] tensor (r, g, b composited over the backdrop,
+    alpha = accumulated opacity); pass `out` to fill one.  Ray i draws its samples from ctx.rng advanced by (first_ray + i) * spp.
+    Asynchronous on `stream` (default: torch's current stream); no sync."""
+    import torch
+    device = torch.device("cuda", tree.device)
+    n = int(origins.shape[0])
+    o = _ray_tensor(origins, "origins", 3, n, device)
+    d = _ray_tensor(dirs, "dirs", 3, n, device)
+    tm = None if t_max is None else _ray_tensor(t_max, "t_max", 0, n, device)
+    bg = None if background is None else _ray_tensor(background, "background", 3, n, device)
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.float32, device=device)
+    else:
+        out = _ray_tensor(out, "out", 4, n, device)
+    if n == 0:
+        return out
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    r = CRays()
+    r.origins, r.dirs = o.data_ptr(), d.data_ptr()
+    r.t_max = tm.data_ptr() if tm is not None else None
+    r.background = bg.data_ptr() if bg is not None else None
+    r.n, r.first_ray = n, int(first_ray)
+    co = options.to_c()
+    check(lib().rto_launch_rays(tree._h, C.byref(r), C.byref(co), ctx._h, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    return out
 
 
 def _dev_ptr(t):
