@@ -16,6 +16,49 @@ def rgba_tree(tree_sh, seed=3):
     return synth.SynthTree(tree_sh.child, data, tree_sh.scale, tree_sh.offset, "RGBA", tree_sh.depth_limit, {})
 
 
+# World frames (invradius3, offset) other than synth.make_tree's cube centred on the origin.  The tree-space content does not
+# move under a re-framing, so the object stays inside [0, 1)^3; the world it is seen from is stretched and shifted.
+FRAME_ANISO = ((0.5, 0.25, 0.3), (0.55, 0.4, 0.5))        # strongly anisotropic, off centre; x is the short world axis
+FRAME_ANISO_PERM = ((0.3, 0.5, 0.25), (0.5, 0.55, 0.4))   # the same values on other axes: y is the short one
+FRAME_OFF_CENTRE = ((1.0 / 3.0,) * 3, (0.3, 0.65, 0.5))   # isotropic, off centre
+FRAME_LARGE = ((0.01, 0.012, 0.008), (0.45, 0.5, 0.6))    # a world some hundred units across
+FRAME_SMALL = ((8.0, 6.0, 10.0), (0.5, 0.55, 0.4))        # a world an eighth of a unit across
+FRAMES = {"aniso": FRAME_ANISO, "aniso_perm": FRAME_ANISO_PERM, "off_centre": FRAME_OFF_CENTRE, "large": FRAME_LARGE,
+          "small": FRAME_SMALL}
+ANISO_FRAMES = ("aniso", "aniso_perm")
+
+
+def reframe(tree, scale3, offset3):
+    """The same SynthTree (topology, data, lobes) in another world frame: tree = offset3 + scale3 * world."""
+    scale3 = np.broadcast_to(np.asarray(scale3, np.float32), (3,)).copy()
+    offset3 = np.broadcast_to(np.asarray(offset3, np.float32), (3,)).copy()
+    return synth.SynthTree(tree.child, tree.data, scale3, offset3, tree.data_format, tree.depth_limit, tree.stats, tree.extra)
+
+
+def reframe_point(p, tree_from, tree_to):
+    """world' = (offset_from + scale_from * world - offset_to) / scale_to: the same tree-space point in the other world"""
+    p = np.asarray(p, np.float64)
+    q = tree_from.offset.astype(np.float64) + tree_from.scale.astype(np.float64) * p
+    return (q - tree_to.offset.astype(np.float64)) / tree_to.scale.astype(np.float64)
+
+
+def reframe_pose(c2w, tree_from, tree_to, target=None):
+    """A camera placed for tree_from's world, in tree_to's: the position is mapped with reframe_point, the orientation rebuilt
+    with synth.look_at_c2w towards the mapped `target` (a point of tree_from's world; default: the scene centre, tree-space
+    (0.5, 0.5, 0.5)).  An affine map does not keep a rotation a rotation, hence the rebuilding."""
+    c2w = np.asarray(c2w, np.float64)
+    if target is None:
+        target = (0.5 - tree_from.offset.astype(np.float64)) / tree_from.scale.astype(np.float64)
+    return synth.look_at_c2w(reframe_point(c2w[:3, 3], tree_from, tree_to), reframe_point(target, tree_from, tree_to))
+
+
+def aim_point(c2w, distance=None):
+    """the point `distance` (default: the camera's distance from the origin, at least 1) along the view axis of a look_at_c2w pose"""
+    c2w = np.asarray(c2w, np.float64)
+    pos = c2w[:3, 3]
+    return pos - c2w[:3, 2] * (max(np.linalg.norm(pos), 1.0) if distance is None else distance)
+
+
 def make_pair(tree, device=0):
     """-> (orc.HostTree, R.N3Tree) over the same arrays"""
     ht = orc.HostTree(tree.child, tree.data, tree.scale, tree.offset, tree.data_format)

@@ -9,7 +9,10 @@ the HIP kernels:
     z-scores have unit variance (a wrong `do { ++cnt; ++spp } while` or a wrong optical-depth factor
     shifts the mean; a wrong sample count per threshold shows up in the variance);
   * closed-form rays through a hand-built root node: one homogeneous medium, two media, a leaf below
-    sigma_thresh, a ray lying exactly in the face between two leaves, an SH leaf with opt.rot_dirs;
+    sigma_thresh, a ray lying exactly in the face between two leaves, an SH leaf with opt.rot_dirs, a depth limit
+    that falls inside a leaf;
+  * the same estimator on anisotropic and off-centre world frames, SH16 / SH25, SG / ASG lobes, an NDC tree, and single
+    rays with a depth limit, a backdrop of their own and directions of any length;
   * sample_dst for every supported SPP == the order statistics of -log(1 - u) over the pcg32 stream
     (pcg32 itself is pinned to the reference's header: tests/golden/pcg32_kat.json).
 CPU only; the GPU twin is tests/test_expectation_gpu.py."""
@@ -85,7 +88,7 @@ def test_estimator_mean_matches_rendering_equation(fmt, density):
 
 
 def test_estimator_mean_with_options():
-    """crop box, sigma threshold, step size, basis mask, rot_dirs: every option the kernel reads."""
+    """crop box (in tree units), sigma threshold, step size, basis mask, rot_dirs: every option the kernel reads."""
     t = _thin(synth.make_tree(depth_limit=5, basis_dim=9, seed=5, shell=1.5), 0.15)
     ht = orc.HostTree(t.child, t.data, t.scale, t.offset, t.data_format)
     W, H = 20, 20
@@ -110,7 +113,7 @@ def _root_only(values, fmt="RGBA"):
     return orc.HostTree(child, data, np.ones(3, np.float32), np.zeros(3, np.float32), fmt), data
 
 
-def _trace_many(ht, origin, direction, n_rays, spp, vdir=None, **optkw):
+def _trace_many(ht, origin, direction, n_rays, spp, vdir=None, t_max=1e9, **optkw):
     """Mean out[4] of n_rays independent calls of the oracle's trace_ray (each with its own RNG stream)."""
     L = orc.lib()
     opt = orc.default_options(spp=spp, **optkw)
@@ -123,7 +126,7 @@ def _trace_many(ht, origin, direction, n_rays, spp, vdir=None, **optkw):
         v = (C.c_float * 3)(*(direction if vdir is None else vdir))
         c = (C.c_float * 3)(*origin)
         out = (C.c_float * 4)(0, 0, 0, 0)
-        rc = L.orc_trace_ray(C.byref(ht.c), d, v, c, C.byref(opt), C.c_float(1e9), out, C.byref(r), None)
+        rc = L.orc_trace_ray(C.byref(ht.c), d, v, c, C.byref(opt), C.c_float(t_max), out, C.byref(r), None)
         assert rc == 0
         acc += np.array(out[:], np.float64)
     return acc / n_rays
@@ -213,6 +216,188 @@ def test_sh_leaf_colour_and_rot_dirs():
         want = 1.0 / (1.0 + np.exp(-(c16 @ real_sh(vd[None], 4)[0])))
         assert aux[3, 0, 0] == 1.0
         assert np.allclose(aux[:3, 0, 0], want, atol=2e-6), (rot, aux[:3, 0, 0], want)
+
+
+# ------------------------------------------------------------------ the same estimator, wider inputs
+def _estimator_case(t, pose, what, W=24, H=20, fx_factor=0.9, n_frames=128, spp=32, first_frame=0, bg=0.5, ndc=None,
+                    model_kw=None, need_stat=True, min_cover=60, **optkw):
+    """oracle frames of tree t at `pose` against the float64 model, as test_estimator_mean_matches_rendering_equation does"""
+    ht = orc.HostTree(t.child, t.data, t.scale, t.offset, t.data_format, ndc=ndc)
+    fx = fx_factor * synth.blender_focal(W)
+    cam = orc.camera(W, H, fx, fx, np.asarray(pose)[:3, :4].T.reshape(-1))
+    got = _mean_of_frames(ht, cam, n_frames, spp, first_frame=first_frame, background_brightness=bg, **optkw)
+    mean, var = E.expected_frame(E.Scene.of(t), pose, W, H, fx, fx, bg=bg, ndc=ndc, **(model_kw or {}))
+    assert (mean[3] > 0.05).sum() > min_cover, int((mean[3] > 0.05).sum())  # the object covers a good part of the image
+    _check_against_model(got, mean, var, n_frames * spp, what, need_stat=need_stat)
+
+
+def _thin_tree(basis=9, seed=3, density=0.08, depth=5):
+    return _thin(synth.make_tree(depth_limit=depth, basis_dim=basis, seed=seed, shell=1.5), density)
+
+
+@pytest.mark.parametrize("frame", ["aniso", "aniso_perm", "off_centre"])
+def test_estimator_mean_in_anisotropic_and_off_centre_frames(frame):
+    """invradius3 with three different values and a free offset: segment lengths are WORLD lengths, so the optical depth of
+    a leaf depends on the ray's direction through the per-axis scale (delta_scale of rt_core.cuh:53-65)."""
+    from helpers import FRAMES, reframe, reframe_pose
+    t0 = _thin_tree()
+    t = reframe(t0, *FRAMES[frame])
+    _estimator_case(t, reframe_pose(synth.orbit_poses(7)[3], t0, t), frame)
+
+
+@pytest.mark.parametrize("basis", [16, 25])
+def test_estimator_mean_sh16_sh25(basis):
+    """the two bases the benchmark times"""
+    _estimator_case(_thin_tree(basis=basis), synth.orbit_poses(7)[3], "SH%d" % basis, first_frame=500)
+
+
+NDC_POSE = synth.look_at_c2w((0.1, -0.05, 0.2), target=(0.0, 0.1, -4.0), up=(0, 1, 0))  # forward-facing, as LLFF cameras are
+
+
+def test_estimator_mean_ndc_tree():
+    """an NDC tree: rays are warped (NeRF appendix C) and marched in the warped world; the colour's view direction is the
+    unwarped one.  With ndc = the camera's own (W, H, focal) the frame spans the NDC cube [-1, 1]^3."""
+    W, H = 24, 20
+    fx = 0.9 * synth.blender_focal(W)
+    _estimator_case(_thin_tree(), NDC_POSE, "ndc", W=W, H=H, ndc=(float(W), float(H), fx), first_frame=700)
+
+
+def test_estimator_mean_with_options_anisotropic():
+    """test_estimator_mean_with_options on an anisotropic, off-centre tree.  The crop box (render_bbox) is given in TREE
+    units, [0, 1]^3 being the whole tree (rt_core.cuh:19-36 applies it to the tree-space ray), so it is the same numbers as
+    on the isotropic tree although the world is another; step_size is a tree-space length too."""
+    from helpers import FRAME_ANISO, reframe, reframe_pose
+    t0 = _thin_tree(seed=5)  # (thinner than there, 24 x 20 and another pose: 652 noisy values instead of 179)
+    t = reframe(t0, *FRAME_ANISO)
+    bbox = [0.05, 0.1, 0.0, 0.95, 0.9, 0.8]
+    rot = [0.2, -0.4, 0.3]
+    _estimator_case(t, reframe_pose(synth.orbit_poses(5)[3], t0, t), "options, anisotropic", fx_factor=1.0,
+                    first_frame=300, bg=1.0, render_bbox=bbox, sigma_thresh=3.0, step_size=5e-4, basis_minmax=[0, 3],
+                    rot_dirs=rot, model_kw=dict(rot_dirs=rot, bbox=bbox, sigma_thresh=3.0, step_size=5e-4, basis_minmax=(0, 3)))
+
+
+def _lobed_thin(kind, seed=3):
+    """an SG9 / ASG9 tree with moderate sharpness: the lobes are wide enough for the colour to vary with the view direction
+    over the whole frame (with_lobes' default spread reaches lambda = 2000, where a lobe is 0 almost everywhere)"""
+    t = _thin_tree()
+    d = t.data.astype(np.float32)
+    B = (d.shape[-1] - 1) // 3
+    coef = d[..., :3 * B].reshape(d.shape[:-1] + (3, B)).copy()
+    coef[..., 1:] *= 30.0  # (make_tree's coefficients decay with the SH band; here every lobe is to weigh like the first)
+    d[..., :3 * B] = coef.reshape(d.shape[:-1] + (3 * B,))
+    t = synth.SynthTree(t.child, d.astype(np.float16), t.scale, t.offset, t.data_format, t.depth_limit, {})
+    return synth.with_lobes(t, kind, seed=seed, lambda_max=8.0)
+
+
+@pytest.mark.parametrize("kind", ["SG", "ASG"])
+def test_estimator_mean_sg_asg(kind):
+    """The oracle marches but does not shade SG / ASG leaves, so the estimate is put together as tests/test_sg_asg.py does
+    for its bit-exact frames: which leaf a sample ends in comes from the oracle at SPP 1 (an RGBA tree over the same
+    child[] and sigma whose colours spell the leaf slot), that leaf's colour from the float32 restatement sg_asg_ref --
+    against the float64 lobes of the model."""
+    import sg_asg_ref as ref
+    from test_sg_asg import _slot_tree
+    t = _lobed_thin(kind)
+    W, H, n = 24, 20, 4096
+    fx = 0.9 * synth.blender_focal(W)
+    pose = synth.orbit_poses(7)[3]
+    m12 = pose[:3, :4].T.reshape(-1)
+    cam = orc.camera(W, H, fx, fx, m12)
+    st = _slot_tree(t)
+    bg = 1.0  # (against mid grey the colours, sigmoids around 0.5, would leave only alpha noisy)
+    opt = orc.default_options(spp=1, background_brightness=bg)
+    slots = np.full((n, H * W), -1, np.int64)
+    for k in range(n):
+        aux, _, _ = orc.render_frame(st, cam, opt, orc.rng(seed=977 + 7919 * (900 + k)), want_stats=False)
+        hit = aux[3].reshape(-1) == 1.0
+        dg = aux[:3].reshape(3, -1)[:, hit].astype(np.int64)
+        slots[k, hit] = dg[0] + 2048 * (dg[1] + 2048 * dg[2])
+    ys, xs = np.divmod(np.arange(H * W), W)
+    basis_fn = ref.basis(kind, t.extra, ref.pixel_vdir(W, H, fx, fx, m12, xs, ys))
+    D = t.data_dim
+    flat = t.data.reshape(-1, D)
+    got = np.zeros((4, H * W))
+    for px in range(H * W):
+        s, cnt = np.unique(slots[:, px], return_counts=True)
+        miss = cnt[s < 0].sum()
+        s, cnt = s[s >= 0], cnt[s >= 0]
+        rgb = np.zeros(3)
+        if s.size:
+            col = ref.shade_leaf(np.repeat(basis_fn[px:px + 1], s.size, 0), flat[s, :D - 1].astype(np.float32))
+            rgb = (col.astype(np.float64) * cnt[:, None]).sum(0)
+        got[:3, px] = (rgb + bg * miss) / n
+        got[3, px] = cnt.sum() / n
+    mean, var = E.expected_frame(E.Scene.of(t), pose, W, H, fx, fx, bg=bg)
+    assert (mean[3] > 0.05).sum() > 60
+    _check_against_model(got.reshape(4, H, W), mean, var, n, kind)
+    # the lobes matter: the model with every lobe but the first switched off is far from this one
+    flatc, _ = E.expected_frame(E.Scene.of(t), pose, W, H, fx, fx, bg=bg, basis_minmax=(0, 0))
+    assert np.abs(flatc[:3] - mean[:3]).max() > 0.05
+
+
+# ------------------------------------------------------------------ single rays: depth limit, backdrop, direction length
+def test_t_max_inside_a_medium_keeps_the_whole_leaf():
+    """One homogeneous medium, the ray along +x through two leaves (x in [0, 0.5) and [0.5, 1)), cut at 40 % of the
+    crossing, inside the first leaf.  rt_core.cuh:217,241: the cut ends the march, and the march tests it where a leaf is
+    ENTERED -- the first leaf counts whole (path 0.5, not 0.4), the second not at all."""
+    sigma, col = 3.0, (0.8, 0.3, 0.1)
+    vals = [[[(*col, sigma)] * 2] * 2] * 2
+    ht, data = _root_only(vals)
+    scene = E.Scene(np.zeros((1, 2, 2, 2), np.int32), data, np.ones(3), np.zeros(3), "RGBA")
+    o, d = (-1.0, 0.25, 0.25), (1.0, 0.0, 0.0)
+    whole = 1.0 - np.exp(-sigma * (0.5 - 1e-6 + 1e-4))
+    clipped, both = 1.0 - np.exp(-sigma * 0.4), 1.0 - np.exp(-sigma * (1.0 - 1e-6 + 1e-4))
+    assert min(whole - clipped, both - whole) > 4 * TOL  # (the three readings are far apart)
+    got = _trace_many(ht, o, d, N_RAYS, SPP, t_max=1.4)
+    assert abs(got[3] - whole) < TOL
+    assert np.allclose(got[:3], whole * np.array(col, np.float16).astype(np.float64), atol=TOL)
+    m, _ = E.expected_sample(scene, o, d, bg=0.0, t_max=1.4)
+    assert abs(m[3] - whole) < 1e-6
+    # a cut just behind the second leaf's entry keeps both; at the box's face, and in front of it, nothing is left
+    got = _trace_many(ht, o, d, N_RAYS, SPP, t_max=1.5 + 2e-4)
+    m, _ = E.expected_sample(scene, o, d, bg=0.0, t_max=1.5 + 2e-4)
+    assert abs(got[3] - both) < TOL and abs(m[3] - both) < 1e-6
+    for cut in (1.0, 0.5):
+        assert np.all(_trace_many(ht, o, d, 8, SPP, t_max=cut) == 0)
+        assert E.expected_sample(scene, o, d, bg=0.0, t_max=cut)[0][3] == 0
+    # t_max is a WORLD distance: the same medium in a world twice as long along x (scale 0.5) is cut at twice the distance,
+    # and holds twice the optical depth
+    ht2 = orc.HostTree(np.zeros((1, 2, 2, 2), np.int32), data, np.array([0.5, 1, 1], np.float32), np.zeros(3, np.float32), "RGBA")
+    got = _trace_many(ht2, o, d, N_RAYS, SPP, t_max=2.8)  # (_trace_many takes the origin in tree space: world x = -2)
+    assert abs(got[3] - (1.0 - np.exp(-sigma * 2 * (0.5 - 1e-6 + 1e-4)))) < TOL
+
+
+def _ray_means(ht, o, d, n_rep, spp, first, **kw):
+    """mean over n_rep independently seeded batches of test_rays.ray_oracle (the oracle's trace_ray + the composite)"""
+    from test_rays import ray_oracle
+    acc = np.zeros((o.shape[0], 4))
+    for k in range(n_rep):
+        acc += ray_oracle(ht, o, d, spp, rng_base=orc.rng(seed=977 + 7919 * (first + k)), **kw)
+    return acc / n_rep
+
+
+def test_rays_with_depth_limit_backdrop_and_any_direction_length():
+    """Camera rays of an anisotropic tree, each cut in the middle of its widest empty gap (so the result does not depend on
+    what a cut inside a leaf does), over a random backdrop per ray, the directions scaled by 0.01 and by 100: t_max is
+    measured along the UNIT direction, in world units, and a direction's length changes nothing."""
+    import rt_octree_amd as R
+    from helpers import FRAME_ANISO, cameras, reframe, reframe_pose
+    t0 = _thin_tree(depth=6)  # (a finer shell: half of the rays that meet the model cross a hollow between two walls)
+    t = reframe(t0, *FRAME_ANISO)
+    scene = E.Scene.of(t)
+    W, H = 32, 24
+    _, cam = cameras(W, H, reframe_pose(synth.orbit_poses(7)[3], t0, t), fx=0.9 * synth.blender_focal(W))
+    o, d = R.camera_rays(cam)
+    tm = np.array([E.t_max_in_widest_gap(scene, o[i], d[i], min_gap=0.02) or np.inf for i in range(o.shape[0])], np.float32)
+    assert np.isfinite(tm).sum() > 100  # (the thin shell model has a front and a back along most rays)
+    back = np.random.default_rng(11).uniform(0, 1, o.shape).astype(np.float32)
+    mean, var = E.expected_rays(scene, o, d, t_max=tm, background=back)
+    full, _ = E.expected_rays(scene, o, d, background=back)
+    assert (np.abs(full[:, 3] - mean[:, 3]) > 0.02).sum() > 100  # (the cut removes something)
+    ht = orc.HostTree(t.child, t.data, t.scale, t.offset, t.data_format)
+    for k, factor in enumerate((0.01, 100.0)):
+        got = _ray_means(ht, o, d * np.float32(factor), 64, 32, 1100 + 64 * k, t_max=tm, background=back)
+        _check_against_model(got, mean, var, 64 * 32, "rays, directions x %g" % factor)
 
 
 # ------------------------------------------------------------------ sample_dst

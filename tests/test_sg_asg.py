@@ -13,6 +13,7 @@ import pytest
 import orc
 import rt_octree_amd as R
 import sg_asg_ref as ref
+from expected_render import lobe_values
 from helpers import assert_bits_equal, oracle_threads
 from rt_octree_amd import _lib, synth
 
@@ -138,11 +139,7 @@ def test_restatement_agrees_with_float64_closed_form(kind):
     got = ref.lobe_basis(kind, lobes.astype(np.float32), d.astype(np.float32)).astype(np.float64)
     d = d.astype(np.float32).astype(np.float64)
     lob = lobes.astype(np.float32).astype(np.float64)
-    if kind == "SG":
-        want = np.exp(lob[:, 0] * (d @ lob[:, 1:4].T - 1.0)) / B
-    else:
-        S, dx, dy = d @ lob[:, 8:11].T, d @ lob[:, 2:5].T, d @ lob[:, 5:8].T
-        want = S * np.exp(-lob[:, 0] * dx * dx - lob[:, 1] * dy * dy) / B
+    want = lobe_values(kind, lob, d)  # (the float64 closed form of the rendering model, tests/expected_render.py)
     assert np.max(np.abs(got - want)) < 2e-6
 
 
