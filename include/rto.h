@@ -188,7 +188,7 @@ void rto_tree_free(rto_tree* t);
 
 /* ---- render context (RenderContext) ---- */
 /* RenderContext::update (render_context.hpp:70-91): aux [8][H][W] f32, noisy and final images
- * [H][W][4] f32, rng = pcg32(20230418) (:16).  offscreen is always true (headless path). */
+ * [H][W][4] f32, rng = pcg32(20230418) (:16).  offscreen is true until rto_ctx_set_layers hands the context a depth / colour layer. */
 int rto_ctx_create(int width, int height, int device, rto_ctx** out);
 /* The same with `frames` (1..128) frame slots: aux [frames][8][H][W], noisy / image [frames][H][W][4],
  * contiguous.  Single-frame entry points and accessors act on the slot chosen with
@@ -209,6 +209,37 @@ void rto_ctx_rng_seed(rto_ctx* c, uint64_t initstate, uint64_t initseq);
 void rto_ctx_rng_advance(rto_ctx* c, int64_t delta);
 void rto_ctx_rng_set(rto_ctx* c, uint64_t state, uint64_t inc);
 void rto_ctx_rng_get(const rto_ctx* c, uint64_t* state, uint64_t* inc);
+/* RenderContext::offscreen = false with surf_obj_depth / surf_obj (render_context.hpp; volrend.cu:146-153,162-184; the viewer's
+ * frame, cuda_renderer.cpp:96-156): every pixel's ray stops at a depth surface and the volume is composited over a colour surface
+ * instead of the constant background -- a PlenOctree shown together with rasterised geometry.
+ *   depth: device memory [frames][H][W] float32, the world distance along the pixel's unit ray direction (as rto_rays.t_max);
+ *          +inf = no limit; a value <= 0 or NaN = the pixel is not traced (its backdrop, alpha 0).
+ *   color: device memory [frames][H][W][4] float32, 16-byte aligned; only r, g, b are read.
+ * frames, H, W are the context's.  Frame slot k reads plane k: a single-frame launch the selected slot's plane, frame f of a
+ * batched launch plane f.  Either pointer may be NULL: no depth = 1e9f, no colour = options->background_brightness; both NULL
+ * restores the offscreen behaviour.  The pointers are BORROWED: they must stay valid until the launches that read them have
+ * finished, and live on the context's device.  They must not overlap the context's aux / noisy / image buffers -- the reference
+ * reads and overwrites surf_obj in place; here the batched path stores a pixel from another kernel than the one that would
+ * have to read it, so a binding keeps its mesh pass in a buffer of its own.
+ * Semantics: pixel (x, y) of a layered frame is, bit for bit, ray y * W + x of rto_launch_rays on that camera's rays (origin =
+ * the camera centre, direction = M xyz) with t_max = its depth, background = its colour's rgb, first_ray = 0 and the frame's RNG
+ * base (batch frame f: ctx.rng advanced by rng_jumps[f] * 2^32) -- (r, g, b, alpha).  The outputs are the reference's
+ * (volrend.cu:186-212): aux planes 0..3 those four values, planes 4..7 their squares, the noisy / final image (r, g, b, 1); a
+ * lean level-1 launch stores (r, g, b, alpha).
+ * Affects rto_launch_renderer and rto_launch_renderer_batch only (all kernels; empty-space culling stays on: a tile no culling
+ * cell projects into meets no density whatever the depth, its pixels are their backdrop).  rto_launch_rays ignores it.
+ * The layered batched kernels exist for the default tuning: the A/B part of the tuning key "refill" (100 * waves/SIMD +
+ * threshold) is ignored by a layered launch; its tiles-per-dequeue part and every other key apply.
+ * The tile marks promise "an unmarked tile's pixels are the constant background".  With a depth layer only that holds: lean
+ * level 2, rto_ctx_tile_marks and rto_denoise's culled routes work unchanged.  With a colour layer it does not: the launch still
+ * culls its marching, but rto_ctx_tile_marks returns RTO_E_INVALID after it, rto_denoise takes its plain kernels, and a lean
+ * level-2 launch returns RTO_E_UNSUPPORTED.
+ * RTO_E_INVALID: color not 16-byte aligned, a layer that overlaps the context's buffers or is not memory of the context's device
+ * (the context keeps the layers it had).  Launches return RTO_E_UNSUPPORTED for layers combined with rto_ctx_enable_stats or
+ * with a tree loaded with RTO_TREE_QUANT_DIRECT.  enable_probe stays RTO_E_UNSUPPORTED. */
+int rto_ctx_set_layers(rto_ctx* c, const float* depth, const float* color);
+/* the layers the context holds (NULL: none); either out pointer may be NULL */
+int rto_ctx_layers(const rto_ctx* c, const float** depth, const float** color);
 /* choose the traversal kernel (RTO_KERNEL_*); default AUTO */
 int rto_ctx_set_kernel(rto_ctx* c, int kernel);
 /* Performance knobs; never change results.  key: "strip_rows" (single-frame kernel: tile rows per XCD
@@ -287,8 +318,8 @@ int rto_wide_image_probe(const int32_t* child, const uint16_t* sigma_bits, int64
                          int64_t* out_wide_nodes);
 
 /* ---- the operator ---- */
-/* launch_renderer(tree, cam, options, ctx, stream, offscreen=true) (volrend.cu:236-285).
- * Asynchronous on `stream`.  Writes ctx aux + (options->denoise ? noisy : image).
+/* launch_renderer(tree, cam, options, ctx, stream, offscreen) (volrend.cu:236-285); offscreen = false is a context with
+ * layers (rto_ctx_set_layers).  Asynchronous on `stream`.  Writes ctx aux + (options->denoise ? noisy : image).
  * cam->width/height must equal the ctx size. */
 int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_options* options,
                         rto_ctx* ctx, void* stream);

@@ -96,6 +96,8 @@ SYMBOLS = {
     "rto_ctx_frames_are_lean": (C.c_int, [_P, C.c_int, C.c_int]),
     "rto_ctx_frames_lean_level": (C.c_int, [_P, C.c_int, C.c_int]),
     "rto_ctx_queue_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rto_ctx_set_layers": (C.c_int, [_P, _P, _P]),
+    "rto_ctx_layers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "rto_ctx_tile_marks": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "rto_ctx_kernel_timing": (C.c_int, [_P, C.c_int]),
     "rto_ctx_kernel_timing_read": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -374,6 +374,45 @@ RTO_DEV void write_pixel(const FrameOut& fo, int64_t SIZE, int idx, float bg, fl
     reinterpret_cast<float4*>(fo.image)[idx] = make_float4(out[0], out[1], out[2], 1.0f);
 }
 
+// ---- the layers of rto_ctx_set_layers (RenderContext::offscreen = false: surf_obj_depth / surf_obj, volrend.cu:146-153,162-184)
+// backdrop of pixel i (an index into the launch's colour planes): its rgb, or the options' brightness without a colour layer
+RTO_DEV void layer_backdrop(const LayerDev& layers, uint32_t i, float bg_default, float* bg) {
+    bg[0] = bg[1] = bg[2] = bg_default;
+    if (layers.color) {
+        const float4 c = layers.color[i];
+        bg[0] = c.x;
+        bg[1] = c.y;
+        bg[2] = c.z;
+    }
+}
+
+// ray_from_batch's verdict on a pixel's ray after ray_setup (tree-space dir / cen) with the depth tmax_bg: false = not traced,
+// the pixel is its backdrop with alpha 0 (a depth that is not > 0, NaN included; a camera that yields no finite ray)
+RTO_DEV bool ray_is_live(float tmax_bg, const float* dir, const float* cen) {
+    bool ok = tmax_bg > 0.f && (dir[0] != 0.f || dir[1] != 0.f || dir[2] != 0.f);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ok = ok && __builtin_isfinite(dir[c]) && __builtin_isfinite(cen[c]);
+    return ok;
+}
+
+// write_pixel over a per-pixel backdrop (write_ray's composite: out += bg * (1 - alpha) per channel), same outputs
+RTO_DEV void write_pixel_over(const FrameOut& fo, int64_t SIZE, int idx, const float* bg, float* out) {
+    const float nalpha = 1.f - out[3];
+    out[0] += bg[0] * nalpha;
+    out[1] += bg[1] * nalpha;
+    out[2] += bg[2] * nalpha;
+    float* a = fo.aux + idx;
+    a[0] = out[0];
+    a[SIZE] = out[1];
+    a[2 * SIZE] = out[2];
+    a[3 * SIZE] = out[3];
+    a[4 * SIZE] = out[0] * out[0];
+    a[5 * SIZE] = out[1] * out[1];
+    a[6 * SIZE] = out[2] * out[2];
+    a[7 * SIZE] = out[3] * out[3];
+    reinterpret_cast<float4*>(fo.image)[idx] = make_float4(out[0], out[1], out[2], 1.0f);
+}
+
 // ------------------------------------------------------------------ generic kernel (any N)
 
 // n3tree_query.hpp:13-48
@@ -414,6 +453,15 @@ __global__ void __launch_bounds__(256) render_rays_generic(const TreeDev tree, c
 #define RTO_GENERIC_RAYS 1
 #include "rto_render_generic.inc"
 #undef RTO_GENERIC_RAYS
+}
+
+// rto_launch_renderer over the context's layers (rto_ctx_set_layers) on any tree the fast kernel does not take and RTO_KERNEL_GENERIC
+template <int SPP>
+__global__ void __launch_bounds__(256) render_generic_layers(const TreeDev tree, const CamDev cam, const OptDev opt, const Pcg32 rng_base,
+                                                              const FrameOut fo, const LayerDev layers) {
+#define RTO_GENERIC_LAYERS 1
+#include "rto_render_generic.inc"
+#undef RTO_GENERIC_LAYERS
 }
 
 // ------------------------------------------------------------------ traversal image
@@ -710,6 +758,19 @@ __global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_rays(
 #define RTO_FAST_RAYS 1
 #include "rto_render_fast.inc"
 #undef RTO_FAST_RAYS
+}
+
+// rto_launch_renderer over the context's layers (rto_ctx_set_layers) on an N == 2 tree: the same body, each pixel's ray stopped at
+// its depth and composited over its colour; the tiles culled by fo.cull_marks get their backdrop.  No counting instantiation
+// (layers and rto_ctx_enable_stats are refused together).
+template <int SPP, bool WIDE, int STACK, int LOBES>
+__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_layers(const TreeDev tree, const CamDev cam, const OptDev opt,
+                                                           const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
+                                                           const TileMap tm, const FrameOut fo, const LayerDev layers) {
+    constexpr bool STATS = false;
+#define RTO_FAST_LAYERS 1
+#include "rto_render_fast.inc"
+#undef RTO_FAST_LAYERS
 }
 
 // ------------------------------------------------------------------ persistent kernel (N == 2)
@@ -1080,368 +1141,18 @@ template <int SPP, int REFILL, int WPS, bool WIDE, int STACK>
 __global__ void __launch_bounds__(256, WPS) render_persist(const TreeDev tree, const OptDev opt, const FrameBatch fb,
                                                        unsigned long long* __restrict__ queue,
                                                        uint32_t* __restrict__ hits, const uint32_t chunk) {
-    // queue[8 + 8k]: next ray of queue k's list (zeroed on the stream before the launch)
-    // LDS: [max_depth+1-top_levels][256] ancestor stack | [SPP+1][256] sorted thresholds | frame table
-    extern __shared__ uint32_t s_mem[];
-    const int tid = threadIdx.x;
-    uint32_t* stack = s_mem + tid;  // [level - G][256]
-    // levels top_levels.. only.  STACK == 1 (ancestor stack in a register): two rows all the same -- they hold a ray's two
-    // hand-off offsets (rs.hoff, rs.hnext: written at the set-up, read at the flush, dead weight in the march loop whose
-    // 64-register budget the restart's constants need)
-    const int stack_levels = STACK == 1 ? 2 : tree.max_depth + 1 - tree.top_levels;
-    float* s_dst = reinterpret_cast<float*>(s_mem + (size_t)stack_levels * 256) + tid;
-    // the cameras of the batch: {fx, fy, transform[12]} per frame = the head of a FrameDesc (56 of its 96 bytes: at 100 frames
-    // per launch the table then leaves room for 8 workgroups per CU)
-    float* s_cams = reinterpret_cast<float*>(s_mem + (size_t)(stack_levels + SPP + 1) * 256);
-    __shared__ int s_qstart[kMaxQueues + 1];
-    __shared__ uint32_t s_qcount[kMaxQueues];  // live tile slots of each queue (queue_scan_kernel)
-    static_assert(offsetof(FrameDesc, transform) == 8 && kCamFloats == 14, "s_cams copies the first 14 floats of a FrameDesc");
-    for (int i = tid; i < fb.n * kCamFloats; i += 256) {  // device memory -> LDS
-        const int f = i / kCamFloats;
-        s_cams[i] = reinterpret_cast<const float*>(fb.f + f)[i - f * kCamFloats];
-    }
-#pragma unroll
-    for (int k = 0; k <= kMaxQueues; ++k)
-        if (tid == 64 + k) s_qstart[k] = fb.qstart[k];
-#pragma unroll
-    for (int k = 0; k < kMaxQueues; ++k)
-        if (tid == 128 + k) s_qcount[k] = k < fb.n_queues ? fb.qcount[k] : 0u;
-    __syncthreads();
+#include "rto_render_persist.inc"
+}
 
-    const int W = fb.width, H = fb.height;
-    const uint32_t SIZE = (uint32_t)W * (uint32_t)H;
-    const uint32_t hstride = hit_stride(SIZE);  // distance between consecutive entries of one pixel (behind the first)
-    // the queue this wave draws from first: the one of the XCD it runs on (HW_REG_XCC_ID bits 3:0)
-    const uint32_t n_queues = (uint32_t)fb.n_queues;
-    uint32_t cur_q = n_queues > 1 ? ((uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) % n_queues) : 0u;
-    uint32_t q_tried = 0;            // queues found empty so far (wave-uniform)
-    uint32_t res_off = 0;            // list offset of the queue the reservoir was drawn from (wave-uniform)
-
-    // Loop-invariant scalars pinned in SGPRs: hipcc otherwise re-loads them from the kernarg segment inside the descent loop (an s_load +
-    // lgkmcnt(0) round trip per level).
-    typedef const __attribute__((address_space(1))) uint32_t* gptr_t;  // keep global_load (not flat_load)
-    // WIDE: the two-level image and its top grid (rto_abi.cpp build_wide_image) instead of the one-level ones
-    const uint32_t* nodew_p = WIDE ? tree.widew : tree.nodew;
-    const uint2* topgrid_p = tree.topgrid;  // (WIDE: unused -- the grid cells are the first entries of the two-level image)
-    const uint32_t* __restrict__ qlist = fb.qlist;
-    float step_size = opt.step_size, sigma_thresh = opt.sigma_thresh;
-    asm volatile("" : "+s"(nodew_p), "+s"(topgrid_p), "+s"(step_size), "+s"(sigma_thresh));
-    const gptr_t nodew = (gptr_t)nodew_p;
-    typedef unsigned int __attribute__((ext_vector_type(2))) u32x2;
-    typedef const __attribute__((address_space(1))) u32x2* gptr2_t;
-    const gptr2_t topgrid = (gptr2_t)topgrid_p;
-    const int G = tree.top_levels;  // grid bits per axis; the LDS stack holds node levels G.. (entry 0 = level G)
-    if (G == 0) stack[0] = 0u;      // no top grid: level 0 is the root
-    // indexed by node level (only ever with levels >= G); WIDE: by the PAIR of levels (G + 2p, G + 2p + 1) a wide node spans
-    uint32_t* const stack_g = WIDE ? stack : stack - G * 256;
-
-#ifdef RTO_DBG_COUNTERS
-    // per-branch occupancy of the march loop (tools/dbg_counters.py): for each branch, how many wave-level executions and
-    // how many lanes took part.  0 iteration (any active lane), 1 descend, 2 leaf (march step), 3 sigma > thresh,
-    // 4 hit (threshold crossed), 5 restart (ray goes on), 6 ray set-up (refill round), 7 grid lookups
-    unsigned dbg_w[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dbg_l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RTO_DBG_AT(i)                                                                                          \
-    {                                                                                                          \
-        const unsigned long long m_ = __builtin_amdgcn_ballot_w64(true);                                      \
-        ++dbg_l[i];                                                                                            \
-        if ((tid & 63) == __ffsll((long long)m_) - 1) ++dbg_w[i];                                              \
-    }
-#else
-#define RTO_DBG_AT(i) {}
-#endif
-    // Two pairs of levels below the grid at most (a tree of depth <= G + 4: the NeRF-synthetic PlenOctrees' 9-10 levels) and the
-    // ancestor "stack" is two registers: the restart node then comes from a select, not from an LDS read on the path of
-    // every iteration (-2 % in one box, profiles/r4_r_ab_regstack.txt).  Deeper trees keep the LDS rows.  (wave-uniform)
-    uint32_t stk0 = 0u, stk1 = 0u;
-    static_assert(WIDE || STACK == 0, "the register stack is for the two-level image");
-    constexpr bool regstack = STACK == 1, kStackInRegs = regstack;
-    uint32_t g_vgpr = (uint32_t)tree.top_levels;  // (rto_march_leaf.inc: the restart's `wb` select)
-    asm volatile("" : "+v"(g_vgpr));
-    // (the restart's selects, rto_march_leaf.inc: bit offsets of the grid and of the first pair below it, in VGPRs; the
-    //  coordinate difference from which a ray is back at the grid, in an SGPR)
-    uint32_t woff_grid_v = 24u - (uint32_t)tree.top_levels, woff_pair0_v = 22u - (uint32_t)tree.top_levels;
-    uint32_t tgrid = 1u << (24 - tree.top_levels);
-    asm volatile("" : "+v"(woff_grid_v), "+v"(woff_pair0_v), "+s"(tgrid));
-    constexpr bool kOffsInLds = STACK == 1;
-    RayState rs;
-    // a lane marches a ray while rs.t < rs.tmax: that comparison IS the lane's state (an ended ray has t >= tmax or
-    // tmax = -1), so the wave-level count of marching lanes is the ballot of one v_cmp instead of a loop-carried flag
-    rs.t = 0.f;
-    rs.tmax = -1.f;
-    rs.nh = 0;
-    bool drained = false;   // queue exhausted (wave-uniform)
-    const uint32_t kChunk = chunk;           // rays per global dequeue (a multiple of the 64-ray tile)
-    uint32_t res_next = 0, res_end = 0;      // the wave's private reservoir (wave-uniform)
-
-    // Two nested loops (round 3): the OUTER one refills the wave, the INNER one marches until REFILL lanes are idle again.
-    // The inner loop's back edge is one compare + population count + branch; with a single loop that re-decided "refill?"
-    // at its top the compiler spent 14 scalar instructions per iteration on that decision -- and scalar instructions come
-    // out of the same issue budget as the vector ones (profiles/r3_valu_calibration.json).
-    for (;;) {
-        {
-            for (;;) {
-                // (a finished ray needs no retiring: the stale threshold behind its last hit entry ends the list)
-                if (drained) break;
-                // ---- refill: hand the next queue entries to the idle lanes (ballot + prefix sum)
-                const bool idle = !(rs.t < rs.tmax);
-                const unsigned long long need = __builtin_amdgcn_ballot_w64(idle);
-                const int n_need = __popcll(need);
-                if (n_need < REFILL) break;
-                // The wave draws rays from a private reservoir [res_next, res_end) and tops it up from
-                // the global queue kChunk rays (kChunk/64 tiles) at a time: one device-scope atomic per
-                // kChunk rays instead of one per refill (a single counter sustains only ~90 dequeues/us).
-                if (res_next == res_end) {
-                    for (;;) {  // own queue first, then the others in turn (wave-uniform)
-                        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane(s_qstart[cur_q]);
-                        const uint32_t qtotal = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_qcount[cur_q]) * 64u;  // live rays
-                        unsigned long long base = 0;
-                        if ((tid & 63) == 0) base = atomicAdd(queue + 8 + 8 * cur_q, (unsigned long long)kChunk);
-                        const uint32_t base32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-                        if (base32 < qtotal) {  // a counter never exceeds qtotal + kChunk * waves: fits 32 bits
-                            res_next = base32;
-                            res_end = base32 + kChunk < qtotal ? base32 + kChunk : qtotal;
-                            res_off = t0 * (uint32_t)fb.n;
-                            break;
-                        }
-                        if (++q_tried >= n_queues) {
-                            drained = true;
-                            break;
-                        }
-                        cur_q = cur_q + 1 == n_queues ? 0u : cur_q + 1;
-                    }
-                    if (drained) break;
-                }
-                const uint32_t take = (uint32_t)n_need < res_end - res_next ? (uint32_t)n_need : res_end - res_next;
-                const uint32_t first = res_next;
-                res_next += take;
-                if (idle && rs.nh) {  // the ended ray's hit list leaves in one go
-                    if constexpr (kOffsInLds) {
-                        rs.hoff = stack[0];
-                        rs.hnext = stack[256];
-                    }
-                    flush_hits<SPP, WIDE>(rs, tree, hits, s_dst, hstride, !tree.rec_by_entry);
-                }
-                if (idle) {
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-                    const uint32_t r = first + rank;
-                    // ray r of the queue: lane (r & 63) of the live tile slot qlist[.. + (r >> 6)] = {frame, tile y, tile x}
-                    // (the lists hold marked tiles only: every ray handed out can meet density or at least crosses near it)
-                    const uint32_t entry = rank < take ? qlist[res_off + (r >> 6)] : 0u;
-                    const int frame = (int)(entry >> 20);
-                    const int x = (int)(entry & 1023u) * 8 + (int)(r & 7u);  // (Z-order inside the tile was tried: no fewer L1 accesses)
-                    const int y = (int)((entry >> 10) & 1023u) * 8 + (int)((r >> 3) & 7u);
-                    if (rank < take && x < W && y < H) {
-                        RTO_DBG_AT(6)
-                        const float* fd = s_cams + frame * kCamFloats;
-                        // (round 5: what the set-up derives from launch constants -- 0.5 W, bbox +- 1e-6 in double, the NDC factors --
-                        //  is derived HERE: left alone the compiler hoists those values out of the kernel's loops into ~12 VGPRs and
-                        //  spills them; the empty asm statements make the inputs opaque.  This was the kernel's whole private segment.)
-                        int Wl = W, Hl = H;
-                        OptDev o2 = opt;
-                        TreeDev t2 = tree;
-                        asm volatile("" : "+s"(Wl), "+s"(Hl));
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) asm volatile("" : "+s"(o2.render_bbox[i]));
-                        asm volatile("" : "+s"(t2.ndc_width), "+s"(t2.ndc_height), "+s"(t2.ndc_focal));
-                        CamDev cam;
-                        cam.width = Wl;
-                        cam.height = Hl;
-                        cam.fx = fd[0];
-                        cam.fy = fd[1];
-#pragma unroll
-                        for (int i = 0; i < 12; ++i) cam.transform[i] = fd[2 + i];
-                        float vdir[3];
-                        ray_setup(x, y, cam, t2, rs.dir, vdir, rs.cen);
-                        float tmin;
-                        {   // where this pixel's next hit entry goes (hoff) and the one after it (hnext): hit_index
-                            const uint32_t fbase = (uint32_t)frame * (uint32_t)SPP * SIZE, pixel = (uint32_t)(y * W + x);
-                            rs.hoff = fbase + hit_index<SPP>(pixel, 0u, SIZE);
-                            rs.hnext = fbase + hit_index<SPP>(pixel, SPP > 1 ? 1u : 0u, SIZE);
-                        }
-                        if (ray_enter(t2, o2, rs.dir, rs.cen, 1e9f, rs.invdir, rs.delta_scale, tmin, rs.tmax)) {
-                            // sorted thresholds of this pixel (sample_kernel left them in the hand-off
-                            // buffer, where the ray's hit list will overwrite them)
-                            rs.cur = __uint_as_float(hits[rs.hoff]);
-                            const uint32_t* tp = hits + rs.hnext;
-                            if constexpr (kOffsInLds) {  // (parked until the ray's flush)
-                                stack[0] = rs.hoff;
-                                stack[256] = rs.hnext;
-                            }
-#pragma unroll
-                            for (int i = 1; i < SPP; ++i) s_dst[i * 256] = __uint_as_float(tp[(uint32_t)(i - 1) * hstride]);
-                            s_dst[SPP * 256] = 3.402823466e+38f;
-                            rs.spp = 0;
-                            rs.src = 0;
-                            rs.t = tmin;
-                            float k24 = kPos24;  // (an SGPR operand: as a literal the compiler parks it in a VGPR pair across the kernel)
-                            asm volatile("" : "+s"(k24));
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) {  // (from here on the ray's origin and direction are the scaled ones: kPos24)
-                                rs.cen[i] *= k24;
-                                rs.dir[i] *= k24;
-                            }
-                            rs.cxy.x = rs.cen[0];
-                            rs.cxy.y = rs.cen[1];
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) rs.exit_add[i] = rs.invdir[i] > 0.f ? rs.invdir[i] : 0.f;
-                            rs.pix = rs.piy = rs.piz = 0;
-                            rs.prev_lvl = 0;
-                            {  // locate the first position: fixed-point coordinates + first node
-#pragma unroll
-                                for (int i = 0; i < 3; ++i) rs.pos[i] = clamp_unit24(rs.cen[i] + rs.t * rs.dir[i]);
-                                rs.pix = (uint32_t)rs.pos[0];
-                                rs.piy = (uint32_t)rs.pos[1];
-                                rs.piz = (uint32_t)rs.pos[2];
-                                rs.node = WIDE ? 0u : (G > 0 ? kGridNext : 0u);
-                                rs.woff = 24u - (uint32_t)G;
-                                rs.wb = (uint32_t)G;
-                            }
-                        } else {
-                            rs.tmax = -1.f;  // missed the box (ray_enter wrote a tmax that the stale t might undercut)
-                        }
-                    }
-                }
-            }
-        }
-        bool active = rs.t < rs.tmax;
-        if (__builtin_amdgcn_ballot_w64(active) == 0ULL) {
-            if (drained) break;
-            continue;  // (every ray of the round missed the volume)
-        }
-        // once the queues are empty there is nothing to refill with: march until the last ray ends
-        const int exit_at = drained ? 0 : 64 - REFILL;
-        int n_active;
-        do {
-        {
-            // ---- one node visit for every active lane
-            if (active) {
-                RTO_DBG_AT(0)
-                uint32_t slot, w;
-                if constexpr (WIDE) {
-                    // Round 4: ONE array holds the top grid and the two-level ("wide") nodes below it (rto_abi.cpp
-                    // build_wide_image), so a node visit is ONE uniform load: entry = ((node << b | x bits) << b | y bits) << b |
-                    // z bits, b bits per axis from bit rs.woff on -- (node, b, woff) = (0, G, 24 - G) at the grid,
-                    // (node number, 2, 22 - G - 2 p) at the wide node of the levels (G + 2p, G + 2p + 1).  v_bfe_u32 and
-                    // v_lshl_or_b32 take the per-lane widths: no grid / node case split, no second address, no branch pair
-                    // around two loads (the one-level walk below spends 19 VALU + 7 SALU where this spends 10 VALU).
-                    const uint32_t b = rs.wb;
-                    slot = (rs.node << b) | __builtin_amdgcn_ubfe(rs.pix, rs.woff, b);
-                    slot = (slot << b) | __builtin_amdgcn_ubfe(rs.piy, rs.woff, b);
-                    slot = (slot << b) | __builtin_amdgcn_ubfe(rs.piz, rs.woff, b);
-                    if (rs.node == 0u) { RTO_DBG_AT(7) }
-#ifdef RTO_STUB_LOADS
-                    {   // calibration build (tools/calibrate_valu.sh): the gather replaced by a hash of its address
-                        const uint32_t hsh = slot * 0x9E3779B1u;
-                        const uint32_t sg = (hsh & 0x600u) ? 0u : 0x4D00u;
-                        if (rs.node == 0u) {
-                            const uint32_t glv = 2u + (hsh >> 30);
-                            w = (glv == 5u && (hsh & 0x100u)) ? ((hsh >> 8) & 0xffffu) | 1u : (kLeafTag | glv << kWideLevelShift | sg);
-                        } else {  // two pairs below the grid (levels G .. G + 3), leaves at either level of a pair
-                            const uint32_t lv = 22u - rs.woff + ((hsh >> 27) & 1u);
-                            w = (rs.woff == 22u - (uint32_t)G && (hsh >> 29) < 5u) ? ((hsh >> 8) & 0xffffu) | 1u : (kLeafTag | lv << kWideLevelShift | sg);
-                        }
-                    }
-#else
-                    // (through the L1: non-temporal loads cost 15-50 %.  The byte offset as a 32-bit value -- the image has < 2^29
-                    //  entries -- lets the load take its base from SGPRs and one VGPR of offset: no 64-bit address pair, no register
-                    //  pinned to zero for its high half)
-                    w = *(gptr_t)((const __attribute__((address_space(1))) char*)nodew + (uint32_t)(slot << 2));
-#endif
-                    if ((int32_t)w >= -(1 << 30)) {  // internal: two levels down (from the grid: into the level-G node)
-                        RTO_DBG_AT(1)
-                        rs.node = w;
-                        if (regstack) {
-                            // two pairs at most: the ancestor "stack" is ONE register, the node of the first pair.  (The second
-                            // pair's node needs none: a restart inside the second pair happens at a leaf of that very node --
-                            // the ray stays in rs.node.)
-                            const bool first = rs.woff == 24u - (uint32_t)G;
-                            stk0 = first ? w : stk0;
-                        } else
-                            stack[(((24u - (uint32_t)G) - rs.woff) >> 1) * 256u] = w;  // row p + 1 of the pair it spans (grid: row 0)
-                        rs.woff -= 2u;
-                        rs.wb = 2u;
-                    }
-                }
-                if constexpr (!WIDE) {
-                const bool grid = rs.node == kGridNext;
-                const uint32_t gs = 24u - (uint32_t)G;
-                const uint32_t key = (((rs.pix >> gs) << G | (rs.piy >> gs)) << G) | (rs.piz >> gs);
-                const uint32_t sh = 23u - (uint32_t)rs.prev_lvl;
-                slot = (rs.node << 1) | __builtin_amdgcn_ubfe(rs.pix, sh, 1u);  // node * 8 + child digit,
-                slot = (slot << 1) | __builtin_amdgcn_ubfe(rs.piy, sh, 1u);       // three v_lshl_or
-                slot = (slot << 1) | __builtin_amdgcn_ubfe(rs.piz, sh, 1u);
-                // Both addresses exist in registers before either load is issued.  Left to itself the compiler sinks each
-                // address computation into its branch, and when a temporary of the second branch lands in the register the
-                // first branch's load is still writing, it has to put an s_waitcnt vmcnt(0) between the two loads -- the
-                // iteration then pays two memory latencies back to back (measured: 8.16 instead of 7.16 ms per 100
-                // frames from a one-instruction difference elsewhere in the kernel that renumbered the registers).
-                gptr_t pn = nodew + slot;
-                gptr2_t pg = topgrid + key;
-                asm volatile("" : "+v"(pn), "+v"(pg));
-#ifdef RTO_STUB_LOADS
-                // Calibration build only (tools/calibrate_valu.sh): both gathers replaced by a hash of their address -- a
-                // procedural stand-in for the tree with the same loop, the same divergence and no memory latency, to measure
-                // what the loop body sustains in VALU instructions per clock at 1..8 waves per SIMD.  Never shipped.
-                if (grid) {
-                    const uint32_t hsh = key * 0x9E3779B1u;
-                    const uint32_t glv = 2u + (hsh >> 30);
-                    slot = (key << 3) & kGridSlotMask;
-                    const uint32_t sg = (hsh & 0x600u) ? 0u : 0x4D00u;
-                    rs.prev_lvl = (int)glv;
-                    rs.node = slot >> 3;
-                    w = (glv == 5u && (hsh & 0x100u)) ? 1u : (kLeafTag | sg);
-                } else {
-                    const uint32_t hsh = slot * 0x9E3779B1u;
-                    const uint32_t sg = (hsh & 0x600u) ? 0u : 0x4D00u;
-                    w = (rs.prev_lvl < 9 && (hsh >> 29) < 3u) ? 1u : (kLeafTag | sg);
-                }
-#else
-                if (grid) {  // the iteration's one load: 8 bytes of the top grid ...
-                    const u32x2 e = *pg;  // (through the L1 as well: non-temporal costs 15 %)
-                    slot = e.x & kGridSlotMask;
-                    rs.prev_lvl = (int)(e.x >> kGridSlotBits);
-                    rs.node = slot >> 3;
-                    w = e.y;
-                } else {  // ... or 4 bytes of the traversal image
-                    w = *pn;  // (through the L1: a non-temporal load here costs 50 %)
-                }
-#endif
-                if (grid) { RTO_DBG_AT(7) }
-                if ((int32_t)w >= -(1 << 30)) {  // internal: one level down
-                    RTO_DBG_AT(1)
-                    rs.node += w;
-                    ++rs.prev_lvl;
-                    stack_g[rs.prev_lvl * 256] = rs.node;
-                }
-                }  // (!WIDE)
-                if ((int32_t)w < -(1 << 30)) {  // leaf: the march step (rt_core.cuh:241-270)
-#include "rto_march_leaf.inc"
-                }
-            }
-        }
-            active = rs.t < rs.tmax;
-            {
-                const unsigned long long am = __builtin_amdgcn_ballot_w64(active);
-                asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n_active) : "s"(am) : "scc");
-            }
-        } while (n_active > exit_at);
-    }
-    if (rs.nh) {  // rays that ended after the last refill round
-        if constexpr (kOffsInLds) {
-            rs.hoff = stack[0];
-            rs.hnext = stack[256];
-        }
-        flush_hits<SPP, WIDE>(rs, tree, hits, s_dst, hstride, !tree.rec_by_entry);
-    }
-#ifdef RTO_DBG_COUNTERS
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {  // queue words 1..7 / 9..15 are padding of the queue counters: wave counts, lane counts
-        const int wi = i == 0 ? 16 + 1 : i, li = i == 0 ? 16 + 2 : 8 + i;
-        if (dbg_w[i]) atomicAdd(queue + wi, (unsigned long long)dbg_w[i]);
-        if (dbg_l[i]) atomicAdd(queue + li, (unsigned long long)dbg_l[i]);
-    }
-#endif
+// the batched traversal over the context's depth layer (rto_ctx_set_layers): the same body, the ray set-up reads the depth of its
+// tile's pixels.  Instantiated for the default tuning only (REFILL 32, RTO_WPS_DEFAULT waves per SIMD).
+template <int SPP, int REFILL, int WPS, bool WIDE, int STACK>
+__global__ void __launch_bounds__(256, WPS) render_persist_layers(const TreeDev tree, const OptDev opt, const FrameBatch fb,
+                                                              unsigned long long* __restrict__ queue,
+                                                              uint32_t* __restrict__ hits, const uint32_t chunk, const LayerDev layers) {
+#define RTO_PERSIST_LAYERS 1
+#include "rto_render_persist.inc"
+#undef RTO_PERSIST_LAYERS
 }
 
 
@@ -1584,233 +1295,17 @@ __host__ __device__ constexpr uint32_t shade_blocks_per_band(int W, int block_px
 template <int SPP, int P, int MODE, int LOBES = 0>
 __global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kernel(const TreeDev tree, const OptDev opt, const FrameBatch fb,
                                                                               const uint32_t* __restrict__ hits0) {
-    __shared__ uint32_t s_h[kShadeWaves][kShadeCap];       // packed hit entry
-    __shared__ uint16_t s_q[kShadeWaves][kShadeCap];       // its pixel, relative to the wave's first pixel
-    __shared__ float s_c[kShadeWaves][3 * kShadeCap];      // its contribution, [channel][entry]
-    const int W = fb.width, H = fb.height;
-    const int64_t SIZE = (int64_t)W * H;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#ifdef RTO_DBG_COUNTERS
-    unsigned long long ph[8];
-    for (int i = 0; i < 8; ++i) ph[i] = 0;
-    RTO_SHADE_STAMP(0)
-#endif
-    // Workgroup -> (pixel block, frame), XCD-aware: workgroups go round-robin over the 8 XCDs, so id & 7 picks the XCD, and the L2 is
-    // per XCD.  Rounds 2-5 put the same 128-pixel block of ALL frames of the batch on one XCD, frame after frame, hoping that
-    // neighbouring poses hit the same leaves there; the counters never agreed (L2 hit 15 %, as with frame-major order): an orbiting
-    // camera moves a leaf SIDEWAYS by ten or twenty pixels per frame -- out of its block after a few frames, but not out of its rows.
-    // Round 6: BANDS of 8 rows.  Band b of all frames runs on XCD b & 7, frame after frame, a band's blocks side by side: L2 hit
-    // 0.15 -> 0.28, FETCH 4.25 -> 3.56 GB per 100 C2 frames, 1.335 -> 1.298 ms (C4 6.75 -> 6.23, C5 0.985 -> 0.936); bands of 4 / 16 /
-    // 32 rows: 1.306 / 1.315 / 1.43 (profiles/r6_y_ab_shade_bands*.txt, r6_y_pmc_shade_bands.txt).  RTO_SHADE_BAND_ROWS=0: the old order.
-    const uint32_t bid = blockIdx.x, q = bid >> 3;
-#if RTO_SHADE_BAND_ROWS > 0
-    const uint32_t cpb = shade_blocks_per_band(W, 64 * kShadeWaves * P), per_band = cpb * (uint32_t)fb.n;
-    const uint32_t bi = q / per_band, rem = q - bi * per_band;
-    const uint32_t frame = rem / cpb;
-    const uint32_t pblock = (bi * 8u + (bid & 7u)) * cpb + (rem - frame * cpb);
-#else
-    const uint32_t frame = q % (uint32_t)fb.n;
-    const uint32_t pblock = (q / (uint32_t)fb.n) * 8u + (bid & 7u);
-#endif
-    const int64_t wave_px0 = ((int64_t)pblock * kShadeWaves + wv) * (64 * P);
-    if (wave_px0 >= SIZE) return;  // wave-uniform
-    const FrameDesc& fd = fb.f[frame];  // block-uniform index: scalar loads
-    // (the frame's hand-off lists: from the launch's base, not from the frame table -- a wave's first loads then depend on its
-    //  kernel arguments only; a shading wave spends a fifth of its life before its hit lists have arrived, profiles/r6_d_shade_phases.txt)
-    const RTO_GLOBAL uint32_t* const fhits = as_global(hits0) + (size_t)frame * (size_t)SPP * (size_t)SIZE;
+#include "rto_shade.inc"
+}
 
-    // ---- each lane: the hit lists of its P pixels (pixel p*64 + lane of the wave: coalesced)
-    uint32_t h[P][SPP];
-    uint32_t n[P];
-    uint32_t mine = 0, live_bits = 0;  // bit p: pixel p of this lane lies in a marked tile
-    // A pixel of a culled tile has no hit list (nobody wrote one: sample_kernel, render_persist): it is read off the tile
-    // marks, a few hundred cached words per frame, instead of 4 * SPP bytes per pixel of stale memory -- two thirds of the
-    // pixels of the bench scene.  (x, y) of the wave's first pixel by one wave-uniform division, the lanes' by carries.
-    const uint32_t* fmask = fb.tile_mask ? fb.tile_mask + (size_t)frame * fb.mask_words : nullptr;
-    const uint32_t keep_all = fmask ? fmask[fb.mask_words - 1] & 1u : 1u;
-    const int tiles_x = (W + 7) >> 3;
-    const int wy0 = (int)(wave_px0 / W), wx0 = (int)(wave_px0 - (int64_t)wy0 * W);
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int64_t idx = wave_px0 + p * 64 + lane;
-        n[p] = 0;
-        bool live = idx < SIZE;
-        if (live && fmask) {  // (the mark word is requested before the frame's keep-all flag is back: no dependent second trip)
-            int x = wx0 + p * 64 + lane, y = wy0;
-            while (x >= W) {
-                x -= W;
-                ++y;
-            }
-            const uint32_t t = (uint32_t)((y >> 3) * tiles_x + (x >> 3));
-            live = (((fmask[t >> 5] >> (t & 31u)) | keep_all) & 1u) != 0u;
-        }
-        live_bits |= live ? 1u << p : 0u;
-        if (live) {
-            bool open = true;
-            // the first entry from its dense plane, the run behind it (fetched eagerly: fetching the run only for a pixel whose
-            // first entry is valid saves 20 bytes per empty pixel and costs a dependent round trip per wave, 2.03 vs 1.95 ms)
-            uint32_t raw[SPP];
-            raw[0] = fhits[idx];
-            const RTO_GLOBAL uint32_t* hp = fhits + SIZE + idx * (SPP - 1);
-#pragma unroll
-            for (int i = 1; i < SPP; ++i) raw[i] = hp[i - 1];
-#pragma unroll
-            for (int i = 0; i < SPP; ++i) {
-                open = open && (raw[i] & kHitValid) != 0u;
-                h[p][i] = open ? raw[i] : 0u;
-                n[p] += open ? 1u : 0u;
-            }
-        }
-        mine += n[p];
-    }
-    // (sparse lean outputs: a wave whose pixels all lie in unmarked tiles -- two thirds of the bench scene's waves -- has nothing to
-    //  shade and nothing to store)
-    if (fb.lean == 2 && __builtin_amdgcn_ballot_w64(live_bits != 0u) == 0ULL) return;
-    // ---- wave exclusive prefix sum -> each pixel's range in the compacted list
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    const uint32_t total = __shfl(inc, 63, 64);
-    RTO_SHADE_STAMP(1)  // tile marks + hit lists are here (the prefix sum consumed them)
-    uint32_t start[P];
-    {
-        uint32_t sacc = inc - mine;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            start[p] = sacc;
-            sacc += n[p];
-        }
-    }
-    float out[P][4];
-#pragma unroll
-    for (int p = 0; p < P; ++p) out[p][0] = out[p][1] = out[p][2] = out[p][3] = 0.f;
-
-    CamDev cam;
-    cam.width = W;
-    cam.height = H;
-    cam.fx = fd.fx;
-    cam.fy = fd.fy;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) cam.transform[i] = fd.transform[i];
-
-    for (uint32_t w0 = 0; w0 < total; w0 += kShadeCap) {  // wave-uniform
-        // ---- pixel lanes publish the entries that fall into this window
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-#pragma unroll
-            for (int i = 0; i < SPP; ++i) {
-                const uint32_t pos = start[p] + i - w0;  // wraps to a huge value below the window
-                if ((uint32_t)i < n[p] && pos < (uint32_t)kShadeCap) {
-                    s_h[wv][pos] = h[p][i];
-                    s_q[wv][pos] = (uint16_t)(p * 64 + lane);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // ---- one entry per lane
-        RTO_SHADE_STAMP(2)  // (last window's) entries published
-        const uint32_t cnt_w = min(total - w0, (uint32_t)kShadeCap);
-        for (uint32_t j = lane; j < cnt_w; j += 64) {
-            const uint32_t he = s_h[wv][j];
-            // the entry's pixel = pixel s_q of the wave's run, which starts at (wx0, wy0): carries instead of a 64-bit division
-            // per entry (round 5: `idx % W`, `idx / W` on an int64 were ~150 of the ~690 instructions an entry cost)
-            int x = wx0 + (int)s_q[wv][j], y = wy0;
-            while (x >= W) {
-                x -= W;
-                ++y;
-            }
-            float dir[3], vdir[3], cen[3];
-            ray_setup(x, y, cam, tree, dir, vdir, cen);  // only vdir is needed (rt_core.cuh:278)
-            float basis_fn[RTO_BASIS_MAX_DEV];
-            // (view direction + basis once per hit PIXEL, parked in LDS, removes ~200 of these ~430 instructions per entry and was
-            //  built twice -- round 4 and round 6, tools/experiments/r6_shade_basis_table.patch -- and lost both times: 1.54 vs
-            //  1.48 ms on C2, 1.24 vs 1.02 on C5: this arithmetic runs while the entry's record is in flight and costs nothing)
-            if constexpr (LOBES != 0 && MODE > 0)  // SG / ASG tree, data_dim = MODE
-                ray_basis_lobes<LOBES, (MODE - 1) / 3>(tree, opt, vdir, basis_fn);
-            else if constexpr (MODE > 0)  // (the launcher picks MODE from the tree: SH, data_dim = MODE)
-                ray_basis_sh<(MODE - 1) / 3>(opt, vdir, basis_fn);
-            else if constexpr (MODE < 0)  // quantised SH tree, -MODE basis functions
-                ray_basis_sh<-MODE>(opt, vdir, basis_fn);
-            else
-                ray_basis<LOBES>(tree, opt, vdir, basis_fn);
-            float o[4];
-            leaf_contrib<MODE>(tree, hit_slot<SPP>(he), basis_fn, (float)hit_count<SPP>(he), o);
-            s_c[wv][j] = o[0];
-            s_c[wv][kShadeCap + j] = o[1];
-            s_c[wv][2 * kShadeCap + j] = o[2];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // ---- pixel lanes add their entries up, in hit order
-        RTO_SHADE_STAMP(3)  // (last window's) entries shaded
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-#pragma unroll
-            for (int i = 0; i < SPP; ++i) {
-                const uint32_t pos = start[p] + i - w0;
-                if ((uint32_t)i < n[p] && pos < (uint32_t)kShadeCap) {
-                    out[p][0] += s_c[wv][pos];
-                    out[p][1] += s_c[wv][kShadeCap + pos];
-                    out[p][2] += s_c[wv][2 * kShadeCap + pos];
-                    out[p][3] += (float)hit_count<SPP>(h[p][i]);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-
-    RTO_SHADE_STAMP(4)  // sums done
-    RTO_GLOBAL float* const g_aux = as_global(fd.aux);
-    typedef float f4_t __attribute__((ext_vector_type(4)));  // (HIP's float4 has no assignment across address spaces)
-    RTO_GLOBAL f4_t* const g_image = (RTO_GLOBAL f4_t*)as_global(fd.image);
-    constexpr float INV_SPP = 1.0f / SPP;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int64_t idx = wave_px0 + p * 64 + lane;
-        if (idx >= SIZE) continue;
-        if (n[p]) {  // (a pixel without hits keeps its exact zeros, as before)
-            out[p][0] *= INV_SPP;
-            out[p][1] *= INV_SPP;
-            out[p][2] *= INV_SPP;
-            out[p][3] *= INV_SPP;
-        }
-        // volrend.cu:174-212 (write_pixel, through global-address-space pointers): background composite, then the 8 aux planes
-        // and the RGBA32F image with alpha = 1 -- or, lean (block-uniform), the four values their consumers read in one store
-        const float remain = opt.background_brightness * (1.f - out[p][3]);
-        const float r = out[p][0] + remain, g = out[p][1] + remain, b = out[p][2] + remain, al = out[p][3];
-        if (fb.lean) {
-            // (sparse, level 2: nothing for a pixel of an unmarked tile -- it is the background and its consumers know it)
-            if (fb.lean == 1 || ((live_bits >> p) & 1u)) g_image[idx] = f4_t{r, g, b, al};
-        } else {
-            RTO_GLOBAL float* a = g_aux + idx;
-            a[0] = r;
-            a[SIZE] = g;
-            a[2 * SIZE] = b;
-            a[3 * SIZE] = al;
-            a[4 * SIZE] = r * r;
-            a[5 * SIZE] = g * g;
-            a[6 * SIZE] = b * b;
-            a[7 * SIZE] = al * al;
-            g_image[idx] = f4_t{r, g, b, 1.0f};
-        }
-    }
-#ifdef RTO_DBG_COUNTERS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have left
-    RTO_SHADE_STAMP(5)
-    if (lane == 0 && blockIdx.x * (uint32_t)kShadeWaves + (uint32_t)wv < (uint32_t)kShadeStampWaves) {
-        unsigned long long* o = g_shade_phase + (size_t)(blockIdx.x * (uint32_t)kShadeWaves + (uint32_t)wv) * 8;
-        for (int i = 0; i <= 5; ++i) o[i] = ph[i];
-        o[6] = total;
-        o[7] = 1;
-    }
-#endif
+// the shading kernel over the context's colour layer (rto_ctx_set_layers): the same body, the epilogue composites every pixel --
+// hit, missed or culled -- over its pixel of the colour plane of its frame
+template <int SPP, int P, int MODE, int LOBES = 0>
+__global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kernel_layers(const TreeDev tree, const OptDev opt, const FrameBatch fb,
+                                                                                     const uint32_t* __restrict__ hits0, const LayerDev layers) {
+#define RTO_SHADE_LAYERS 1
+#include "rto_shade.inc"
+#undef RTO_SHADE_LAYERS
 }
 
 // ------------------------------------------------------------------ frame table
@@ -1899,7 +1394,7 @@ TileMap make_tile_map(int width, int height, int strip_rows) {
 
 template <int SPP, int LOBES>
 static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                        const FrameOut& fo, int strip_rows, hipStream_t stream) {
+                        const FrameOut& fo, int strip_rows, const LayerDev* layers, hipStream_t stream) {
     const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
     const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
     const dim3 grid(8 * tm.per_xcd), block(256);
@@ -1908,7 +1403,20 @@ static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& op
         hipLaunchKernelGGL((render_fast<SPP, ST, WI, SK>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);             \
     else                                                                                                                             \
         hipLaunchKernelGGL((render_fast_lobes<SPP, ST, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo)
-    if (fo.stats) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
+    if (layers) {  // (launch_fast's choice of the image; the host refuses layers with work counters)
+        const LayerDev ld = *layers;
+#define RTO_FAST_L(WI, SK) hipLaunchKernelGGL((render_fast_layers<SPP, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, ld)
+        if (tree.widew) {
+            if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
+                RTO_FAST_L(true, 1);
+            } else {
+                RTO_FAST_L(true, 0);
+            }
+        } else {
+            RTO_FAST_L(false, 0);
+        }
+#undef RTO_FAST_L
+    } else if (fo.stats) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
         RTO_FAST(true, false, 0);
     } else if (tree.widew) {
         if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {  // two pairs of levels below the grid at most
@@ -1924,16 +1432,21 @@ static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& op
 
 template <int SPP>
 static hipError_t launch_spp(int kernel, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
-                             const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, hipStream_t stream) {
+                             const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, const LayerDev* layers,
+                             hipStream_t stream) {
     if (kernel == 2) {
         if (tree.format == kFmtSG)
-            launch_fast<SPP, kFmtSG>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
+            launch_fast<SPP, kFmtSG>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
         else if (tree.format == kFmtASG)
-            launch_fast<SPP, kFmtASG>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
+            launch_fast<SPP, kFmtASG>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
         else
-            launch_fast<SPP, 0>(tree, cam, opt, rng, jump, fo, strip_rows, stream);
+            launch_fast<SPP, 0>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
     } else {
         const int64_t size = (int64_t)cam.width * cam.height;
+        if (layers)
+            hipLaunchKernelGGL(render_generic_layers<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam, opt, rng,
+                               fo, *layers);
+        else
         hipLaunchKernelGGL(render_generic<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam,
                            opt, rng, fo);
     }
@@ -2012,18 +1525,18 @@ hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_
 
 hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
                          const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows,
-                         hipStream_t stream) {
+                         const LayerDev* layers, hipStream_t stream) {
     switch (spp) {  // volrend.cu:266-278
 #ifndef RTO_DEV_SPP6_ONLY
-        case 1: return launch_spp<1>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 2: return launch_spp<2>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 3: return launch_spp<3>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 4: return launch_spp<4>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 8: return launch_spp<8>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 16: return launch_spp<16>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
-        case 32: return launch_spp<32>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
+        case 1: return launch_spp<1>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 2: return launch_spp<2>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 3: return launch_spp<3>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 4: return launch_spp<4>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 8: return launch_spp<8>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 16: return launch_spp<16>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
+        case 32: return launch_spp<32>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
 #endif
-        case 6: return launch_spp<6>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, stream);
+        case 6: return launch_spp<6>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -2050,10 +1563,30 @@ static void launch_shade_lobes(const dim3 sgrid, const TreeDev& tree, const OptD
 #undef RTO_SHADE_L
 }
 
-template <int SPP, int REFILL, int WPS, bool WIDE>
+// shade_kernel_layers for an expanded tree of any format (LOBES = 0: SH / RGBA; quantised-direct trees take no layers)
+template <int SPP, int SP, int LOBES>
+static void launch_shade_layers(const dim3 sgrid, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb, const uint32_t* hits,
+                                const LayerDev& layers, hipStream_t stream) {
+    const bool rec = LOBES != 0 || tree.format == 1;  // (the record modes: launch_batch_impl's / launch_shade_lobes' choice)
+#define RTO_SHADE_L(M) hipLaunchKernelGGL((shade_kernel_layers<SPP, SP, M, LOBES>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, hits, layers)
+    if (rec && tree.data_dim == 28)
+        RTO_SHADE_L(28);
+    else if (rec && tree.data_dim == 49)
+        RTO_SHADE_L(49);
+    else if (rec && tree.data_dim == 76)
+        RTO_SHADE_L(76);
+    else
+        RTO_SHADE_L(0);
+#undef RTO_SHADE_L
+}
+
+// LAYERS: the launch may carry layers (`layers` != nullptr: rto_ctx_set_layers) -- a depth layer takes render_persist_layers, a
+// colour layer shade_kernel_layers; instantiated for the default tuning only
+template <int SPP, int REFILL, int WPS, bool WIDE, bool LAYERS = false>
 static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                     const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                                    int chunk_override, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream) {
+                                    int chunk_override, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream,
+                                    const LayerDev* layers = nullptr) {
     // dynamic LDS: ancestor stack + thresholds per lane, then the frame table of THIS batch (96 B per frame: a batch of
     // one does not pay for 128)
     // (two pairs of levels below the grid at most: the ancestor stack is two registers and its LDS rows only park a ray's two
@@ -2062,6 +1595,14 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     const size_t lds = (size_t)((regstack ? 2 : tree.max_depth + 1 - tree.top_levels) + SPP + 1) * 256 * sizeof(uint32_t) + sizeof(float) * kCamFloats * (size_t)fb.n;
     const auto kern = regstack ? &render_persist<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0> : &render_persist<SPP, REFILL, WPS, WIDE, 0>;
     const void* fn = reinterpret_cast<const void*>(kern);
+    bool depth_layer = false, color_layer = false;
+    if constexpr (LAYERS) {
+        depth_layer = layers && layers->depth;
+        color_layer = layers && layers->color;
+        if (depth_layer)
+            fn = regstack ? reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>)
+                          : reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, 0>);
+    }
     OccupancyCache local;
     if (!occ) occ = &local;
     occ->lds_refused = false;
@@ -2078,7 +1619,7 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
             }
         }
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds) != hipSuccess || nb < 1)
             nb = 2;
         occ->blocks_per_cu = nb > 8 ? 8 : nb;
         occ->fn = fn;
@@ -2116,7 +1657,18 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     hipLaunchKernelGGL(queue_write_kernel, dim3(n_chunks), dim3(kQueueChunk), 0, stream, fb);
     hipLaunchKernelGGL(sample_kernel<SPP>, dim3((unsigned)(((tiles / fb.n + kSampleTiles - 1) / kSampleTiles + kSampleWaves - 1) / kSampleWaves), fb.n), dim3(64 * kSampleWaves), 0, stream, fb, jump);
     if (ev) (void)hipEventRecord(ev[1], stream);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
+    if constexpr (LAYERS) {
+        if (depth_layer) {
+            const LayerDev ld = *layers;
+            if (regstack)
+                hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb,
+                                   queue, hits, chunk, ld);
+            else
+                hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
+                                   hits, chunk, ld);
+        }
+    }
+    if (!depth_layer) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
     if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
     if (ev) (void)hipEventRecord(ev[2], stream);
 #ifndef RTO_SHADE_P
@@ -2131,7 +1683,16 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     const dim3 sgrid(((pblocks + 7u) / 8u) * 8u * (unsigned)fb.n);  // see shade_kernel: (pixel block, frame) <- block id
 #endif
 #define RTO_SHADE(M) hipLaunchKernelGGL((shade_kernel<SPP, SP, M>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, (const uint32_t*)hits)
-    if (tree.qrec) {  // (the host admits SH4/9/16/25 only)
+    if (color_layer) {  // (never a quantised-direct tree: the host refuses it layers)
+        if constexpr (LAYERS) {
+            if (tree.format == kFmtSG)
+                launch_shade_layers<SPP, SP, kFmtSG>(sgrid, tree, opt, fb, hits, *layers, stream);
+            else if (tree.format == kFmtASG)
+                launch_shade_layers<SPP, SP, kFmtASG>(sgrid, tree, opt, fb, hits, *layers, stream);
+            else
+                launch_shade_layers<SPP, SP, 0>(sgrid, tree, opt, fb, hits, *layers, stream);
+        }
+    } else if (tree.qrec) {  // (the host admits SH4/9/16/25 only)
         if (tree.basis_dim == 4)
             RTO_SHADE(-4);
         else if (tree.basis_dim == 9)
@@ -2160,7 +1721,7 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
 template <int SPP>
 static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                    const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                                   int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream) {
+                                   int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream) {
     // tuning: refill = 1000 * tiles_per_dequeue + 100 * waves/SIMD + threshold
     refill %= 100000;
     const int chunk_override = (refill / 1000) * 64;
@@ -2168,7 +1729,7 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     const bool wide = tree.widew != nullptr;
     if constexpr (SPP == 6) {  // tuning instantiations only for the benchmark configuration (and its usual two-level image)
 #define RTO_F(R, O) return launch_batch_impl<SPP, R, O, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream)
-        if (wide) switch (refill) {  // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
+        if (wide && !layers) switch (refill) {  // (a layered launch: the default instantiation whatever the key's A/B part says)  // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
             case 808: RTO_F(8, 8);
             case 816: RTO_F(16, 8);
             case 824: RTO_F(24, 8);
@@ -2194,6 +1755,11 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     // memory: rto_abi.cpp build_wide_image), else the one-level image: the same pixels either way.
     // (Round 5's reservoir kernel -- whole-tile set-up, rays parked in LDS, refill rounds at 8-24 idle lanes -- lost its same-box
     //  A/B, 4.27-4.32 against 4.11-4.20 ms per 100 C2 frames, and lives in tools/experiments/r5_lab_switches.patch.)
+    if (layers) {
+        if (wide)
+            return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers);
+        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers);
+    }
     if (wide)
         return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
     return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
@@ -2201,19 +1767,19 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
 
 hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream) {
+                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream) {
     switch (spp) {
 #ifndef RTO_DEV_SPP6_ONLY  // (development builds: compile the benchmark's instantiation only)
-        case 1: return launch_batch_spp<1>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
-        case 2: return launch_batch_spp<2>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
-        case 3: return launch_batch_spp<3>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
-        case 4: return launch_batch_spp<4>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
+        case 1: return launch_batch_spp<1>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 2: return launch_batch_spp<2>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 3: return launch_batch_spp<3>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 4: return launch_batch_spp<4>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
 #endif
-        case 6: return launch_batch_spp<6>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
+        case 6: return launch_batch_spp<6>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
 #ifndef RTO_DEV_SPP6_ONLY
-        case 8: return launch_batch_spp<8>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
-        case 16: return launch_batch_spp<16>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
-        case 32: return launch_batch_spp<32>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, stream);
+        case 8: return launch_batch_spp<8>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 16: return launch_batch_spp<16>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 32: return launch_batch_spp<32>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
 #endif
         default: return hipErrorInvalidValue;
     }

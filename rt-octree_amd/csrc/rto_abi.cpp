@@ -166,6 +166,9 @@ struct rto_ctx {
     float* aux = nullptr;
     float* noisy = nullptr;
     float* image = nullptr;
+    // rto_ctx_set_layers (RenderContext::offscreen = false): borrowed device planes, one per frame slot; both null = offscreen
+    const float* layer_depth = nullptr;  // [frames][H][W]
+    const float* layer_color = nullptr;  // [frames][H][W][4]
     uint8_t* rgba8 = nullptr;
     rto::Pcg32 rng{};
     rto::PcgJumpEntry* jump = nullptr;
@@ -1399,6 +1402,66 @@ void rto_ctx_rng_get(const rto_ctx* c, uint64_t* state, uint64_t* inc) {
     if (inc) *inc = c->rng.inc;
 }
 
+// device a pointer is memory of, -1 when the runtime does not know it
+static int pointer_device_of(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return a.device;
+}
+
+int rto_ctx_set_layers(rto_ctx* c, const float* depth, const float* color) {
+    if (!c) return set_err(RTO_E_INVALID, "rto_ctx_set_layers: null context");
+    if ((uintptr_t)color % 16 != 0) return set_err(RTO_E_INVALID, "rto_ctx_set_layers: color must be 16-byte aligned");
+    if ((uintptr_t)depth % 4 != 0) return set_err(RTO_E_INVALID, "rto_ctx_set_layers: depth must be 4-byte aligned");
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    const size_t px = frame_px(c) * (size_t)c->frames;
+    struct Range {
+        const char* what;
+        uintptr_t lo, hi;
+    };
+    const Range own[3] = {{"aux", (uintptr_t)c->aux, (uintptr_t)c->aux + px * RTO_AUX_CHANNELS * sizeof(float)},
+                          {"noisy", (uintptr_t)c->noisy, (uintptr_t)c->noisy + px * 4 * sizeof(float)},
+                          {"image", (uintptr_t)c->image, (uintptr_t)c->image + px * 4 * sizeof(float)}};
+    const Range in[2] = {{"depth", (uintptr_t)depth, (uintptr_t)depth + px * sizeof(float)},
+                         {"color", (uintptr_t)color, (uintptr_t)color + px * 4 * sizeof(float)}};
+    for (const Range& l : in) {
+        if (!l.lo) continue;
+        if (pointer_device_of((const void*)l.lo) != c->device)
+            return set_err(RTO_E_INVALID, std::string("rto_ctx_set_layers: ") + l.what + " is not memory of the context's device");
+        // (in-place use, the reference's surf_obj, is not offered: the batched path stores a pixel from another kernel than the
+        //  one that would have to read it)
+        for (const Range& o : own)
+            if (l.lo < o.hi && o.lo < l.hi)
+                return set_err(RTO_E_INVALID, std::string("rto_ctx_set_layers: ") + l.what + " overlaps the context's " + o.what +
+                                                  " buffer (keep the layers in buffers of their own)");
+    }
+    c->layer_depth = depth;
+    c->layer_color = color;
+    return RTO_OK;
+}
+
+int rto_ctx_layers(const rto_ctx* c, const float** depth, const float** color) {
+    if (!c) return set_err(RTO_E_INVALID, "rto_ctx_layers: null context");
+    if (depth) *depth = c->layer_depth;
+    if (color) *color = c->layer_color;
+    return RTO_OK;
+}
+
+// the layers of a launch whose first frame is context slot `slot0`, as the kernels take them; false: the context has none
+static bool ctx_layers_at(const rto_ctx* c, int slot0, rto::LayerDev* out) {
+    if (!c->layer_depth && !c->layer_color) return false;
+    const size_t off = (size_t)slot0 * frame_px(c);
+    out->depth = c->layer_depth ? c->layer_depth + off : nullptr;
+    out->color = c->layer_color ? reinterpret_cast<const float4*>(c->layer_color) + off : nullptr;
+    return true;
+}
+static const char* const kLayersNoStats = "layers (rto_ctx_set_layers) and work counters (rto_ctx_enable_stats) do not combine";
+static const char* const kLayersNoQuant = "a quantised tree loaded with RTO_TREE_QUANT_DIRECT takes no layers (rto_ctx_set_layers): expand it";
+
 int rto_ctx_set_kernel(rto_ctx* c, int kernel) {
     if (!c || kernel < RTO_KERNEL_AUTO || kernel > RTO_KERNEL_FAST)
         return set_err(RTO_E_INVALID, "rto_ctx_set_kernel: bad argument");
@@ -1638,6 +1701,10 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
 int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_options* o, rto_ctx* ctx,
                         void* stream_) {
     if (!tree || !cam || !o || !ctx) return set_err(RTO_E_INVALID, "rto_launch_renderer: null argument");
+    rto::LayerDev layers;
+    const bool layered = ctx_layers_at(ctx, ctx->sel, &layers);  // (a single-frame launch reads the selected slot's planes)
+    if (layered && ctx->stats_on) return set_err(RTO_E_UNSUPPORTED, kLayersNoStats);
+    if (layered && tree->quant) return set_err(RTO_E_UNSUPPORTED, kLayersNoQuant);
     if (tree->quant) {  // codebook shading lives in the batched kernels: a batch of one into the selected slot
         if (ctx->kernel == RTO_KERNEL_GENERIC || ctx->stats_on)
             return set_err(RTO_E_UNSUPPORTED, "a quantised tree loaded with RTO_TREE_QUANT_DIRECT has no generic kernel / work counters");
@@ -1733,9 +1800,10 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     ctx->lean_slot[(size_t)ctx->sel] = 0;  // (a single frame has full outputs; the other slots keep what they hold)
     // (the generic kernel reads tree->dev itself: child[] / data[] may just have been rebuilt by ensure_reference_arrays)
     hipError_t e = rto::launch_render(kernel, o->spp, kernel == RTO_KERNEL_FAST ? tdev : tree->dev, cd, od, ctx->rng, ctx->jump, fo,
-                                      ctx->strip_rows, stream);
+                                      ctx->strip_rows, layered ? &layers : nullptr, stream);
     if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("render launch failed: ") + hipGetErrorString(e));
-    if (cull_one) {  // the selected slot's marks, for rto_ctx_tile_marks / the culled denoise stage
+    // (over a colour layer an unmarked tile is not the constant background: the marks are kept from the denoise stage)
+    if (cull_one && !(layered && layers.color)) {  // the selected slot's marks, for rto_ctx_tile_marks / the culled denoise stage
         ctx->marks_n = 1;
         ctx->marks_slot0 = ctx->sel;
         ctx->marks_bg = o->background_brightness;
@@ -1841,8 +1909,10 @@ static int generic_frames(const rto_tree* tree, const rto_camera* cams, const in
         fo.stats = nullptr;
         fo.stat_marks = nullptr;
         fo.stat_mask_words = 0;
+        rto::LayerDev layers;
+        const bool layered = ctx_layers_at(ctx, slot0 + f, &layers);
         hipError_t e = rto::launch_render(RTO_KERNEL_GENERIC, o->spp, tree->dev, cd, od, rng, ctx->jump, fo, ctx->strip_rows,
-                                          (hipStream_t)stream_);
+                                          layered ? &layers : nullptr, (hipStream_t)stream_);
         if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("render launch failed: ") + hipGetErrorString(e));
     }
     return RTO_OK;
@@ -1862,6 +1932,14 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
                                           "density only: sigma_thresh must be >= 0");
     if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature, not on the headless path");
     if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
+    rto::LayerDev layers;
+    const bool layered = ctx_layers_at(ctx, slot0, &layers);  // (batch frame f = slot slot0 + f reads plane slot0 + f)
+    if (layered && ctx->stats_on) return set_err(RTO_E_UNSUPPORTED, kLayersNoStats);
+    if (layered && tree->quant) return set_err(RTO_E_UNSUPPORTED, kLayersNoQuant);
+    // sparse lean outputs store nothing for unmarked tiles because those are the constant background -- not over a colour layer
+    if (layered && layers.color && o->denoise && ctx->lean == 2)
+        return set_err(RTO_E_UNSUPPORTED, "sparse lean outputs (rto_ctx_set_lean_outputs level 2) need a constant backdrop: not with a colour "
+                                          "layer (rto_ctx_set_layers)");
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     ctx->marks_n = 0;  // whatever happens below, the tile marks of an earlier launch no longer describe this context's frames
@@ -1973,7 +2051,7 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
     ctx->occ.force_lds_refusal = ctx->batch_fallback == 2;
     hipError_t e = rto::launch_render_batch(o->spp, tdev, od, fb, ctx->jump, ctx->queue,
                                             ctx->hits + (size_t)slot0 * o->spp * px,  // = fb.f[0].hits: the kernel indexes frames from here
-                                            ctx->num_cus, ctx->refill, cull, &ctx->occ, ev, stream);
+                                            ctx->num_cus, ctx->refill, cull, &ctx->occ, ev, layered ? &layers : nullptr, stream);
     if (ctx->occ.lds_refused) {
         if (ev) --ctx->kt_count;  //  nothing was launched, nothing recorded the slot's events: give it back
         // the device does not grant a workgroup the LDS the traversal kernel needs for this depth x SPP x frame count
@@ -1982,7 +2060,9 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
         return generic_frames(tree, cams, rng_jumps, n, o, ctx, stream_, slot0);
     }
     if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("batched render launch failed: ") + hipGetErrorString(e));
-    ctx->marks_n = n;
+    // (over a colour layer an unmarked tile's pixels are not the constant background the marks' consumers take them for: the
+    //  launch culled its marching with them, and rto_ctx_tile_marks / rto_denoise then see none)
+    ctx->marks_n = layered && layers.color ? 0 : n;
     ctx->marks_slot0 = slot0;
     ctx->marks_bg = o->background_brightness;
     if (fb.lean)

@@ -204,6 +204,14 @@ struct RayBatch {
     uint32_t per_xcd;         // 0: block b takes rays 256 b ..; else workgroups per XCD: each XCD takes one contiguous range
 };
 
+// The layers of rto_ctx_set_layers as the layered kernels see them (render_fast_layers, render_generic_layers,
+// render_persist_layers, shade_kernel_layers): plane 0 = the launch's first frame.  A kernel argument of its own, BEHIND the
+// arguments of the offscreen kernels -- a member of FrameOut / FrameBatch would move their other arguments.
+struct LayerDev {
+    const float* depth;   // [frames][H][W] world distance along the unit direction where a pixel's ray stops, or nullptr (1e9f)
+    const float4* color;  // [frames][H][W] (r, g, b, unread) the volume is composited over, or nullptr (background_brightness)
+};
+
 // stats[0..5] = SURVEY 8d's units over EVERY ray (orc_stats order: rays, rays_in_box, steps, levels of a root-restart walk,
 // hit leaves, rays with a hit); stats[6..11] = the same frame as the batched path works through it: rays of marked tiles,
 // their march steps, top-grid entries loaded (8 B each), traversal-image words loaded (4 B each), hit entries written,

@@ -29,8 +29,11 @@ hipError_t launch_build_topgrid(const uint32_t* nodew, int G, uint2* grid, hipSt
 TileMap make_tile_map(int width, int height, int strip_rows);
 
 // kernel: 1 = generic, 2 = fast.  spp must be one of {1,2,3,4,6,8,16,32} (hipErrorInvalidValue otherwise)
+// layers != nullptr (rto_ctx_set_layers; never with fo.stats): the layered kernels -- pixel (x, y) stops at layers->depth[y W + x]
+// and is composited over layers->color[y W + x] (the caller has offset both to the frame's plane)
 hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
-                         const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, hipStream_t stream);
+                         const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, const LayerDev* layers,
+                         hipStream_t stream);
 
 // rto_launch_rays: the rb.n rays of rb (rb.n * spp < 2^32, else hipErrorInvalidValue) with the fast (2: render_rays) or the generic
 // (1: render_rays_generic) kernel; ray i draws its samples from rng advanced by i * spp.  xcd_order: each XCD takes one contiguous
@@ -59,10 +62,11 @@ struct OccupancyCache {
 };
 
 // persistent batched renderer (N == 2 trees): fb.n frames in one launch (traversal kernel, then the
-// shading kernel); `queue` = kQueueWords u64 (zeroed by queue_scan_kernel on the stream before every traversal launch); ev = nullptr or 4 events recorded before the thresholds kernel, before / after the traversal, after the shading
+// shading kernel); layers != nullptr (rto_ctx_set_layers): frame f stops at plane f of layers->depth and is composited over plane
+// f of layers->color, by the layered kernels of the default tuning (the A/B part of `refill` is then ignored); `queue` = kQueueWords u64 (zeroed by queue_scan_kernel on the stream before every traversal launch); ev = nullptr or 4 events recorded before the thresholds kernel, before / after the traversal, after the shading
 hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream);
+                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream);
 
 // quant_map [nq][ns] + data_retained [nr][ns][3] -> slot-major records of `rec` u16 (TreeDev::qrec)
 hipError_t launch_pack_quant(const uint16_t* qmap, const uint16_t* retained, int64_t ns, int nr, int nq, int rec,

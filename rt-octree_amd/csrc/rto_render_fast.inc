@@ -1,6 +1,8 @@
 // rto_render_fast.inc -- body of the single-frame fast kernel, included by render_kernels.hip into render_fast (LOBES = 0: SH and
 // RGBA trees), render_fast_lobes (LOBES = kFmtSG / kFmtASG) and render_rays (RTO_FAST_RAYS defined to 1 around the include: the
-// rays of rto_launch_rays instead of a camera's pixels).  In scope: the kernel parameters and SPP, STATS, WIDE, STACK, LOBES.
+// rays of rto_launch_rays instead of a camera's pixels) and render_fast_layers (RTO_FAST_LAYERS defined to 1: a camera's pixels,
+// each ray stopped at its pixel of the depth layer and composited over its pixel of the colour layer -- `layers`, rto_ctx_set_layers).
+// In scope: the kernel parameters and SPP, STATS, WIDE, STACK, LOBES.
 // (The ray source is switched by the preprocessor, not by if constexpr: the frame kernels' text -- and so their code -- is
 // exactly what it was before the ray kernel existed.)
     extern __shared__ uint32_t s_stack[];  // [max_depth][256] ancestor node indices, level-major
@@ -24,15 +26,27 @@
     const int idx = y * cam.width + x;
 
     float out[4] = {0.f, 0.f, 0.f, 0.f};
+#if RTO_FAST_LAYERS
+    float bg[3];
+    layer_backdrop(layers, (uint32_t)idx, opt.background_brightness, bg);
+#endif
     if (!STATS && fo.cull_marks) {  // (wave-uniform: a wave is one 8x8 tile)
         const uint32_t t = (uint32_t)(y >> 3) * ((uint32_t)(cam.width + 7) >> 3) + (uint32_t)(x >> 3);
         if (!(((fo.cull_marks[t >> 5] >> (t & 31u)) | fo.cull_marks[fo.cull_mask_words - 1]) & 1u)) {
+#if RTO_FAST_LAYERS
+            write_pixel_over(fo, SIZE, idx, bg, out);  // no ray of this tile meets density, whatever its depth: the backdrop
+#else
             write_pixel(fo, SIZE, idx, opt.background_brightness, out);  // no ray of this tile meets density: background
+#endif
             return;
         }
     }
     float dir[3], vdir[3], cen[3], invdir[3];
     ray_setup(x, y, cam, tree, dir, vdir, cen);
+#if RTO_FAST_LAYERS
+    const float tmax_bg = layers.depth ? layers.depth[idx] : 1e9f;
+    const bool live = ray_is_live(tmax_bg, dir, cen);  // (false: not traced, as a degenerate ray of rto_launch_rays)
+#endif
 #endif
     float delta_scale, tmin, tmax;
     unsigned long long st_steps = 0, st_levels = 0, st_hits = 0, st_inbox = 0, st_grid = 0, st_words = 0, st_wide = 0;
@@ -40,6 +54,10 @@
     if (live && ray_enter(tree, opt, dir, cen, tmax_bg, invdir, delta_scale, tmin, tmax)) {
         Pcg32 rng = rng_base;
         pcg_advance_tab(rng, ray * (uint32_t)SPP, jump);  // (the host keeps n * SPP < 2^32)
+#elif RTO_FAST_LAYERS
+    if (live && ray_enter(tree, opt, dir, cen, tmax_bg, invdir, delta_scale, tmin, tmax)) {
+        Pcg32 rng = rng_base;
+        pcg_advance_tab(rng, (uint32_t)(idx * SPP), jump);
 #else
     if (ray_enter(tree, opt, dir, cen, 1e9f, invdir, delta_scale, tmin, tmax)) {
         if (STATS) st_inbox = 1;
@@ -291,6 +309,9 @@
     }
 #if RTO_FAST_RAYS
     write_ray(rays, ray, bg, out);
+    (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
+#elif RTO_FAST_LAYERS
+    write_pixel_over(fo, SIZE, idx, bg, out);
     (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
 #else
     write_pixel(fo, SIZE, idx, opt.background_brightness, out);

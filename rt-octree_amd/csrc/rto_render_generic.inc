@@ -1,5 +1,6 @@
 // rto_render_generic.inc -- body of the generic kernel, included by render_kernels.hip into render_generic (a camera's pixels)
-// and render_rays_generic (RTO_GENERIC_RAYS defined to 1 around the include: the rays of rto_launch_rays).  In scope: the kernel
+// render_rays_generic (RTO_GENERIC_RAYS defined to 1 around the include: the rays of rto_launch_rays) and render_generic_layers
+// (RTO_GENERIC_LAYERS defined to 1: a camera's pixels over the layers of rto_ctx_set_layers).  In scope: the kernel
 // parameters and SPP.  (The ray source is switched by the preprocessor: render_generic's text and code are unchanged.)
 #if RTO_GENERIC_RAYS
     const uint32_t ray = ray_index(rays, blockIdx.x, threadIdx.x);
@@ -11,6 +12,23 @@
     if (tree.N > 0 && live) {  // enable_draw volrend.cu:98
         Pcg32 rng = rng_base;
         pcg_advance(rng, (int64_t)ray * SPP);  // volrend.cu:157
+        float delta_scale, tmin, tmax;
+        if (ray_enter(tree, opt, dir, cen, tmax_bg, invdir, delta_scale, tmin, tmax)) {
+#elif RTO_GENERIC_LAYERS
+    const int64_t SIZE = (int64_t)cam.width * cam.height;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= SIZE) return;
+    const int x = idx % cam.width, y = idx / cam.width;
+    float out[4] = {0.f, 0.f, 0.f, 0.f};
+    float dir[3], vdir[3], cen[3], invdir[3], bg[3];
+    layer_backdrop(layers, (uint32_t)idx, opt.background_brightness, bg);
+    ray_setup(x, y, cam, tree, dir, vdir, cen);
+    const float tmax_bg = layers.depth ? layers.depth[idx] : 1e9f;
+    const bool live = ray_is_live(tmax_bg, dir, cen);  // (false: not traced, as a degenerate ray of rto_launch_rays)
+
+    if (tree.N > 0 && live) {  // enable_draw volrend.cu:98
+        Pcg32 rng = rng_base;
+        pcg_advance(rng, (int64_t)(idx * SPP));  // volrend.cu:157
         float delta_scale, tmin, tmax;
         if (ray_enter(tree, opt, dir, cen, tmax_bg, invdir, delta_scale, tmin, tmax)) {
 #else
@@ -92,6 +110,8 @@
     }
 #if RTO_GENERIC_RAYS
     write_ray(rays, ray, bg, out);
+#elif RTO_GENERIC_LAYERS
+    write_pixel_over(fo, SIZE, idx, bg, out);
 #else
     write_pixel(fo, SIZE, idx, opt.background_brightness, out);
 #endif

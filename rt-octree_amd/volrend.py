@@ -295,6 +295,7 @@ class RenderContext:
         self._h = h
         self.width, self.height, self.device, self.frames = int(width), int(height), int(device), int(frames)
         self.offscreen = True
+        self._layers = (None, None)  # the tensors handed to set_layers: kept referenced while the context may read them
         self._timer = Timer(self)
 
     # rng (pcg32.h)
@@ -329,6 +330,28 @@ class RenderContext:
 
     def set_kernel(self, kernel):
         check(lib().rto_ctx_set_kernel(self._h, int(kernel)))
+
+    def set_layers(self, depth=None, color=None):
+        """rto_ctx_set_layers (RenderContext::offscreen = false): launch_renderer / launch_renderer_batch stop every pixel's ray at
+        `depth` [frames, H, W] (world distance along the unit direction; +inf = no limit) and composite the volume over `color`
+        [frames, H, W, 4] (rgb read) instead of the constant background.  Contiguous float32 torch tensors on the context's device
+        (numpy arrays are copied over); either may be None, both None restores the offscreen behaviour.  Frame slot k reads plane
+        k.  The tensors stay referenced by the context; they must not be the context's own buffers."""
+        import torch
+        device = torch.device("cuda", self.device)
+        n = self.frames * self.height * self.width
+        d = None if depth is None else _ray_tensor(_as_planes(depth, (self.frames, self.height, self.width)), "depth", 0, n, device)
+        c = None if color is None else _ray_tensor(_as_planes(color, (self.frames, self.height, self.width, 4)), "color", 4, n, device)
+        check(lib().rto_ctx_set_layers(self._h, C.c_void_p(d.data_ptr()) if d is not None else None,
+                                       C.c_void_p(c.data_ptr()) if c is not None else None))
+        self._layers = (d, c)
+        self.offscreen = d is None and c is None
+
+    def layers(self):
+        """(depth pointer or None, colour pointer or None) the context holds (rto_ctx_layers)"""
+        d, c = C.c_void_p(None), C.c_void_p(None)
+        check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
+        return d.value, c.value
 
     def timer(self):
         return self._timer
@@ -435,10 +458,11 @@ class RenderContext:
 def launch_renderer(tree, cam, options, ctx, stream=None, offscreen=True):
     """volrend::launch_renderer(tree, cam, options, ctx, stream, offscreen)
     (renderer_kernel.hpp:11-16).  Asynchronous on `stream`.  Unsupported spp raises like the
-    reference's std::runtime_error("spp == N not supported.") (volrend.cu:275-277).  offscreen=False (GL
-    interop) raises; the volume composited over the caller's depth and colour, per ray, is render_rays."""
-    if not offscreen:  # (per-ray depth limits and backdrops, the compositing of offscreen = false: render_rays)
-        raise RtoError(-3, "only the offscreen (headless) path is built; GL interop is out of scope")
+    reference's std::runtime_error("spp == N not supported.") (volrend.cu:275-277).  offscreen=False renders over the
+    context's depth / colour layers (RenderContext.set_layers: the reference's surf_obj_depth / surf_obj) and raises when the
+    context has none; a context with layers composites over them whatever `offscreen` says (rto_ctx_set_layers)."""
+    if not offscreen and ctx.layers() == (None, None):
+        raise RtoError(-3, "offscreen=False needs a depth / colour layer on the context (RenderContext.set_layers); GL interop is out of scope")
     cc, co = cam.to_c(), options.to_c()
     check(lib().rto_launch_renderer(tree._h, C.byref(cc), C.byref(co), ctx._h, _stream_ptr(stream)))
 
@@ -475,6 +499,15 @@ def camera_rays(cam):
             dirs[..., c] = m[c] * xyz0 + m[3 + c] * xyz1 + m[6 + c] * xyz2
     origins = np.broadcast_to(m[9:12], (H * W, 3)).copy()
     return origins, dirs.reshape(H * W, 3)
+
+
+def _as_planes(a, shape):
+    """a layer given in its frame shape [frames, H, W(, 4)] (a single-slot context also takes [H, W(, 4)]) -> the flat shape
+    _ray_tensor checks; anything else is passed on for _ray_tensor to refuse"""
+    got = tuple(a.shape)
+    if got == tuple(shape) or (shape[0] == 1 and got == tuple(shape[1:])):
+        return a.reshape((-1, 4) if len(shape) == 4 else (-1,))
+    return a
 
 
 def _ray_tensor(a, name, cols, n, device):
