@@ -47,7 +47,7 @@ extern "C" {
 #define RTO_OK 0
 #define RTO_E_INVALID -1     /* bad argument */
 #define RTO_E_SPP -2         /* spp not in {1,2,3,4,6,8,16,32} (volrend.cu:266-278) */
-#define RTO_E_UNSUPPORTED -3 /* feature outside the headless path (GUI probe), or a combination not built (e.g. SG/ASG + QUANT_DIRECT) */
+#define RTO_E_UNSUPPORTED -3 /* a combination not built (e.g. SG/ASG + QUANT_DIRECT, enable_probe over layers) */
 #define RTO_E_HIP -4         /* HIP runtime error / no device */
 #define RTO_E_IO -5          /* file missing / malformed */
 #define RTO_E_FORMAT -6      /* npz content violates the tree schema (n3tree.cpp:283-291,345) */
@@ -70,7 +70,7 @@ typedef struct rto_options {
     int show_grid;                /* false; GUI */
     int grid_max_depth;           /* 4; GUI */
     int render_depth;             /* false; unused by the kernel */
-    int enable_probe;             /* false; GUI probe -> RTO_E_UNSUPPORTED when set */
+    int enable_probe;             /* false; draws the lumisphere of the leaf at `probe` into the frame's top right corner (see rto_launch_renderer) */
     float probe[3];               /* {0,0,1} */
     int probe_disp_size;          /* 100 */
     int denoise;                  /* true: kernel writes the noisy image, else the final image */
@@ -236,7 +236,8 @@ void rto_ctx_rng_get(const rto_ctx* c, uint64_t* state, uint64_t* inc);
  * level-2 launch returns RTO_E_UNSUPPORTED.
  * RTO_E_INVALID: color not 16-byte aligned, a layer that overlaps the context's buffers or is not memory of the context's device
  * (the context keeps the layers it had).  Launches return RTO_E_UNSUPPORTED for layers combined with rto_ctx_enable_stats or
- * with a tree loaded with RTO_TREE_QUANT_DIRECT.  enable_probe stays RTO_E_UNSUPPORTED. */
+ * with a tree loaded with RTO_TREE_QUANT_DIRECT.  enable_probe on a context with layers stays RTO_E_UNSUPPORTED: the suite pins that
+ * refusal, it is not principled -- the probe's overlay (rto_launch_renderer) would work over layers as it does offscreen. */
 int rto_ctx_set_layers(rto_ctx* c, const float* depth, const float* color);
 /* the layers the context holds (NULL: none); either out pointer may be NULL */
 int rto_ctx_layers(const rto_ctx* c, const float** depth, const float** color);
@@ -317,10 +318,53 @@ int rto_wide_image_probe(const int32_t* child, const uint16_t* sigma_bits, int64
                          const uint32_t* points, int64_t n, int32_t* out_level, int64_t* out_slot, uint16_t* out_sigma,
                          int64_t* out_wide_nodes);
 
+/* ---- point queries (svox's tree(points); the reference's query_single_from_root, n3tree_query.hpp:13-48) ---- */
+/* What the tree holds at n points.  All pointers are device memory on the tree's device; any member of rto_query_out may be NULL
+ * (that output is not computed; sigma, level and cube come from the walk alone and read neither data[] nor a coefficient record). */
+typedef struct rto_query_out {
+    float*   values; /* [n][data_dim]: half -> float of the leaf's data[], in data[]'s order (last = sigma) */
+    float*   sigma;  /* [n] */
+    int32_t* level;  /* [n]: levels of child[] visited to reach the leaf (rto_tree_info.max_depth's convention); -1 = not answered */
+    float*   cube;   /* [n][4], 16-byte aligned: the leaf's min corner in tree coordinates and its side, 1 / cube_sz */
+} rto_query_out;
+/* Point p (world space) maps to xyz[i] = offset[i] + scale[i] * p[i] in float arithmetic, the product rounded before the add
+ * (volrend.cu:220-222); NO NDC warp is applied, also for an NDC tree (the reference's probe applies none): pass points of the
+ * tree's own space there.  Then the reference's clamp to [0, 1 - 1e-6f] and its descent: the answer names the leaf
+ * query_single_from_root reaches, for every finite float, whichever traversal image the kernel walks.  A point with a non-finite
+ * coordinate is not answered: level -1, zeros elsewhere (the convention of rto_launch_rays' degenerate rays).
+ * Asynchronous on `stream`: no host synchronisation, no allocation and no host-to-device copy per call; n == 0 launches nothing.
+ * Splitting a call gives the same bytes.  Reads the tree as it is resident: child[] / data[] of a tree that released them are
+ * not brought back.
+ * RTO_E_INVALID (checked before any device use): null tree or out, n < 0, null points with n > 0, cube not 16-byte aligned.
+ * RTO_E_UNSUPPORTED, for `values` only (sigma, level and cube still work): a tree loaded with RTO_TREE_QUANT_DIRECT (its values
+ * live in codebooks, as for rto_launch_rays); a tree loaded with RTO_TREE_COMPACT_RECORDS, which keeps the coefficients of leaves
+ * with sigma > 0 only -- load it with RTO_TREE_KEEP_REFERENCE as well. */
+int rto_tree_query(const rto_tree* tree, const float* points /* device [n][3] world space */, int64_t n,
+                   const rto_query_out* out, void* stream);
+
 /* ---- the operator ---- */
 /* launch_renderer(tree, cam, options, ctx, stream, offscreen) (volrend.cu:236-285); offscreen = false is a context with
  * layers (rto_ctx_set_layers).  Asynchronous on `stream`.  Writes ctx aux + (options->denoise ? noisy : image).
- * cam->width/height must equal the ctx size. */
+ * cam->width/height must equal the ctx size.
+ * options->enable_probe (volrend.cu:100-134, 215-231, 244-251; offscreen contexts, both launch forms): one query of the point
+ * options->probe -- as rto_tree_query maps, clamps and answers it -- fetches that leaf's coefficients into a buffer the context
+ * owns (stream-ordered; the reference allocates and frees one per launch), and behind the render kernels one overlay kernel
+ * overwrites the pixels of the probe's disc in every output the launch wrote, for each frame with its camera.  A disc pixel never
+ * depended on the trace (enable_draw = false), a pixel outside the disc is traced as always: the overlay is exact.  Pixel (x, y)
+ * with y < probe_disp_size + 5 and x >= width - probe_disp_size - 5 is in the disc when c = cen0^2 + cen1^2 <= 1.f, cen0 =
+ * -(xx / (0.5f * probe_disp_size) - 1.f), cen1 = yy / (0.5f * probe_disp_size) - 1.f, xx = x - (width - probe_disp_size) + 5,
+ * yy = y - 5 (float arithmetic, every operation rounded).  Its colour: dir = M (cen0, cen1, -sqrtf(1 - c)) with the camera's
+ * rotation columns (not normalised, no rot_dirs rotation), the tree's basis at dir, per channel tmp = the left-to-right sum of
+ * basis[i] * coeff[channel * basis_dim + i] and 1.f / (1.f + expf(-tmp)) in the library's deterministic expf; an RGBA tree's first
+ * three coefficients as they are.  Outputs as volrend.cu:174-212 with nalpha = 0: aux planes 0..3 = (r, g, b, 1), 4..7 their
+ * squares, the noisy / final image (r, g, b, 1); a lean level-1 launch stores (r, g, b, 1).  The disc is clipped to the image.
+ * Deviation: the reference sums i = basis_minmax[0] .. basis_minmax[1] whatever the tree's basis_dim (with the default {0, 24} on
+ * an SH9 tree it reads uninitialised basis entries and the next channel's coefficients); here i runs over max(lo, 0) ..
+ * min(hi, basis_dim - 1).
+ * With the probe on a launch still culls its marching but leaves no tile marks (the disc is no background: the colour layer's
+ * precedent) -- rto_ctx_tile_marks returns RTO_E_INVALID after it, rto_denoise takes its plain kernels, a lean level-2 launch
+ * returns RTO_E_UNSUPPORTED, the tuning key "cull_single" is ignored.  RTO_E_INVALID: probe_disp_size <= 0.  RTO_E_UNSUPPORTED:
+ * a context with layers, rto_ctx_enable_stats, a tree whose `values` rto_tree_query refuses. */
 int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_options* options,
                         rto_ctx* ctx, void* stream);
 
@@ -355,7 +399,7 @@ typedef struct rto_rays {
  * A degenerate ray -- non-finite origin, a direction that is zero, NaN, infinite or whose squared length under- / overflows,
  * t_max <= 0 or NaN -- returns its backdrop with alpha 0.
  * RTO_E_INVALID: a null argument, n < 0, first_ray < 0, null origins / dirs with n > 0, out not 16-byte aligned, tree and ctx
- * on different devices; RTO_E_SPP; RTO_E_UNSUPPORTED: enable_probe, or a tree loaded with RTO_TREE_QUANT_DIRECT (its codebook
+ * on different devices; RTO_E_SPP; RTO_E_UNSUPPORTED: enable_probe (the probe is drawn into a frame; rays have none), or a tree loaded with RTO_TREE_QUANT_DIRECT (its codebook
  * shading lives only in the batched kernels); RTO_E_FORMAT: an SG / ASG tree without lobes.  n == 0 launches nothing. */
 int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_options* options, rto_ctx* ctx, float* out,
                     void* stream);

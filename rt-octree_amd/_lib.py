@@ -42,6 +42,11 @@ class CRays(C.Structure):
                 ("n", C.c_int64), ("first_ray", C.c_int64)]
 
 
+class CQueryOut(C.Structure):
+    """rto_query_out (include/rto.h): device pointers, any of them NULL"""
+    _fields_ = [("values", C.c_void_p), ("sigma", C.c_void_p), ("level", C.c_void_p), ("cube", C.c_void_p)]
+
+
 class CTreeInfo(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64), ("N", C.c_int), ("data_dim", C.c_int), ("format", C.c_int),
@@ -74,6 +79,7 @@ SYMBOLS = {
                                              _P, C.c_int64, C.POINTER(_P)]),
     "rto_tree_set_ndc": (C.c_int, [_P, C.c_float, C.c_float, C.c_float]),
     "rto_tree_get_info": (C.c_int, [_P, C.POINTER(CTreeInfo)]),
+    "rto_tree_query": (C.c_int, [_P, _P, C.c_int64, C.POINTER(CQueryOut), _P]),
     "rto_tree_probe_npz": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "rto_tree_free": (None, [_P]),
     "rto_ctx_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -109,6 +109,7 @@ void usage() {
         "  --fx F --fy F      focal lengths (-1 = 1111.11 / fx)\n"
         "  --bg B             background brightness 0-1 (1.0)\n"
         "  -s,--step_size -e,--stop_thresh -a,--sigma_thresh   render options when no --options file\n"
+        "  --probe x,y,z      (no --options file) draw the lumisphere of the leaf at that world point into the top right corner\n"
         "  --options opt.json render options (spp, denoise, ...)\n"
         "  --dataset blender|tt|llff (blender)\n"
         "  --ts_module ts.ts  TorchScript GuidanceNet (needed when denoise = true)\n"
@@ -380,6 +381,15 @@ int main(int argc, char** argv) {
         options.step_size = (float)std::atof(args.get("step_size", "1e-4").c_str());
         options.stop_thresh = (float)std::atof(args.get("stop_thresh", "1e-2").c_str());
         options.sigma_thresh = (float)std::atof(args.get("sigma_thresh", "1e-2").c_str());
+        if (args.has("probe")) {  // opts.cpp:52-58: --probe x,y,z draws the lumisphere of the leaf at that point
+            float xyz[3];
+            if (std::sscanf(args.get("probe", "").c_str(), " %f , %f , %f", &xyz[0], &xyz[1], &xyz[2]) != 3) {  // (fewer than three values)
+                std::fputs("ERROR: --probe must be of format 'x,y,z'\n", stderr);
+                return 1;
+            }
+            options.enable_probe = 1;
+            for (int i = 0; i < 3; ++i) options.probe[i] = xyz[i];
+        }
     }
 
     int batch = std::max(1, std::min(128, std::atoi(args.get("batch", "100").c_str())));

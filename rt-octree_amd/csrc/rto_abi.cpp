@@ -24,6 +24,7 @@
 namespace {
 
 constexpr int kKtRing = 256;
+constexpr int kProbeFloats = 128;  // >= 3 * RTO_BASIS_MAX: what the probe's disc reads of a leaf's data_dim - 1 coefficients
 
 thread_local std::string g_err;
 
@@ -103,6 +104,7 @@ struct rto_tree {
     void* d_qsigma = nullptr;
     void* d_extra = nullptr;  // SG / ASG lobes (TreeDev::extra)
     bool quant = false;  // rendered from the codebooks; only the batched path can shade it
+    int flags = 0;       // the RTO_TREE_* flags of the upload
     bool fast_ok = false;
     // Footprint (VERDICT r2 task 8): a dense SH9 / SH16 tree that renders through the fast / batched kernels reads only
     // nodew + topgrid + shrec, so child[] / data[] are released after the upload and rebuilt from those two on the first
@@ -169,6 +171,7 @@ struct rto_ctx {
     // rto_ctx_set_layers (RenderContext::offscreen = false): borrowed device planes, one per frame slot; both null = offscreen
     const float* layer_depth = nullptr;  // [frames][H][W]
     const float* layer_color = nullptr;  // [frames][H][W][4]
+    float* probe_coeffs = nullptr;       // kProbeFloats: the probe point's leaf coefficients of the launch in flight (enable_probe)
     uint8_t* rgba8 = nullptr;
     rto::Pcg32 rng{};
     rto::PcgJumpEntry* jump = nullptr;
@@ -549,6 +552,7 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
 
     auto t = new rto_tree();
     t->device = device;
+    t->flags = flags;
     const int64_t N3 = (int64_t)N * N * N;
     const int64_t n_slots = capacity * N3;
     // Re-lay the tree breadth-first unless the file already is (derived layout: every query returns the same
@@ -1320,6 +1324,7 @@ int rto_ctx_create_batch(int width, int height, int frames, int device, rto_ctx*
         hipMalloc((void**)&c->rgba8, px * 4) != hipSuccess ||
         hipMalloc((void**)&c->queue, rto::kQueueWords * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void**)&c->d_frames, rto::kMaxBatch * sizeof(rto::FrameDesc)) != hipSuccess ||
+        hipMalloc((void**)&c->probe_coeffs, kProbeFloats * sizeof(float)) != hipSuccess ||
         hipMemset(c->queue, 0, rto::kQueueWords * sizeof(unsigned long long)) != hipSuccess) {
         rto_ctx_free(c);
         return set_err(RTO_E_HIP, "hipMalloc(ctx buffers) failed");
@@ -1357,6 +1362,7 @@ void rto_ctx_free(rto_ctx* c) {
     for (void* p : {(void*)c->tile_mask, (void*)c->qlist, (void*)c->qscratch})
         if (p) (void)hipFree(p);
     if (c->d_frames) (void)hipFree(c->d_frames);
+    if (c->probe_coeffs) (void)hipFree(c->probe_coeffs);
     if (c->hits) (void)hipFree(c->hits);
     if (c->tile_order) (void)hipFree(c->tile_order);
     if (c->wedge_order) (void)hipFree(c->wedge_order);
@@ -1698,6 +1704,96 @@ int rto_ctx_get_stats(rto_ctx* c, void* stream_, uint64_t out[6], int reset) {
 static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const int64_t* rng_jumps, int n,
                            const rto_options* o, rto_ctx* ctx, void* stream_, int slot0);
 
+// How a point query walks `tree` and, when `values` are asked for, where a leaf's coefficients are read (rto_launch.h).  Needs no
+// device.  The walk takes whatever image is resident; child[] of a tree without one (N != 2, depth > 24) is never released.
+static int query_plan(const rto_tree* tree, bool values, int* walk, rto::ValuesSrc* vs) {
+    const rto::TreeDev& d = tree->dev;
+    *walk = d.widew ? rto::kWalkWide : d.nodew ? rto::kWalkNodew : rto::kWalkChild;
+    *vs = rto::ValuesSrc{nullptr, 0u, 0};
+    if (!values) return RTO_OK;
+    if (tree->quant)
+        return set_err(RTO_E_UNSUPPORTED, "the values of a quantised tree loaded with RTO_TREE_QUANT_DIRECT live in its codebooks: sigma, level "
+                                          "and cube can be queried, values need an expanded tree");
+    // compact records exist for leaves of positive density only, and the upload released data[]: the coefficients of the other
+    // leaves are gone (ensure_reference_arrays rebuilds them as zeros, which no ray can see)
+    if (tree->d_recidx && !(tree->flags & RTO_TREE_KEEP_REFERENCE))
+        return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps the coefficients of leaves of positive density "
+                                          "only: load it with RTO_TREE_KEEP_REFERENCE as well to query values (sigma, level and cube work)");
+    if (d.shrec && d.rec_by_entry && d.widew)
+        *vs = rto::ValuesSrc{d.shrec, (uint32_t)tree->shrec_halves, 1};
+    else if (d.shrec && !d.rec_by_entry && !d.recidx)
+        *vs = rto::ValuesSrc{d.shrec, (uint32_t)tree->shrec_halves, 0};
+    else if (d.data)  // (the uploaded array: only a tree with records ever releases it)
+        *vs = rto::ValuesSrc{d.data, (uint32_t)d.data_dim, 0};
+    else
+        return set_err(RTO_E_UNSUPPORTED, "the tree holds neither coefficient records nor data[] to answer values from");
+    return RTO_OK;
+}
+
+int rto_tree_query(const rto_tree* tree, const float* points, int64_t n, const rto_query_out* out, void* stream_) {
+    if (!tree || !out) return set_err(RTO_E_INVALID, "rto_tree_query: null tree or out");
+    if (n < 0) return set_err(RTO_E_INVALID, "rto_tree_query: n must be >= 0");
+    if (n > 0 && !points) return set_err(RTO_E_INVALID, "rto_tree_query: null points with n > 0");
+    if ((uintptr_t)out->cube % 16 != 0) return set_err(RTO_E_INVALID, "rto_tree_query: out->cube must be 16-byte aligned");
+    int walk;
+    rto::ValuesSrc vs;
+    int rc = query_plan(tree, out->values != nullptr, &walk, &vs);
+    if (rc != RTO_OK) return rc;
+    if (n == 0 || (!out->values && !out->sigma && !out->level && !out->cube)) return RTO_OK;
+    DeviceGuard guard(tree->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    const int64_t per_launch = int64_t(1) << 38;  // (2^30 workgroups of 256 points: inside the grid's 2^31 - 1)
+    for (int64_t i0 = 0; i0 < n; i0 += per_launch) {
+        rto::QueryOut qo;
+        qo.values = out->values ? out->values + i0 * tree->dev.data_dim : nullptr;
+        qo.sigma = out->sigma ? out->sigma + i0 : nullptr;
+        qo.level = out->level ? out->level + i0 : nullptr;
+        qo.cube = out->cube ? out->cube + 4 * i0 : nullptr;
+        const hipError_t e = rto::launch_query(tree->dev, walk, vs, points + 3 * i0, std::min(per_launch, n - i0), qo, (hipStream_t)stream_);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("query launch failed: ") + hipGetErrorString(e));
+    }
+    return RTO_OK;
+}
+
+// enable_probe (volrend.cu:100-134, 244-251): what a frame launch checks before it renders ...
+static int probe_check(const rto_tree* tree, const rto_options* o, const rto_ctx* ctx, bool layered) {
+    // (pinned by the suite rather than principled: the overlay would work over layers too)
+    if (layered) return set_err(RTO_E_UNSUPPORTED, "enable_probe over a context with layers (rto_ctx_set_layers) is not built");
+    if (ctx->stats_on) return set_err(RTO_E_UNSUPPORTED, "enable_probe and work counters (rto_ctx_enable_stats) do not combine");
+    if (tree->quant)
+        return set_err(RTO_E_UNSUPPORTED, "enable_probe reads a leaf's coefficients: not with a quantised tree loaded with RTO_TREE_QUANT_DIRECT");
+    if (o->probe_disp_size <= 0) return set_err(RTO_E_INVALID, "enable_probe: probe_disp_size must be > 0");
+    int walk;
+    rto::ValuesSrc vs;
+    return query_plan(tree, true, &walk, &vs);
+}
+
+// ... and what it launches behind its render kernels: the probe point's coefficients into the context's buffer, then the disc
+// over every output the launch wrote -- frame f = table[f] (device), or the one descriptor `one`
+static int draw_probe(const rto_tree* tree, const rto_options* o, rto_ctx* ctx, hipStream_t stream, const rto::FrameDesc* table,
+                      const rto::FrameDesc* one, int frames, int lean) {
+    int walk;
+    rto::ValuesSrc vs;
+    int rc = query_plan(tree, true, &walk, &vs);
+    if (rc != RTO_OK) return rc;
+    hipError_t e = rto::launch_probe_fetch(tree->dev, walk, vs, o->probe, ctx->probe_coeffs, kProbeFloats, stream);
+    if (e == hipSuccess) {
+        rto::OptDev od = make_opt_dev(o);
+        od.rot_on = 0;  // the probe's basis is evaluated at the unrotated direction (volrend.cu:114-116)
+        rto::ProbeDraw pd;
+        std::memset(&pd, 0, sizeof(pd));
+        pd.width = ctx->width;
+        pd.height = ctx->height;
+        pd.disp = o->probe_disp_size;
+        pd.lean = lean;
+        pd.table = table;
+        if (one) pd.one = *one;
+        e = rto::launch_probe_overlay(tree->dev, od, pd, frames, ctx->probe_coeffs, stream);
+    }
+    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("probe launch failed: ") + hipGetErrorString(e));
+    return RTO_OK;
+}
+
 int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_options* o, rto_ctx* ctx,
                         void* stream_) {
     if (!tree || !cam || !o || !ctx) return set_err(RTO_E_INVALID, "rto_launch_renderer: null argument");
@@ -1718,8 +1814,10 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     if (tree->d_recidx && !(o->sigma_thresh >= 0.f))
         return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps coefficient records for leaves of positive "
                                           "density only: sigma_thresh must be >= 0");
-    if (o->enable_probe)
-        return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature (volrend.cu:100-134), not on the headless path");
+    if (o->enable_probe) {
+        const int rc = probe_check(tree, o, ctx, layered);
+        if (rc != RTO_OK) return rc;
+    }
     if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
     if (!(cam->fx != 0.f) || !(cam->fy != 0.f)) return set_err(RTO_E_INVALID, "camera focal length is zero");
 
@@ -1765,8 +1863,9 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     // tree's culling cells into this camera (same bound and premises as the batched path, see launch_batch_at), and the
     // waves of unmarked 8x8 tiles write the background without ray set-up, threshold draws or marching.  The marks stay
     // on the context for the denoise stage (rto_ctx_tile_marks), like after a batched launch.
+    // (not with the probe: its disc is no background, so the launch would leave marks nobody may use)
     const bool cull_one = kernel == RTO_KERNEL_FAST && !ctx->stats_on && ctx->cull_on && ctx->cull_single && tree->dev.occ_cells &&
-                          o->sigma_thresh >= 0.f && !(tree->dev.ndc_width > 0.f);
+                          o->sigma_thresh >= 0.f && !(tree->dev.ndc_width > 0.f) && !o->enable_probe;
     if (cull_one) {
         const int tiles = ((ctx->width + 7) / 8) * ((ctx->height + 7) / 8);
         const int mask_words = (tiles + 31) / 32 + 1;
@@ -1802,6 +1901,14 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     hipError_t e = rto::launch_render(kernel, o->spp, kernel == RTO_KERNEL_FAST ? tdev : tree->dev, cd, od, ctx->rng, ctx->jump, fo,
                                       ctx->strip_rows, layered ? &layers : nullptr, stream);
     if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("render launch failed: ") + hipGetErrorString(e));
+    if (o->enable_probe) {
+        rto::FrameDesc one = {};
+        std::memcpy(one.transform, cam->transform, sizeof(one.transform));
+        one.aux = fo.aux;
+        one.image = fo.image;
+        const int rc = draw_probe(tree, o, ctx, stream, nullptr, &one, 1, 0);
+        if (rc != RTO_OK) return rc;
+    }
     // (over a colour layer an unmarked tile is not the constant background: the marks are kept from the denoise stage)
     if (cull_one && !(layered && layers.color)) {  // the selected slot's marks, for rto_ctx_tile_marks / the culled denoise stage
         ctx->marks_n = 1;
@@ -1830,7 +1937,7 @@ int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_option
     if (tree->d_recidx && !(o->sigma_thresh >= 0.f))
         return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps coefficient records for leaves of positive "
                                           "density only: sigma_thresh must be >= 0");
-    if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature, not on the headless path");
+    if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe draws into a frame's corner: caller-supplied rays have no frame");
     if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
 
     int kernel = ctx->kernel;
@@ -1914,6 +2021,14 @@ static int generic_frames(const rto_tree* tree, const rto_camera* cams, const in
         hipError_t e = rto::launch_render(RTO_KERNEL_GENERIC, o->spp, tree->dev, cd, od, rng, ctx->jump, fo, ctx->strip_rows,
                                           layered ? &layers : nullptr, (hipStream_t)stream_);
         if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("render launch failed: ") + hipGetErrorString(e));
+        if (o->enable_probe) {
+            rto::FrameDesc one = {};
+            std::memcpy(one.transform, cams[f].transform, sizeof(one.transform));
+            one.aux = fo.aux;
+            one.image = fo.image;
+            rc = draw_probe(tree, o, ctx, (hipStream_t)stream_, nullptr, &one, 1, 0);
+            if (rc != RTO_OK) return rc;
+        }
     }
     return RTO_OK;
 }
@@ -1930,10 +2045,16 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
     if (tree->d_recidx && !(o->sigma_thresh >= 0.f))
         return set_err(RTO_E_UNSUPPORTED, "a tree loaded with RTO_TREE_COMPACT_RECORDS keeps coefficient records for leaves of positive "
                                           "density only: sigma_thresh must be >= 0");
-    if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe is a GUI feature, not on the headless path");
     if (missing_lobes(tree)) return set_err(RTO_E_FORMAT, missing_lobes_msg);
     rto::LayerDev layers;
     const bool layered = ctx_layers_at(ctx, slot0, &layers);  // (batch frame f = slot slot0 + f reads plane slot0 + f)
+    if (o->enable_probe) {
+        const int rc = probe_check(tree, o, ctx, layered);
+        if (rc != RTO_OK) return rc;
+        // sparse lean outputs store nothing for unmarked tiles because those are the constant background -- the disc is not
+        if (o->denoise && ctx->lean == 2)
+            return set_err(RTO_E_UNSUPPORTED, "sparse lean outputs (rto_ctx_set_lean_outputs level 2) need a constant backdrop: not with enable_probe");
+    }
     if (layered && ctx->stats_on) return set_err(RTO_E_UNSUPPORTED, kLayersNoStats);
     if (layered && tree->quant) return set_err(RTO_E_UNSUPPORTED, kLayersNoQuant);
     // sparse lean outputs store nothing for unmarked tiles because those are the constant background -- not over a colour layer
@@ -2062,7 +2183,12 @@ static int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const i
     if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("batched render launch failed: ") + hipGetErrorString(e));
     // (over a colour layer an unmarked tile's pixels are not the constant background the marks' consumers take them for: the
     //  launch culled its marching with them, and rto_ctx_tile_marks / rto_denoise then see none)
-    ctx->marks_n = layered && layers.color ? 0 : n;
+    if (o->enable_probe) {
+        rc = draw_probe(tree, o, ctx, stream, ctx->d_frames, nullptr, n, fb.lean);
+        if (rc != RTO_OK) return rc;
+    }
+    // (... nor are the disc's pixels: a launch with the probe leaves no marks either)
+    ctx->marks_n = (layered && layers.color) || o->enable_probe ? 0 : n;
     ctx->marks_slot0 = slot0;
     ctx->marks_bg = o->background_brightness;
     if (fb.lean)

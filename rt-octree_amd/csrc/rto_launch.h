@@ -78,6 +78,41 @@ hipError_t launch_rgba8(const float* rgba, uint8_t* out, int64_t n_pixels, hipSt
 // compute it; path 0 the run-time ray_basis, 1 the per-B forms of the shading kernel (hipErrorInvalidValue where none exists)
 hipError_t launch_probe_basis(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, int path, float* out, hipStream_t stream);
 
+// ---- query_kernels.hip: rto_tree_query and the probe ----
+// which structure a point's walk descends: child[] with the reference's float descent (a tree without traversal image), the
+// one-level image (top grid + nodew), the two-level image
+constexpr int kWalkChild = 0, kWalkNodew = 1, kWalkWide = 2;
+// where the `values` of a leaf are read: half k of row r is src[r * stride + k], r = the leaf's entry of the two-level image
+// (by_entry: TreeDev::rec_by_entry records) or its slot (slot-ordered records, data[]).  src == nullptr: no values asked for
+struct ValuesSrc {
+    const uint16_t* src;
+    uint32_t stride;
+    int by_entry;
+};
+struct QueryOut {  // rto_query_out
+    float* values;
+    float* sigma;
+    int32_t* level;
+    float* cube;
+};
+// n points [n][3] (device) -> out; one thread per point, 256 per workgroup
+hipError_t launch_query(const TreeDev& tree, int walk, const ValuesSrc& vs, const float* points, int64_t n, const QueryOut& out,
+                        hipStream_t stream);
+// the probe point's leaf coefficients -> coeffs[0 .. min(data_dim - 1, cap) - 1] (retrieve_cursor_lumisphere_kernel)
+hipError_t launch_probe_fetch(const TreeDev& tree, int walk, const ValuesSrc& vs, const float point[3], float* coeffs, int cap,
+                              hipStream_t stream);
+// The probe's disc drawn over `frames` frames a launch wrote: frame f = table[f] (device memory), or the one descriptor `one`
+// (table == nullptr, frames = 1); only transform, aux and image of a descriptor are read.  lean: no aux planes.
+struct ProbeDraw {
+    int width, height;
+    int disp;  // options.probe_disp_size (> 0)
+    int lean;
+    int x0, y1;  // (set by the launcher: the probe's square clipped to the image is x >= x0, y < y1)
+    const FrameDesc* table;
+    FrameDesc one;
+};
+hipError_t launch_probe_overlay(const TreeDev& tree, const OptDev& opt, ProbeDraw pd, int frames, const float* coeffs, hipStream_t stream);
+
 #ifdef RTO_DBG_COUNTERS
 hipError_t debug_shade_phases(unsigned long long* out16, bool reset);  // tools/dbg_shade_phases.py
 #endif

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COptions, CRays, CTreeInfo, RtoError, check, lib
+from ._lib import CCamera, COptions, CQueryOut, CRays, CTreeInfo, RtoError, check, lib
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
@@ -187,6 +187,35 @@ class N3Tree:
         """main_headless.cpp:400-405: tree.use_ndc = true; ndc_width/height/focal."""
         check(lib().rto_tree_set_ndc(self._h, float(width), float(height), float(focal)))
         self._refresh()
+
+    def query(self, points, values=True, sigma=False, level=False, cube=False, stream=None):
+        """rto_tree_query: what the tree holds at `points`, a contiguous float32 CUDA tensor [n, 3] in world space on the tree's
+        device (a numpy array is copied over).  Returns a dict of torch tensors on that device with the outputs asked for:
+        "values" [n, data_dim] float32 (the leaf's data[] row, last = sigma), "sigma" [n], "level" [n] int32 (-1: a point with a
+        non-finite coordinate, which is not answered: zeros elsewhere), "cube" [n, 4] (the leaf's min corner in tree coordinates
+        and its side).  No NDC warp is applied.  Asynchronous on `stream` (default: torch's current stream); no sync."""
+        import torch
+        device = torch.device("cuda", self.device)
+        if not hasattr(points, "shape") or len(points.shape) != 2:
+            raise RtoError(-1, "points must be a contiguous float32 tensor of shape [n, 3]")
+        n = int(points.shape[0])
+        pts = _ray_tensor(points, "points", 3, n, device)
+        res = {}
+        if values:
+            res["values"] = torch.empty((n, self.data_dim), dtype=torch.float32, device=device)
+        if sigma:
+            res["sigma"] = torch.empty((n,), dtype=torch.float32, device=device)
+        if level:
+            res["level"] = torch.empty((n,), dtype=torch.int32, device=device)
+        if cube:
+            res["cube"] = torch.empty((n, 4), dtype=torch.float32, device=device)
+        q = CQueryOut()
+        for k, t in res.items():
+            setattr(q, k, t.data_ptr() if n > 0 else None)
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        check(lib().rto_tree_query(self._h, C.c_void_p(pts.data_ptr()) if n > 0 else None, n, C.byref(q), _stream_ptr(stream)))
+        return res
 
     def is_data_loaded(self):
         return bool(self._h)
