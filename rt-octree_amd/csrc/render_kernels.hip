@@ -20,7 +20,7 @@
 //                        ray compaction, one ray queue per XCD; sample_kernel before it (thresholds)
 //                        and shade_kernel after it (SH colour + pixel epilogue).
 // Since round 4 render_fast and render_persist walk the TWO-LEVEL traversal image when the tree has one
-// (TreeDev::widew, rto_abi.cpp build_wide_image): top-grid cells and nodes merged with their eight children in
+// (TreeDev::widew, host/tree_layout.cpp build_wide_image): top-grid cells and nodes merged with their eight children in
 // ONE array, so that a node visit is one uniform 4-byte load resolving two levels; a ray's hit entries name
 // entries of that image, wait in LDS while it marches and are translated to leaf slots and written once, when
 // it has ended (flush_hits).  The one-level image (nodew + topgrid) serves the counting instantiation and trees
@@ -380,7 +380,7 @@ __global__ void build_shrec_kernel(const uint16_t* __restrict__ data, int64_t n_
     out[dst * rec + k] = k < data_dim - 1 ? data[slot * data_dim + k] : (uint16_t)0;
 }
 
-// The reference-layout arrays back from the derived ones (rto_abi.cpp ensure_reference_arrays): a tree that renders through
+// The reference-layout arrays back from the derived ones (rto_tree.cpp ensure_reference_arrays): a tree that renders through
 // the fast / batched kernels keeps only nodew + shrec resident; the generic kernel's child[] / data[] are rebuilt on
 // first use.  Leaf slots get their exact fp16 values back (coefficients from shrec, sigma from the leaf word); an
 // internal slot's sigma -- which no query ever returns -- becomes 0.
@@ -1603,7 +1603,7 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     // 10.6 / 8.8 / 7.8 / 7.35 ms per 100 frames -- round 2's "4 to 8 waves within 2 %" compared __launch_bounds__ hints,
     // which change the register budget, not the number of resident waves).
     // The two-level traversal image when the tree has one (always, unless it would not fit its index space or the device's
-    // memory: rto_abi.cpp build_wide_image), else the one-level image: the same pixels either way.
+    // memory: host/tree_layout.cpp build_wide_image), else the one-level image: the same pixels either way.
     // (Round 5's reservoir kernel -- whole-tile set-up, rays parked in LDS, refill rounds at 8-24 idle lanes -- lost its same-box
     //  A/B, 4.27-4.32 against 4.11-4.20 ms per 100 C2 frames, and lives in tools/experiments/r5_lab_switches.patch.)
     if (layers) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "rto_device_math.h"
+#include "rto_tree_bits.h"
 
 namespace rto {
 
@@ -11,16 +12,8 @@ namespace rto {
 // TreeDev::format (= RTO_FMT_* of rto.h, data_format.hpp:8-14)
 constexpr int kFmtRGBA = 0, kFmtSH = 1, kFmtSG = 2, kFmtASG = 3;
 
-// Leaf tag of the traversal image `nodew` (see build_nodew_kernel in render_kernels.hip):
-//   internal slot: the reference's child[] value (relative node offset, |v| < 2^30)
-//   leaf slot:     0x80000000 | fp16 bits of the slot's sigma  -> top two bits are 0b10
-constexpr uint32_t kLeafTag = 0x80000000u;
-// A leaf word of the TWO-LEVEL image also carries its leaf's level (< 32), at the bits a float's exponent field starts at:
-// the march step's 2^(level + c) factors are then one integer add / subtract on (word & kWideLevelMask) -- no field extract
-constexpr int kWideLevelShift = 23;
-constexpr uint32_t kWideLevelMask = 31u << kWideLevelShift;
+// (kLeafTag, kWideLevelShift / kWideLevelMask, kOccLevel, kGridSlotBits / kGridSlotMask and nodew_is_leaf: rto_tree_bits.h)
 constexpr int kQueueChunk = 256;  // tile slots per workgroup of the queue compaction
-constexpr int kOccLevel = 7;  // finest cube of the culling cells: 2^-7 of the volume (6 pixels across at 800 x 800)
 constexpr uint32_t kNoRecord = 0xffffffffu;  // TreeDev::recidx entry of a slot without a coefficient record
 
 // Bit budgets of the packed words.  A top-grid entry is {slot | level << kGridSlotBits, word}: the level is < 8 (the
@@ -31,12 +24,9 @@ constexpr uint32_t kNoRecord = 0xffffffffu;  // TreeDev::recidx entry of a slot 
 // kHitValid: the hand-off buffer holds a pixel's sorted thresholds (non-negative floats: top bit clear) until the
 // traversal overwrites the first entries with its hit list, so the first word with a clear top bit ends the list --
 // no terminator is ever written (round 1 wrote one scattered dword per ray: most of the kernel's HBM writes).
-constexpr int kGridSlotBits = 29;
-constexpr uint32_t kGridSlotMask = (1u << kGridSlotBits) - 1u;
 __host__ __device__ constexpr int hit_slot_bits(int spp) {
     return spp <= 1 ? 31 : spp <= 2 ? 30 : spp <= 4 ? 29 : spp <= 8 ? 28 : spp <= 16 ? 27 : 26;
 }
-__host__ __device__ inline bool nodew_is_leaf(uint32_t w) { return (w >> 30) == 2u; }
 
 struct TreeDev {
     const uint16_t* data;   // fp16 bits [capacity*N3*data_dim]   (reference tree.data)
@@ -54,7 +44,7 @@ struct TreeDev {
     // above level G costs this one 8-byte, L2-resident load.  nullptr / 0 when absent.
     const uint2* topgrid;
     int top_levels;
-    // Two-level traversal image (rto_abi.cpp build_wide_image; nullptr: absent).  ONE array: entries [0, 8^G) are the top-grid
+    // Two-level traversal image (host/tree_layout.cpp build_wide_image; nullptr: absent).  ONE array: entries [0, 8^G) are the top-grid
     // cells, padded to wide_grid_nodes nodes of 64; wide node k is node wide_grid_nodes + k.  Entry of a node: index
     // (x2 << 4 | y2 << 2 | z2), two bits per axis; of the grid: (x << 2G | y << G | z).  A word: leaf = kLeafTag | level << kWideLevelShift |
     // sigma fp16, internal = the NODE NUMBER of the wide node below (two levels down; from the grid: the level-G node's).  An

@@ -160,7 +160,7 @@
                 (void)have_w;
                 (void)stk1;
             } else if constexpr (WIDE) {
-                // the two-level image (rto_abi.cpp build_wide_image; round 4): one load per TWO levels below the grid -- a lone
+                // the two-level image (host/tree_layout.cpp build_wide_image; round 4): one load per TWO levels below the grid -- a lone
                 // frame waits for the dependent-load chains of its longest rays, and this shortens every one of them
                 // (node, off): (0, 24 - G) = the top grid, whose cells are indexed by G bits per axis; else the wide node of the
                 // pair (G + 2 pr, G + 2 pr + 1), two bits per axis from bit 22 - G - 2 pr on.  One array holds both.

@@ -42,7 +42,7 @@
     // Loop-invariant scalars pinned in SGPRs: hipcc otherwise re-loads them from the kernarg segment inside the descent loop (an s_load +
     // lgkmcnt(0) round trip per level).
     typedef const __attribute__((address_space(1))) uint32_t* gptr_t;  // keep global_load (not flat_load)
-    // WIDE: the two-level image and its top grid (rto_abi.cpp build_wide_image) instead of the one-level ones
+    // WIDE: the two-level image and its top grid (host/tree_layout.cpp build_wide_image) instead of the one-level ones
     const uint32_t* nodew_p = WIDE ? tree.widew : tree.nodew;
     const uint2* topgrid_p = tree.topgrid;  // (WIDE: unused -- the grid cells are the first entries of the two-level image)
     const uint32_t* __restrict__ qlist = fb.qlist;
@@ -249,7 +249,7 @@
                 RTO_DBG_AT(0)
                 uint32_t slot, w;
                 if constexpr (WIDE) {
-                    // Round 4: ONE array holds the top grid and the two-level ("wide") nodes below it (rto_abi.cpp
+                    // Round 4: ONE array holds the top grid and the two-level ("wide") nodes below it (host/tree_layout.cpp
                     // build_wide_image), so a node visit is ONE uniform load: entry = ((node << b | x bits) << b | y bits) << b |
                     // z bits, b bits per axis from bit rs.woff on -- (node, b, woff) = (0, G, 24 - G) at the grid,
                     // (node number, 2, 22 - G - 2 p) at the wide node of the levels (G + 2p, G + 2p + 1).  v_bfe_u32 and

@@ -1,4 +1,4 @@
-"""The two-level ("wide") traversal image of the batched kernel (round 4; rt-octree_amd/csrc/rto_abi.cpp build_wide_image):
+"""The two-level ("wide") traversal image of the batched kernel (round 4; rt-octree_amd/csrc/host/tree_layout.cpp build_wide_image):
 derived data -- for every point the leaf it answers with (level, slot, sigma) must be the one the plain root walk over
 child[] finds (n3tree_query.hpp:22-47).  Host-only probe of the C ABI: runs without a GPU."""
 import ctypes as C
