@@ -340,9 +340,34 @@ void orc_sh_basis(int basis_dim, const float dir[3], float out[ORC_BASIS_MAX]) {
     }
 }
 
+/* ------------------------------------------------------------------ SG / ASG basis */
+/* cuda/common.cuh:46-51 */
+static inline float v_dot3(const float* u, const float* v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; }
+
+/* internal/lumisphere.hpp:14-37.  The reference's expf is the library's full-range definition here (DESIGN.md
+ * section 7a), as __expf is below; `/ basis_dim` divides by the int converted to float. */
+void orc_lobe_basis(int format, int basis_dim, const float* extra, const float dir[3], float out[ORC_BASIS_MAX]) {
+    const float* ptr = extra;
+    if (format == ORC_FMT_ASG) {
+        for (int i = 0; i < basis_dim && i < ORC_BASIS_MAX; ++i) {
+            const float *ptr_mu_x = ptr + 2, *ptr_mu_y = ptr + 5, *ptr_mu_z = ptr + 8;
+            float S = v_dot3(dir, ptr_mu_z);
+            float dot_x = v_dot3(dir, ptr_mu_x);
+            float dot_y = v_dot3(dir, ptr_mu_y);
+            out[i] = S * m_expf(-ptr[0] * dot_x * dot_x - ptr[1] * dot_y * dot_y) / basis_dim;
+            ptr += 11;
+        }
+    } else if (format == ORC_FMT_SG) {
+        for (int i = 0; i < basis_dim && i < ORC_BASIS_MAX; ++i) {
+            out[i] = m_expf(ptr[0] * (v_dot3(dir, ptr + 1) - 1.f)) / basis_dim;
+            ptr += 4;
+        }
+    }
+}
+
 /* ------------------------------------------------------------------ trace_ray */
-/* cuda/rt_core.cuh:195-332.  returns 0, or -1 for an unsupported format (SG/ASG: lumisphere.hpp
- * :14-37 "UNTESTED", out of scope per SURVEY section 2 #4). */
+/* cuda/rt_core.cuh:195-332.  returns 0, or -1 for an SG / ASG tree without lobes (the reference would read a null
+ * pointer). */
 int orc_trace_ray(const orc_tree* tree, float dir[3], const float vdir[3], const float cen[3],
                   const orc_options* opt, float tmax_bg, float out[4], orc_pcg32* rng,
                   orc_stats* st) {
@@ -438,6 +463,9 @@ int orc_trace_ray(const orc_tree* tree, float dir[3], const float vdir[3], const
     memset(basis_fn, 0, sizeof(basis_fn)); /* reference leaves k>=basis_dim uninitialised; never read */
     if (tree->format == ORC_FMT_SH) {
         orc_sh_basis(basis_dim, vdir, basis_fn); /* :278 */
+    } else if (tree->format == ORC_FMT_SG || tree->format == ORC_FMT_ASG) {
+        if (!tree->extra) return -1;
+        orc_lobe_basis(tree->format, basis_dim, tree->extra, vdir, basis_fn);
     } else if (tree->format != ORC_FMT_RGBA) {
         return -1;
     }
@@ -474,7 +502,10 @@ int orc_trace_ray(const orc_tree* tree, float dir[3], const float vdir[3], const
             }
 #undef MUL_BASIS_I
         } else {
-            for (int j = 0; j < 3; ++j) out[j] += orc_half2float(tv[j]) * cnts[i]; /* :319-321 */
+            /* :319-321.  DELIBERATE DEVIATION: the reference's `tree_val` here is the function's variable (:225), the
+             * leaf queried last, not tree_vals[i] (that declaration, :289, is local to the SH branch); entry i is
+             * shaded from its own leaf (tests/test_reference_kat.py). */
+            for (int j = 0; j < 3; ++j) out[j] += orc_half2float(tv[j]) * cnts[i];
         }
         out[3] += cnts[i];
     }

@@ -11,10 +11,12 @@
  *   - sample_dst:   PINNED against the SURVEY.md section 8c G2 known-answer vector (libm math mode).
  *   - npz reading:  PINNED against the reference's vendored cnpy (oracle/ref_kat, tests/golden/npz_*).
  *   - GuidanceNet:  PINNED against the imported reference module (tests/golden/guidance_*.npz).
- *   - trace_ray / render_kernel / filter:  PARITY UNPINNED by execution.  The reference's
- *     rt_core.cuh / volrend.cu / filtering.cu need cuda_runtime.h, cuda_fp16.h, a cmake-generated
- *     volrend/common.hpp and libtorch: unbuildable in this image without stand-ins, which the
- *     build rules forbid.  These functions are literal restatements, each citing file:line.
+ *   - query / SH, SG, ASG basis / sample_dst / trace_ray:  PINNED against the reference's own rt_core.cuh,
+ *     n3tree_query.hpp and lumisphere.hpp compiled on the host behind stand-in CUDA headers
+ *     (oracle/ref_kat/rt_core_kat.cpp; vectors in tests/golden/ref_rt_core.npz, tests/test_reference_kat.py).
+ *     One deliberate deviation: the colour of an RGBA tree's hit entries (see orc_trace_ray).
+ *   - render_kernel's per-pixel wrapper / NDC warp / rodrigues / filter:  literal restatements, each citing
+ *     file:line (volrend.cu and filtering.cu cannot be compiled on the host).
  *
  * Math modes: the reference calls the NVIDIA approximations __logf/__expf (rt_core.cuh:74,95,314;
  * filtering.cu:191) whose bit patterns cannot be reproduced off NVIDIA hardware.  The oracle
@@ -55,6 +57,7 @@ typedef struct {
     float ndc_width; /* <=0: NDC off (data_spec.hpp:49) */
     float ndc_height;
     float ndc_focal;
+    const float* extra; /* SG / ASG lobes (TreeSpec::extra): [basis_dim][4] / [basis_dim][11]; NULL otherwise */
 } orc_tree;
 
 /* render_options.hpp:13-78, the fields the offscreen kernel reads */
@@ -110,6 +113,8 @@ void orc_math_sweep(int fn, uint32_t first_bits, uint32_t stride, uint32_t count
 /* returns leaf slot index (sub_ptr); xyz becomes leaf-local; *cube_sz = N^depth */
 int64_t orc_query(const orc_tree* t, float xyz[3], float* cube_sz, int* levels);
 void orc_sh_basis(int basis_dim, const float dir[3], float out[ORC_BASIS_MAX]);
+/* SG / ASG lobes (lumisphere.hpp:14-37); expf follows the math mode */
+void orc_lobe_basis(int format, int basis_dim, const float* extra, const float dir[3], float out[ORC_BASIS_MAX]);
 int orc_trace_ray(const orc_tree* t, float dir[3], const float vdir[3], const float cen[3],
                   const orc_options* opt, float tmax_bg, float out[4], orc_pcg32* rng,
                   orc_stats* st);

@@ -181,8 +181,391 @@ def kat_golden():
     print("kat_golden.npz: %d arrays" % len(out))
 
 
+# ------------------------------------------------------------------ ref_rt_core.npz: the reference's ray core, executed
+REF_SPPS = (1, 2, 3, 4, 6, 8, 16, 32)
+REF_FORMATS = {"RGBA": 0, "SH": 1, "SG": 2, "ASG": 3}
+
+
+def _hand_tree(rs, data_format, nodes, depth, scale, offset, sigmas, dense=0.4, lobes=None):
+    """A small octree written out by hand: the root splits, one chain of cells splits down to `depth`, the other splits are
+    drawn until `nodes` nodes exist.  child[node, i, j, k] = (child node) - node, 0 for a leaf (n3tree_query.hpp:36-46).
+    A fraction `dense` of the leaves takes a density from `sigmas` and random coefficients; the others are all zero."""
+    alpha = "".join(c for c in data_format if c.isalpha())
+    basis = int(data_format[len(alpha):]) if alpha != "RGBA" else -1
+    dd = 4 if basis < 0 else 3 * basis + 1
+    child = [np.zeros(8, np.int32)]
+    level = [1]
+    open_slots = [(0, s, 1) for s in range(8)]  # (node, slot, level of the cells of that node)
+    chain = (0, int(rs.randint(8)), 1)
+    while len(child) < nodes:
+        if chain is not None and chain[2] < depth:
+            node, slot, lv = chain
+        else:
+            cand = [c for c in open_slots if c[2] < depth - 1]
+            if not cand:
+                break
+            node, slot, lv = cand[rs.randint(len(cand))]
+        open_slots.remove((node, slot, lv))
+        new = len(child)
+        child.append(np.zeros(8, np.int32))
+        level.append(lv + 1)
+        child[node][slot] = new - node
+        open_slots += [(new, s, lv + 1) for s in range(8)]
+        if chain is not None and (node, slot, lv) == chain:
+            chain = (new, int(rs.randint(8)), lv + 1) if lv + 1 < depth else None
+    child = np.stack(child).reshape(-1, 2, 2, 2)
+    cap = child.shape[0]
+    data = np.zeros((cap * 8, dd), np.float16)
+    leaves = np.flatnonzero(child.reshape(-1) == 0)
+    lit = leaves[rs.rand(leaves.size) < dense]
+    data[lit, :dd - 1] = (rs.randn(lit.size, dd - 1) * (0.5 if basis < 0 else 1.5)).astype(np.float16)
+    data[lit, dd - 1] = np.asarray(sigmas, np.float16)[rs.randint(len(sigmas), size=lit.size)]
+    # the leaves of the first two levels are the thick ones: make sure some of them are dense
+    big = [s for s in leaves if level[s // 8] <= 2]
+    for s in big[::2]:
+        data[s, :dd - 1] = (rs.randn(dd - 1) * (0.5 if basis < 0 else 1.5)).astype(np.float16)
+        data[s, dd - 1] = np.float16(sigmas[s % len(sigmas)])
+    return dict(child=child, data=data.reshape(cap, 2, 2, 2, dd), scale=np.asarray(scale, np.float32),
+                offset=np.asarray(offset, np.float32), data_format=data_format,
+                fmt=np.array([REF_FORMATS[alpha], basis], np.int32), extra=lobes)
+
+
+def _leaf_cells(tree):
+    """[(slot, min corner (3,), side, sigma)] of every leaf, in tree coordinates (float64)"""
+    child = tree["child"].reshape(-1)
+    sig = tree["data"].reshape(child.size, -1)[:, -1].astype(np.float64)
+    out = []
+
+    def walk(node, corner, side):
+        for s in range(8):
+            c = corner + side * np.array([(s >> 2) & 1, (s >> 1) & 1, s & 1], np.float64)  # index = (i * N + j) * N + k
+            slot = node * 8 + s
+            if child[slot] == 0:
+                out.append((slot, c, side, sig[slot]))
+            else:
+                walk(node + child[slot], c, side / 2)
+    walk(0, np.zeros(3), 0.5)
+    return out
+
+
+def _to_world(tree, p):
+    """world points whose float32 image offset + scale * w is the tree coordinate p where one exists among the neighbours of
+    the float64 solution (the nearest otherwise)"""
+    f32 = np.float32
+    p = np.asarray(p, f32)
+    sc, of = tree["scale"], tree["offset"]
+    w = ((p.astype(np.float64) - of) / sc).astype(f32)
+    best, ok = w.copy(), np.zeros(p.shape, bool)
+    for step in range(-3, 4):
+        cand = w.copy()
+        for _ in range(abs(step)):
+            cand = np.nextafter(cand, f32(np.inf if step > 0 else -np.inf))
+        hit = ((of + (sc * cand).astype(f32)).astype(f32) == p) & ~ok
+        best[hit] = cand[hit]
+        ok |= hit
+    return best
+
+
+def _ref_rays(tree, rs, n_random):
+    """World-space rays (origins, raw directions, t_max) of every class the fixture must hold; see the README of the classes in
+    tests/test_reference_kat.py.  Origins are chosen in tree coordinates and mapped to the world."""
+    f32 = np.float32
+    cells = _leaf_cells(tree)
+    dense = [c for c in cells if c[3] > 0.02]
+    empty = [c for c in cells if c[3] == 0]
+    thick = sorted(dense, key=lambda c: -c[2])[:4]
+    O, D, T = [], [], []
+
+    def add(o, d, t=1e9):
+        O.append(np.asarray(o, np.float64))
+        D.append(np.asarray(d, np.float64))
+        T.append(t)
+
+    def sphere(r=1.6):
+        v = rs.randn(3)
+        return 0.5 + r * v / np.linalg.norm(v)
+    # hits (aimed at a point of the volume) and misses (aimed past it, or away from it)
+    for i in range(n_random):
+        o = sphere()
+        add(o, (rs.rand(3) - o) * rs.uniform(0.2, 5.0))
+    for i in range(max(8, n_random // 6)):
+        o = sphere()
+        add(o, (0.5 + 1.5 * rs.randn(3) / 1.0) - o if i % 2 else o - 0.5)
+    # origin inside the box; origin inside a dense leaf
+    for i in range(12):
+        add(rs.uniform(0.02, 0.98, 3), rs.randn(3))
+    for c in (thick + dense)[:12]:
+        add(c[1] + c[2] * rs.uniform(0.2, 0.8, 3), rs.randn(3))
+    # through the thick dense leaves, from outside (several samples in one leaf at SPP 16 / 32)
+    for c in thick:
+        for _ in range(4):
+            o = sphere()
+            add(o, (c[1] + c[2] * rs.uniform(0.3, 0.7, 3)) - o)
+    # in a face (outer faces and the inner ones at 1/2, 1/4), along an edge, through corners shared by several leaves
+    for ax in range(3):
+        for plane in (0.0, 1.0, 0.5, 0.25, 0.75):
+            for zero in (0.0, -0.0):
+                o = rs.uniform(0.1, 0.9, 3)
+                o[ax] = plane
+                o[(ax + 1) % 3] = -0.75
+                d = rs.uniform(0.2, 1.0, 3)
+                d[ax] = zero
+                add(o, d)
+        for a, b in ((0.5, 0.5), (0.25, 0.5), (0.0, 1.0), (0.75, 0.75)):
+            o = np.zeros(3)
+            o[ax], o[(ax + 1) % 3], o[(ax + 2) % 3] = -0.5, a, b
+            d = np.zeros(3)
+            d[ax] = 1.0
+            add(o, d)
+            d2 = d.copy()
+            d2[(ax + 1) % 3] = -0.0
+            add(o + np.array([2.0 if k == ax else 0 for k in range(3)]), -d2)
+    for corner in ((0.5, 0.5, 0.5), (0.25, 0.5, 0.75), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (0.5, 0.25, 0.25)):
+        for sgn in ((1, 1, 1), (1, -1, 1), (-1, -1, -1), (1, 1, -1)):
+            s = np.array(sgn, np.float64)
+            add(np.array(corner) - 0.75 * s, s * 3.0)
+    # direction components 0, -0, +-1e-9f (dir + 1e-9 cancels), +-1e-10f: beside one or two dominant components
+    tiny = [0.0, -0.0, f32(1e-9), -f32(1e-9), f32(1e-10), -f32(1e-10)]
+    for ax in range(3):
+        for t1 in tiny:
+            for sgn in (1.0, -1.0):
+                d = np.zeros(3)
+                d[ax] = sgn
+                d[(ax + 1) % 3] = t1
+                d[(ax + 2) % 3] = tiny[(tiny.index(t1) + 3) % 6] if sgn > 0 else 0.0
+                o = rs.uniform(0.1, 0.9, 3)
+                o[ax] = 0.5 - 1.25 * sgn
+                add(o, d)
+        for t1 in tiny:
+            d = np.array([0.6, 0.8, 0.0])
+            d = np.roll(d, ax)
+            d[(ax + 2) % 3] = t1
+            add(rs.uniform(0.3, 0.7, 3) - 1.5 * d, d)
+    rows = len(O)
+    O, D = np.array(O), np.array(D, np.float64)
+    ow = _to_world(tree, O.astype(f32))
+    # a direction chosen in tree coordinates becomes world units (the kernel multiplies by scale again); the tiny components
+    # keep their value: with one dominant axis and an isotropic scale they reach the `+ 1e-9` unchanged
+    sc = tree["scale"].astype(np.float64)
+    iso = bool(sc[0] == sc[1] == sc[2])
+    dw = (D if iso else D / sc * sc.mean()).astype(f32)
+    dw[D == 0] = D[D == 0].astype(f32)  # (keeps the sign of a zero)
+    tm = np.array(T, f32)
+    # depth limits: inside a dense leaf, in an empty gap, below tmin, (the default 1e9 above)
+    extra_o, extra_d, extra_t = [], [], []
+    for kind, pool in (("leaf", dense), ("gap", empty)):
+        for c in [pool[i] for i in rs.permutation(len(pool))[:10]]:
+            o = _to_world(tree, sphere().astype(f32)[None])[0]
+            target = _to_world(tree, (c[1] + c[2] * rs.uniform(0.3, 0.7, 3)).astype(f32)[None])[0]
+            d = target.astype(np.float64) - o
+            extra_o.append(o)
+            extra_d.append((d * rs.uniform(0.3, 3.0)).astype(f32))
+            extra_t.append(f32(np.linalg.norm(d)))
+    for i in range(8):  # below tmin: the box starts farther away than the limit
+        o = _to_world(tree, sphere(2.0).astype(f32)[None])[0]
+        target = _to_world(tree, rs.uniform(0.3, 0.7, 3).astype(f32)[None])[0]
+        d = target.astype(np.float64) - o
+        extra_o.append(o)
+        extra_d.append(d.astype(f32))
+        extra_t.append(f32(np.linalg.norm(d) * rs.uniform(0.05, 0.3)))
+    ow = np.concatenate([ow, np.array(extra_o, f32)])
+    dw = np.concatenate([dw, np.array(extra_d, f32)])
+    tm = np.concatenate([tm, np.array(extra_t, f32)])
+    assert np.isfinite(ow).all() and np.isfinite(dw).all() and (dw != 0).any(1).all() and (tm > 0).all()
+    return ow, dw, tm, rows
+
+
+def _ref_query_points(tree, rs, n_random):
+    """query points, tree coordinates mapped to the world: faces, edges and corners of cells, 0, 1 - 1e-6f, outside [0, 1)"""
+    f32 = np.float32
+    edge = f32(1.0) - f32(1e-6)
+    vals = [0.0, -0.0, 1.0, edge, np.nextafter(edge, f32(0)), np.nextafter(edge, f32(2)), np.nextafter(f32(1), f32(0)),
+            -0.1, 1.3, -3.0, 7.0, 1e-30]
+    for d in range(1, 7):
+        for k in rs.choice(np.arange(1, 2 ** d), size=min(3, 2 ** d - 1), replace=False):
+            b = f32(k / 2.0 ** d)
+            vals += [b, np.nextafter(b, f32(0)), np.nextafter(b, f32(2))]
+    vals = np.array(vals, f32)
+    rows = [rs.rand(n_random, 3).astype(f32)]
+    for ax in range(3):  # one special coordinate (a face)
+        p = rs.rand(vals.size, 3).astype(f32)
+        p[:, ax] = vals
+        rows.append(p)
+    p = rs.rand(vals.size, 3).astype(f32)  # two (an edge)
+    p[:, 0], p[:, 2] = vals, vals[::-1]
+    rows.append(p)
+    rows.append(np.stack([vals, np.roll(vals, 5), vals[::-1]], 1))  # three (a corner)
+    return _to_world(tree, np.concatenate(rows))
+
+
+def _ref_dirs(rs, n_random):
+    f32 = np.float32
+    d = rs.randn(n_random, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    axes = np.concatenate([np.eye(3), -np.eye(3)])
+    diag = np.array([[1, 1, 0], [0, -1, 1], [1, 1, 1], [-1, 1, -1], [0.6, 0.8, 0.0], [0.0, -0.0, 1.0]], np.float64)
+    diag /= np.linalg.norm(diag, axis=1, keepdims=True)
+    return np.concatenate([axes, diag, d]).astype(f32)
+
+
+def read_kat_tables(path):
+    """the records rt_core_kat writes: `name dtype count\\n` + raw little-endian values"""
+    b = open(path, "rb").read()
+    pos, out = 0, {}
+    while pos < len(b):
+        nl = b.index(b"\n", pos)
+        name, dt, cnt = b[pos:nl].decode().split()
+        a = np.frombuffer(b, np.dtype("<" + dt), int(cnt), nl + 1)
+        out[name] = a.copy()
+        pos = nl + 1 + a.nbytes
+    return out
+
+
+def _pcg32_jump(state, inc, delta):
+    """pcg32::advance (pcg32.h:145-166) in Python integers"""
+    M = (1 << 64) - 1
+    cur_mult, cur_plus, acc_mult, acc_plus = 0x5851f42d4c957f2d, inc, 1, 0
+    delta &= M
+    while delta > 0:
+        if delta & 1:
+            acc_mult = (acc_mult * cur_mult) & M
+            acc_plus = (acc_plus * cur_mult + cur_plus) & M
+        cur_plus = ((cur_mult + 1) * cur_plus) & M
+        cur_mult = (cur_mult * cur_mult) & M
+        delta >>= 1
+    return (acc_mult * state + acc_plus) & M
+
+
+def kat_states_to_draws(res):
+    """trace<SPP>_state (the RNG state after ray i, which started at base advanced by i * SPP) -> trace<SPP>_draws, the number
+    of draws that ray consumed (uint8); a state that no count 0..SPP reaches is an error.  Everything else is passed on."""
+    base = json.load(open(os.path.join(HERE, "pcg32_kat.json")))
+    state0, inc = int(base["state0"], 16), int(base["inc"], 16)
+    out = {}
+    for k, v in res.items():
+        if not (k.startswith("trace") and k.endswith("_state")):
+            out[k] = v
+            continue
+        spp = int(k[5:-6])
+        draws = np.zeros(v.size, np.uint8)
+        for i, s in enumerate(v.tolist()):
+            cand = [c for c in (0, spp) if _pcg32_jump(state0, inc, i * spp + c) == s]
+            if not cand:
+                cand = [c for c in range(spp + 1) if _pcg32_jump(state0, inc, i * spp + c) == s]
+            assert cand, (k, i)
+            draws[i] = cand[0]
+        out[k[:-6] + "_draws"] = draws
+    return out
+
+
+def write_kat_case(path, tree, case):
+    """one case file of rt_core_kat: tree arrays, options, points, directions, rays"""
+    kw = dict(child=tree["child"], data=tree["data"].view(np.uint16), scale=tree["scale"], offset=tree["offset"], fmt=tree["fmt"],
+              optf=case["optf"], opti=case["opti"])
+    if tree["extra"] is not None:
+        kw["extra"] = tree["extra"]
+    for k in ("qpts", "bdirs", "origins", "dirs", "tmax"):
+        if k in case:
+            kw[k] = case[k]
+    np.savez(path, **kw)
+
+
+def ref_rt_core():
+    """tests/golden/ref_rt_core.npz: trees, inputs and what the REFERENCE's own query_single_from_root, maybe_precalc_basis,
+    sample_dst and trace_ray return for them, run on the host by oracle/_ref/rt_core_kat (oracle/ref_kat/Makefile)."""
+    import tempfile
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle", "ref_kat"), "-s"])
+    exe = os.path.join(ROOT, "oracle", "_ref", "rt_core_kat")
+    rs = np.random.RandomState(20240611)
+    f32 = np.float32
+    h = lambda bits: np.array([bits], np.uint16).view(np.float16)[0]
+    mix = [0.5, 2.0, 8.0, 40.0, 300.0]
+    third = f32(1.0 / 3.0)
+
+    def unit(n):
+        v = rs.randn(n, 3)
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+    sg = np.concatenate([np.array([0, 0.5, 3, 12, 40, 150, 600, 2000, 5], np.float64)[:, None], unit(9)], 1).astype(f32)
+    asg = np.zeros((4, 11), f32)
+    asg[:, 0], asg[:, 1] = [0.0, 4.0, 60.0, 900.0], [2.0, 0.5, 700.0, 30.0]
+    for i in range(4):
+        z = unit(1)[0]
+        x = np.cross(z, [0.3, -0.5, 0.8])
+        x /= np.linalg.norm(x)
+        asg[i, 2:5], asg[i, 5:8], asg[i, 8:11] = x, np.cross(z, x), z
+    # the halves on both sides of the two thresholds used: 1e-2f lies between 0x211e and 0x211f; 0.5 is a half itself
+    lo, hi = h(0x211e), h(0x211f)
+    assert f32(lo) < f32(1e-2) < f32(hi)
+    around = [lo, hi, h(0x211d), h(0x2120), h(0x37ff), h(0x3800), h(0x3801), np.float16(0.25), np.float16(3.0), np.float16(30.0)]
+    trees = {
+        "sh9": _hand_tree(rs, "SH9", 150, 6, [0.5] * 3, [0.5] * 3, mix),
+        "sh16": _hand_tree(rs, "SH16", 70, 6, [third] * 3, [0.5] * 3, mix),
+        "sh25": _hand_tree(rs, "SH25", 40, 6, [third] * 3, [0.5] * 3, mix),
+        "sh4": _hand_tree(rs, "SH4", 160, 7, [0.25] * 3, [0.5] * 3, mix),
+        "rgba": _hand_tree(rs, "RGBA", 220, 7, [third] * 3, [0.5] * 3, mix),
+        "sg9": _hand_tree(rs, "SG9", 60, 6, [0.5] * 3, [0.5] * 3, mix, lobes=sg),
+        "asg4": _hand_tree(rs, "ASG4", 80, 6, [third] * 3, [0.5] * 3, mix, lobes=asg),
+        "aniso": _hand_tree(rs, "SH9", 90, 6, [0.31, 0.47, 0.23], [0.42, 0.61, 0.37], mix),
+        "thresh": _hand_tree(rs, "SH4", 120, 6, [0.5] * 3, [0.5] * 3, around, dense=0.8),
+    }
+    default = dict(step_size=1e-4, sigma_thresh=1e-2, bbox=[0, 0, 0, 1, 1, 1], minmax=[0, 24])
+    cases = [(name, name, {}, 60) for name in trees]
+    cases += [("sh9.step", "sh9", dict(step_size=0.03), 40),
+              ("sh16.crop", "sh16", dict(bbox=[0.125, 0.0, 0.3, 0.8, 0.75, 1.0]), 40),
+              ("sh9.mask", "sh9", dict(minmax=[1, 6]), 30),
+              ("thresh.raised", "thresh", dict(sigma_thresh=0.5), 60)]
+    out = {"spps": np.array(REF_SPPS, np.int32), "rng_seed": np.array([20230418], np.int64)}
+    for name, t in trees.items():
+        for k in ("child", "data", "scale", "offset", "fmt"):
+            out["tree.%s.%s" % (name, k)] = t[k]
+        out["tree.%s.data_format" % name] = np.array(t["data_format"])
+        if t["extra"] is not None:
+            out["tree.%s.extra" % name] = t["extra"]
+    with tempfile.TemporaryDirectory() as tmp:
+        for ci, (cname, tname, okw, nrand) in enumerate(cases):
+            t = trees[tname]
+            o = dict(default, **okw)
+            case = {"optf": np.array([o["step_size"], o["sigma_thresh"]] + list(o["bbox"]), f32),
+                    "opti": np.array(list(o["minmax"]) + [48 if ci == 0 else 0], np.int32)}
+            ow, dw, tm, _ = _ref_rays(t, rs, nrand)
+            if okw:  # an option set on a tree that has its full set of rays already: the random part and the depth limits
+                keep = np.r_[0:nrand + 40, len(tm) - 28:len(tm)]
+                ow, dw, tm = ow[keep], dw[keep], tm[keep]
+            case["origins"], case["dirs"], case["tmax"] = ow, dw, tm
+            if not okw:
+                case["qpts"] = _ref_query_points(t, rs, 40)
+                case["bdirs"] = _ref_dirs(rs, 40)
+            cpath, opath = os.path.join(tmp, "case.npz"), os.path.join(tmp, "out.bin")
+            write_kat_case(cpath, t, case)
+            subprocess.check_call([exe, cpath, opath])
+            res = read_kat_tables(opath)
+            out["case.%s.tree" % cname] = np.array(tname)
+            for k, v in case.items():
+                out["case.%s.%s" % (cname, k)] = v
+            for k, v in kat_states_to_draws(res).items():
+                if v.size == 0:
+                    continue
+                if k.startswith("dst"):
+                    out["dst.%s" % k] = v
+                else:
+                    out["case.%s.%s" % (cname, k)] = v
+            hit = res["trace32_out"].reshape(-1, 4)[:, 3] > 0
+            print("  %-14s %4d rays, %3d hit at spp 32, %d nodes" % (cname, len(tm), hit.sum(), t["child"].shape[0]))
+        # what the reference's N3Tree(path) holds for the two committed npz trees (src/n3tree.cpp, decode included)
+        for stem in ("npz_dense", "npz_quant"):
+            jpath = os.path.join(tmp, stem + ".json")
+            subprocess.check_call([exe, "--n3tree", os.path.join(HERE, stem + ".npz"), jpath], stdout=subprocess.DEVNULL,
+                                  stderr=subprocess.DEVNULL)
+            out["n3tree.%s" % stem] = np.array(open(jpath).read().strip())
+    path = os.path.join(HERE, "ref_rt_core.npz")
+    np.savez_compressed(path, **out)
+    print("ref_rt_core.npz: %d arrays, %d bytes" % (len(out), os.path.getsize(path)))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["guidance", "npz", "frames", "kat", "ts"]
+    which = sys.argv[1:] or ["guidance", "npz", "frames", "kat", "ts", "ref_rt_core"]
+    if "ref_rt_core" in which:
+        ref_rt_core()
     if "ts" in which:
         ts_ref_format()
     if "kat" in which:

@@ -27,6 +27,7 @@ class Tree(C.Structure):
         ("offset", C.c_float * 3), ("scale", C.c_float * 3),
         ("N", C.c_int), ("data_dim", C.c_int), ("format", C.c_int), ("basis_dim", C.c_int),
         ("ndc_width", C.c_float), ("ndc_height", C.c_float), ("ndc_focal", C.c_float),
+        ("extra", C.c_void_p),
     ]
 
 
@@ -123,7 +124,7 @@ def default_options(spp=1, **kw):
 class HostTree:
     """Keeps the numpy arrays alive next to the orc_tree view."""
 
-    def __init__(self, child, data, scale, offset, data_format="SH9", ndc=None):
+    def __init__(self, child, data, scale, offset, data_format="SH9", ndc=None, extra=None):
         child = np.ascontiguousarray(child, dtype=np.int32)
         data = np.ascontiguousarray(data)
         if data.dtype == np.float16:
@@ -146,6 +147,8 @@ class HostTree:
             t.scale[i] = float(scale[i])
         t.N, t.data_dim, t.format, t.basis_dim = self.N, self.data_dim, self.format, self.basis_dim
         t.ndc_width, t.ndc_height, t.ndc_focal = (-1.0, 0.0, 0.0) if ndc is None else ndc
+        self.extra = None if extra is None else np.ascontiguousarray(extra, dtype=np.float32)  # SG / ASG lobes
+        t.extra = None if self.extra is None else self.extra.ctypes.data
         self.c = t
         self.scale = np.asarray(scale, np.float32)
         self.offset = np.asarray(offset, np.float32)

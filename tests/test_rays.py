@@ -62,13 +62,11 @@ def _rotate(vdir, rot_dirs):
     return out
 
 
-def ray_oracle(ht, origins, dirs, spp, t_max=None, background=None, first_ray=0, bg=1.0, rng_base=None, ndc=None,
-               **optkw):
-    """[n, 4] float32: what rto_launch_rays must return, ray by ray on the CPU"""
+def ray_setup(ht, origins, dirs, ndc=None):
+    """what the frame path does to a ray before trace_ray: normalize3 of the direction, the NDC warp, cen = offset + scale * cen
+    -> (dir, cen, vdir), float32 [n, 3] each; vdir is the unit direction before the warp (and before rot_dirs)"""
     origins = np.ascontiguousarray(origins, f32)
     dirs = np.ascontiguousarray(dirs, f32)
-    n = origins.shape[0]
-    opt = orc.default_options(spp=spp, background_brightness=bg, **optkw)
     d = _normalize3(dirs)
     cen = origins.copy()
     vdir = d.copy()
@@ -83,6 +81,17 @@ def ray_oracle(ht, origins, dirs, spp, t_max=None, background=None, first_ray=0,
             cen = np.stack([-fw * (cen[:, 0] / cen[:, 2]), -fh * (cen[:, 1] / cen[:, 2]), f32(1) + f32(2) / cen[:, 2]], 1)
             d = _normalize3(d)
         cen = ht.offset[None, :] + ht.scale[None, :] * cen
+    return d, cen, vdir
+
+
+def ray_oracle(ht, origins, dirs, spp, t_max=None, background=None, first_ray=0, bg=1.0, rng_base=None, ndc=None,
+               draws=None, **optkw):
+    """[n, 4] float32: what rto_launch_rays must return, ray by ray on the CPU.  draws: an int array [n] that receives the
+    number of RNG draws each ray consumed"""
+    origins = np.ascontiguousarray(origins, f32)
+    n = origins.shape[0]
+    opt = orc.default_options(spp=spp, background_brightness=bg, **optkw)
+    d, cen, vdir = ray_setup(ht, origins, dirs, ndc)
     vdir = _rotate(vdir, optkw.get("rot_dirs", (0.0, 0.0, 0.0)))
     tm = np.full(n, 1e9, f32) if t_max is None else np.asarray(t_max, f32)
     back = np.full((n, 3), bg, f32) if background is None else np.asarray(background, f32)
@@ -104,6 +113,14 @@ def ray_oracle(ht, origins, dirs, spp, t_max=None, background=None, first_ray=0,
         rc = trace(C.byref(ht.c), dbuf, vdir[i].ctypes.data, cen[i].ctypes.data, C.byref(opt), float(tm[i]), o4, C.byref(rng), None)
         assert rc == 0
         out[i] = np.frombuffer(o4, f32)
+        if draws is not None:
+            k, probe = 0, orc.Pcg32(base.state, base.inc)
+            L.orc_pcg32_advance(C.byref(probe), delta - (1 << 64) if delta >= 1 << 63 else delta)
+            while probe.state != rng.state:
+                L.orc_pcg32_next_uint(C.byref(probe))
+                k += 1
+                assert k <= spp
+            draws[i] = k
     nalpha = f32(1) - out[:, 3]
     out[:, :3] += back * nalpha[:, None]
     return out
