@@ -404,6 +404,59 @@ typedef struct rto_rays {
 int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_options* options, rto_ctx* ctx, float* out,
                     void* stream);
 
+/* ---- depth outputs: how far along a ray the volume was hit (no reference counterpart: render_options.hpp:48-49 carries a
+ * render_depth option no kernel reads; options->render_depth stays parsed and ignored -- depth is an output beside the colour) ----
+ * Definitions.  A HIT of a ray is an iteration of the march loop (rt_core.cuh:241-270) in which src + delta >= dst[spp] holds
+ * (:254).  For hit k, in hit order:
+ *   cnt_k = the number of thresholds crossed there (the do ... while);
+ *   t_k   = the value of t at the top of that iteration, in tree units;
+ *   d_k   = t_k * delta_scale, one float product, rounded; delta_scale is the value trace_ray divides tmax_bg by (:206-208), so
+ *           d_k is a distance along the unit ray in the measure of rto_rays.t_max and of the depth layer of rto_ctx_set_layers
+ *           (for an NDC tree that is the warped space, as for t_max).
+ * Two float32 outputs per ray or pixel:
+ *   depth  = (sum_k (float)cnt_k * d_k) * (1.f / SPP): every product and every add rounded (no FMA contraction), the sum left to
+ *            right in hit order from 0.f.  The hit distance summed over the samples that collided, premultiplied as aux planes
+ *            0..2 are: depth / alpha is the mean hit distance, depth + (1 - alpha) * far the expected depth against a far plane.
+ *   t_near = d_0, or +inf when the ray has no hit.
+ * A ray that is not traced or has no hit -- a degenerate ray, a ray that misses the box, t_max <= 0, a pixel of a tile the
+ * single-frame culling (tuning key "cull_single") skips -- gives depth = 0 and t_near = +inf.  A hit at t = 0 is legal (the origin
+ * lies inside a dense leaf): d = 0.  With a t_max or a depth layer only hits with t_k < tmax exist: the loop's own condition.
+ * The generic kernel's loop is the reference's own arithmetic and defines the values; the fast kernel returns the same bits. */
+typedef struct rto_rays_out {
+    float* rgba;   /* [n][4], 16-byte aligned: what rto_launch_rays writes */
+    float* depth;  /* [n] */
+    float* t_near; /* [n] */
+} rto_rays_out;
+/* rto_launch_rays with the depth outputs.  Any member of `out` may be NULL (that output is not stored; without rgba no colour is
+ * computed); all NULL is RTO_E_INVALID, as a null `out`.  With only rgba set this IS rto_launch_rays: the same kernel, the same
+ * bytes.  With depth or t_near set the depth-carrying kernels run (render_rays_depth, render_rays_generic_depth) and rgba, when
+ * asked for, is still bit for bit what rto_launch_rays returns.  Contract, refusals, the splitting rule (matching first_ray gives
+ * the same bytes) and the per-launch split above 2^32 draws are rto_launch_rays'; every argument check comes before any device
+ * use. */
+int rto_launch_rays_ex(const rto_tree* tree, const rto_rays* rays, const rto_options* options, rto_ctx* ctx,
+                       const rto_rays_out* out, void* stream);
+/* Depth outputs of a context's frames: allocates (enable != 0) / releases (0; synchronises the device) two planes [frames][H][W]
+ * float32 on the context's device, depth and t_near of every frame slot; a slot no launch has written yet reads (0, +inf).
+ * While enabled:
+ *   rto_launch_renderer (all kernels, offscreen and over layers, "cull_single" too) writes the selected slot's two planes with
+ *     the rest of its outputs, through the depth-carrying single-frame kernels (render_fast_layers_depth,
+ *     render_generic_layers_depth).  Pixel (x, y) equals, bit for bit, ray y * W + x of rto_launch_rays_ex on the camera's rays
+ *     (origin = the camera centre, direction = M xyz) with t_max = the depth layer's value there, as rto_ctx_set_layers states
+ *     for the colour.
+ *   rto_launch_renderer_batch renders its frames ONE BY ONE through those kernels (the persistent batched kernels carry no
+ *     depth): frame f into slot f with the RNG advanced by rng_jumps[f] * 2^32, the same bytes as n single launches.  Like any
+ *     single-frame launch it leaves no tile marks (rto_ctx_tile_marks: RTO_E_INVALID) and writes full outputs; a lean level
+ *     other than 0 is RTO_E_UNSUPPORTED.
+ *   RTO_E_UNSUPPORTED: options->enable_probe, rto_ctx_enable_stats, a tree loaded with RTO_TREE_QUANT_DIRECT (what the layers
+ *     refuse).
+ * While disabled nothing on the context behaves differently.  rto_launch_rays / _ex do not touch the context's planes. */
+int rto_ctx_enable_depth(rto_ctx* c, int enable);
+int rto_ctx_depth_enabled(const rto_ctx* c);
+float* rto_ctx_depth(rto_ctx* c);  /* device, the selected slot's plane [H][W]; NULL while disabled */
+float* rto_ctx_t_near(rto_ctx* c); /* device, the selected slot's plane [H][W]; NULL while disabled */
+/* the selected slot's planes -> host [H][W] f32 each (either may be NULL); synchronises `stream`.  RTO_E_INVALID while disabled */
+int rto_ctx_download_depth(rto_ctx* c, void* stream, float* host_depth, float* host_t_near);
+
 /* denoiser::filtering(stream, weight_map[L,H,W], guidance_map[L,H,W], img_in, img_out)
  * (filtering.cu:701-717).  All pointers are device pointers; img_in/img_out are [H][W][4] f32
  * (the reference passes ctx.noisy_tex_obj / ctx.surf_obj, denoiser.cpp:56-57).  L in 1..6. */

@@ -42,6 +42,11 @@ class CRays(C.Structure):
                 ("n", C.c_int64), ("first_ray", C.c_int64)]
 
 
+class CRaysOut(C.Structure):
+    """rto_rays_out (include/rto.h): device pointers, any of them NULL"""
+    _fields_ = [("rgba", C.c_void_p), ("depth", C.c_void_p), ("t_near", C.c_void_p)]
+
+
 class CQueryOut(C.Structure):
     """rto_query_out (include/rto.h): device pointers, any of them NULL"""
     _fields_ = [("values", C.c_void_p), ("sigma", C.c_void_p), ("level", C.c_void_p), ("cube", C.c_void_p)]
@@ -115,6 +120,12 @@ SYMBOLS = {
     "rto_launch_renderer": (C.c_int, [_P, C.POINTER(CCamera), C.POINTER(COptions), _P, _P]),
     "rto_launch_renderer_batch": (C.c_int, [_P, C.POINTER(CCamera), C.POINTER(C.c_int64), C.c_int, C.POINTER(COptions), _P, _P]),
     "rto_launch_rays": (C.c_int, [_P, C.POINTER(CRays), C.POINTER(COptions), _P, _P, _P]),
+    "rto_launch_rays_ex": (C.c_int, [_P, C.POINTER(CRays), C.POINTER(COptions), _P, C.POINTER(CRaysOut), _P]),
+    "rto_ctx_enable_depth": (C.c_int, [_P, C.c_int]),
+    "rto_ctx_depth_enabled": (C.c_int, [_P]),
+    "rto_ctx_depth": (_P, [_P]),
+    "rto_ctx_t_near": (_P, [_P]),
+    "rto_ctx_download_depth": (C.c_int, [_P, _P, _P, _P]),
     "rto_filtering_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rto_filtering_batch_mode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
     "rto_filtering_train_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

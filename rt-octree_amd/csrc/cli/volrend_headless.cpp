@@ -54,7 +54,7 @@ struct Args {
 const std::map<std::string, std::string> kShort = {{"w", "width"},      {"h", "height"},     {"s", "step_size"},
                                                    {"e", "stop_thresh"}, {"a", "sigma_thresh"}, {"o", "write_images"},
                                                    {"i", "intrin"},      {"r", "reverse_yz"}};
-const char* kFlags[] = {"reverse_yz", "write_buffer", "help", "print_poses", "quant_direct", "torch_net", "fast_filter", "rank_report", "compact_records", "no_denoise_cull"};
+const char* kFlags[] = {"reverse_yz", "write_buffer", "help", "print_poses", "quant_direct", "torch_net", "fast_filter", "rank_report", "compact_records", "no_denoise_cull", "write_depth"};
 
 bool is_flag(const std::string& k) {
     for (const char* f : kFlags)
@@ -115,6 +115,8 @@ void usage() {
         "  --ts_module ts.ts  TorchScript GuidanceNet (needed when denoise = true)\n"
         "  -o,--write_images DIR   write r_<i>.png (or buf_<name>.bin with --write_buffer)\n"
         "  --write_buffer  --max_imgs N  --scale S  -i intrin  -r,--reverse_yz\n"
+        "  --write_depth      with -o: also write depth_<name>.bin per pose, float32 [2][H][W] = depth, t_near (rto.h \"depth\n"
+        "                     outputs\"); renders one launch per frame (as --batch 1)\n"
         "  --shard i/N        render poses i, i+N, ... only     --warmup K (100)\n"
         "  --gpus N           frames sharded over N GPUs of this node: N child processes (--shard i/N, GPU i each), one\n"
         "                     report for their union; images do not depend on N (per-pose RNG jump-ahead)\n"
@@ -280,6 +282,10 @@ int main(int argc, char** argv) {
         usage();
         return args.has("help") ? 0 : 1;
     }
+    if (args.has("write_depth") && args.get("write_images", "").empty()) {  // (before anything touches a GPU)
+        std::fprintf(stderr, "ERROR: --write_depth needs -o DIR to write into\n");
+        return 1;
+    }
     {
         const int gpus = std::atoi(args.get("gpus", "1").c_str());
         if (gpus < 1 || gpus > 64) {
@@ -369,6 +375,7 @@ int main(int argc, char** argv) {
         }
     }
     const std::string out_dir = args.get("write_images", "");
+    const bool write_depth = args.has("write_depth");
     if (!out_dir.empty()) fs::create_directories(out_dir);
 
     rto_options options;
@@ -394,6 +401,7 @@ int main(int argc, char** argv) {
 
     int batch = std::max(1, std::min(128, std::atoi(args.get("batch", "100").c_str())));
     const int filter_mode = args.has("fast_filter") ? RTO_FILTER_FACTORISED : RTO_FILTER_EXACT;
+    if (write_depth) batch = 1;  // (the depth outputs come from the single-frame kernels: the per-frame loop below)
     {  // no more frame slots than this process has poses to render
         const size_t n_mine = (ps.trans.size() + (size_t)shard_n - 1 - (size_t)shard_i) / (size_t)shard_n;
         if ((size_t)batch > n_mine) batch = (int)std::max<size_t>(1, n_mine);
@@ -404,6 +412,7 @@ int main(int argc, char** argv) {
     }
     rto_ctx* ctx = nullptr;
     CHECK_RTO(rto_ctx_create_batch(width, height, batch, device, &ctx));
+    if (write_depth) CHECK_RTO(rto_ctx_enable_depth(ctx, 1));
 
     std::unique_ptr<rto::TorchDenoiser> denoiser;
     if (options.denoise) {
@@ -485,6 +494,8 @@ int main(int argc, char** argv) {
     std::vector<float> aux;
     const bool write_buffer = args.has("write_buffer");
     if (write_buffer) aux.resize((size_t)width * height * RTO_AUX_CHANNELS);
+    std::vector<float> depth2;  // depth plane, then t_near plane
+    if (write_depth) depth2.resize((size_t)width * height * 2);
     // Batched launches whose aux planes nobody reads store the 16 bytes per pixel the fused denoise stage consumes instead of the
     // reference's 48 (rto_ctx_set_lean_outputs; same PNGs).  --write_buffer dumps the aux planes, the TorchScript module reads them.
     if (batch > 1 && options.denoise && denoiser && denoiser->fused() && !write_buffer) CHECK_RTO(rto_ctx_set_lean_outputs(ctx, 1));
@@ -567,6 +578,16 @@ int main(int argc, char** argv) {
             CHECK_RTO(rto_ctx_download_rgba8(ctx, stream, 0, rgba8.data()));
             if (!rto::write_png_rgba8(out_dir + "/" + ps.basenames[i] + ".png", rgba8.data(), width, height)) {
                 std::fprintf(stderr, "ERROR: cannot write %s/%s.png\n", out_dir.c_str(), ps.basenames[i].c_str());
+                return 1;
+            }
+        }
+        if (write_depth) {
+            CHECK_RTO(rto_ctx_download_depth(ctx, stream, depth2.data(), depth2.data() + (size_t)width * height));
+            std::ofstream f(out_dir + "/depth_" + ps.basenames[i] + ".bin", std::ios::binary);
+            f.write(reinterpret_cast<const char*>(depth2.data()), (std::streamsize)(depth2.size() * sizeof(float)));
+            f.close();
+            if (!f) {
+                std::fprintf(stderr, "ERROR: cannot write %s/depth_%s.bin\n", out_dir.c_str(), ps.basenames[i].c_str());
                 return 1;
             }
         }

@@ -1,0 +1,156 @@
+// depth_kernels.hip -- the depth-carrying instantiations of the single-frame and ray kernels (include/rto.h "depth outputs";
+// DESIGN.md section 7e): the bodies of render_kernels.hip (rto_render_fast.inc, rto_render_generic.inc) with RTO_DEPTH defined, which
+// also keep the distance of a ray's hits and store depth and t_near through a DepthOut argument.  A translation unit of its own:
+// render_kernels.hip keeps its kernels, their text and its compile time, and the two compile side by side.
+#include <hip/hip_runtime.h>
+
+#include "rto_kernel_types.h"
+#include "rto_launch.h"
+#include "rto_tree_device.h"
+
+#pragma clang fp contract(off)
+
+#include "rto_depth_launch.h"
+#include "rto_render_shared.h"
+
+namespace rto {
+
+// ---- the depth-carrying forms (rto_launch_rays_ex with depth / t_near; a context with rto_ctx_enable_depth): the same bodies
+// with RTO_DEPTH -- instantiations of their own, so that the kernels above keep their text, their arguments and their code
+template <int SPP>
+__global__ void __launch_bounds__(256) render_rays_generic_depth(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
+                                                                  const RayBatch rays, const DepthOut dout) {
+#define RTO_GENERIC_RAYS 1
+#define RTO_DEPTH 1
+#include "rto_render_generic.inc"
+#undef RTO_DEPTH
+#undef RTO_GENERIC_RAYS
+}
+
+// (the frame form is the layered body: both layer pointers null is the offscreen frame)
+template <int SPP>
+__global__ void __launch_bounds__(256) render_generic_layers_depth(const TreeDev tree, const CamDev cam, const OptDev opt, const Pcg32 rng_base,
+                                                                    const FrameOut fo, const LayerDev layers, const DepthOut dout) {
+#define RTO_GENERIC_LAYERS 1
+#define RTO_DEPTH 1
+#include "rto_render_generic.inc"
+#undef RTO_DEPTH
+#undef RTO_GENERIC_LAYERS
+}
+
+// The depth-carrying forms of render_rays and render_fast_layers (RTO_DEPTH; DepthOut behind their siblings' arguments).  One frame family
+// serves offscreen and layered contexts: both layer pointers null is the offscreen frame.  render_persist has none: its hit
+// hand-off has no room for t.
+// Waves per SIMD the two kernels are built for: their siblings' (RTO_FAST_WPS up to SPP 8, 4 above), one less where the two more
+// live registers would otherwise go to the private segment -- render_rays at SPP 8 on the two-level image already keeps 8 bytes
+// per lane at 5 waves, and the SPP-32 forms 132-136 at 4; with one wave less the depth forms hold no more than their siblings
+// (tests/test_depth.py::test_depth_kernels_codegen).
+constexpr int depth_rays_wps(int spp) { return spp < 8 ? RTO_FAST_WPS : spp == 8 ? RTO_FAST_WPS - 1 : spp < 32 ? 4 : 3; }
+constexpr int depth_frame_wps(int spp) { return spp <= 8 ? RTO_FAST_WPS : spp < 32 ? 4 : 3; }
+
+template <int SPP, bool WIDE, int STACK, int LOBES>
+__global__ void __launch_bounds__(256, depth_rays_wps(SPP)) render_rays_depth(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
+                                                          const PcgJumpEntry* __restrict__ jump, const RayBatch rays,
+                                                          const DepthOut dout) {
+    constexpr bool STATS = false;
+#define RTO_FAST_RAYS 1
+#define RTO_DEPTH 1
+#include "rto_render_fast.inc"
+#undef RTO_DEPTH
+#undef RTO_FAST_RAYS
+}
+
+template <int SPP, bool WIDE, int STACK, int LOBES>
+__global__ void __launch_bounds__(256, depth_frame_wps(SPP)) render_fast_layers_depth(const TreeDev tree, const CamDev cam, const OptDev opt,
+                                                                 const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
+                                                                 const TileMap tm, const FrameOut fo, const LayerDev layers,
+                                                                 const DepthOut dout) {
+    constexpr bool STATS = false;
+#define RTO_FAST_LAYERS 1
+#define RTO_DEPTH 1
+#include "rto_render_fast.inc"
+#undef RTO_DEPTH
+#undef RTO_FAST_LAYERS
+}
+
+// ------------------------------------------------------------------ launchers (declared in rto_depth_launch.h)
+
+template <int SPP, int LOBES>
+void launch_fast_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                       const FrameOut& fo, int strip_rows, const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
+    const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
+    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
+    const dim3 grid(8 * tm.per_xcd), block(256);
+#define RTO_FAST_D(WI, SK) \
+    hipLaunchKernelGGL((render_fast_layers_depth<SPP, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, layers, depth)
+    if (tree.widew) {  // (launch_fast's choice of the image)
+        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
+            RTO_FAST_D(true, 1);
+        } else {
+            RTO_FAST_D(true, 0);
+        }
+    } else {
+        RTO_FAST_D(false, 0);
+    }
+#undef RTO_FAST_D
+}
+
+template <int SPP>
+void launch_generic_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const FrameOut& fo,
+                          const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
+    const int64_t size = (int64_t)cam.width * cam.height;
+    hipLaunchKernelGGL(render_generic_layers_depth<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam, opt, rng, fo,
+                       layers, depth);
+}
+
+template <int SPP, int LOBES>
+void launch_rays_depth_fast(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump, const RayBatch& rb,
+                            const DepthOut& depth, dim3 grid, hipStream_t stream) {
+    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
+#define RTO_RAYS_D(WI, SK) hipLaunchKernelGGL((render_rays_depth<SPP, WI, SK, LOBES>), grid, dim3(256), lds, stream, tree, opt, rng, jump, rb, depth)
+    if (tree.widew) {  // (launch_fast's choice)
+        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
+            RTO_RAYS_D(true, 1);
+        } else {
+            RTO_RAYS_D(true, 0);
+        }
+    } else {
+        RTO_RAYS_D(false, 0);
+    }
+#undef RTO_RAYS_D
+}
+
+template <int SPP>
+void launch_rays_depth_generic(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb, const DepthOut& depth,
+                               dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL(render_rays_generic_depth<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb, depth);
+}
+
+// every SPP of launch_render / launch_rays (RTO_DEV_SPP6_ONLY: the development build's one)
+#define RTO_DEPTH_INSTANCES(SPP)                                                                                                       \
+    template void launch_generic_depth<SPP>(const TreeDev&, const CamDev&, const OptDev&, const Pcg32&, const FrameOut&, const LayerDev&, \
+                                            const DepthOut&, hipStream_t);                                                              \
+    template void launch_rays_depth_generic<SPP>(const TreeDev&, const OptDev&, const Pcg32&, const RayBatch&, const DepthOut&, dim3,   \
+                                                 hipStream_t);                                                                          \
+    RTO_DEPTH_INSTANCES_L(SPP, 0)                                                                                                       \
+    RTO_DEPTH_INSTANCES_L(SPP, kFmtSG)                                                                                                  \
+    RTO_DEPTH_INSTANCES_L(SPP, kFmtASG)
+#define RTO_DEPTH_INSTANCES_L(SPP, L)                                                                                                   \
+    template void launch_fast_depth<SPP, L>(const TreeDev&, const CamDev&, const OptDev&, const Pcg32&, const PcgJumpEntry*,            \
+                                            const FrameOut&, int, const LayerDev&, const DepthOut&, hipStream_t);                       \
+    template void launch_rays_depth_fast<SPP, L>(const TreeDev&, const OptDev&, const Pcg32&, const PcgJumpEntry*, const RayBatch&,      \
+                                                 const DepthOut&, dim3, hipStream_t);
+#ifndef RTO_DEV_SPP6_ONLY
+RTO_DEPTH_INSTANCES(1)
+RTO_DEPTH_INSTANCES(2)
+RTO_DEPTH_INSTANCES(3)
+RTO_DEPTH_INSTANCES(4)
+RTO_DEPTH_INSTANCES(8)
+RTO_DEPTH_INSTANCES(16)
+RTO_DEPTH_INSTANCES(32)
+#endif
+RTO_DEPTH_INSTANCES(6)
+#undef RTO_DEPTH_INSTANCES_L
+#undef RTO_DEPTH_INSTANCES
+
+}  // namespace rto

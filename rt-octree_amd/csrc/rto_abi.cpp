@@ -304,7 +304,7 @@ void rto_ctx_free(rto_ctx* c) {
     DeviceGuard guard(c->device);
     for (void* p : {(void*)c->aux, (void*)c->noisy, (void*)c->image, (void*)c->rgba8, (void*)c->jump, (void*)c->queue, (void*)c->tile_mask,
                     (void*)c->qlist, (void*)c->qscratch, (void*)c->d_frames, (void*)c->probe_coeffs, (void*)c->hits, (void*)c->tile_order,
-                    (void*)c->wedge_order, (void*)c->stats})
+                    (void*)c->wedge_order, (void*)c->stats, (void*)c->depth, (void*)c->t_near})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : c->kt_ev) (void)hipEventDestroy(e);
     for (int i = 0; i < 3; ++i) {
@@ -384,6 +384,42 @@ int rto_ctx_layers(const rto_ctx* c, const float** depth, const float** color) {
     if (color) *color = c->layer_color;
     return RTO_OK;
 }
+
+int rto_ctx_enable_depth(rto_ctx* c, int enable) {
+    if (!c) return set_err(RTO_E_INVALID, "rto_ctx_enable_depth: null context");
+    if ((enable != 0) == (c->depth != nullptr)) return RTO_OK;
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    if (!enable) {  // (launches in flight may still write the planes)
+        HIP_TRY(hipDeviceSynchronize());
+        float* const d = c->depth;
+        float* const t = c->t_near;
+        c->depth = c->t_near = nullptr;
+        const hipError_t e1 = hipFree(d), e2 = hipFree(t);  // (both planes, whatever the first call says)
+        if (e1 != hipSuccess || e2 != hipSuccess)
+            return set_err(RTO_E_HIP, std::string("hipFree(depth outputs): ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+        return RTO_OK;
+    }
+    const size_t bytes = frame_px(c) * (size_t)c->frames * sizeof(float);
+    float *d = nullptr, *t = nullptr;
+    if (hipMalloc((void**)&d, bytes) != hipSuccess || hipMalloc((void**)&t, bytes) != hipSuccess) {
+        if (d) (void)hipFree(d);
+        return set_err(RTO_E_HIP, "hipMalloc(depth outputs) failed");
+    }
+    // until a launch writes a slot it reads as "no hit": depth 0, t_near +inf (0x7f800000 has no byte pattern: a copy)
+    const std::vector<float> inf(frame_px(c) * (size_t)c->frames, INFINITY);
+    if (hipMemset(d, 0, bytes) != hipSuccess || hipMemcpy(t, inf.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        (void)hipFree(t);
+        return set_err(RTO_E_HIP, "initialising the depth outputs failed");
+    }
+    c->depth = d;
+    c->t_near = t;
+    return RTO_OK;
+}
+int rto_ctx_depth_enabled(const rto_ctx* c) { return c && c->depth ? 1 : 0; }
+float* rto_ctx_depth(rto_ctx* c) { return c && c->depth ? c->depth + (size_t)c->sel * frame_px(c) : nullptr; }
+float* rto_ctx_t_near(rto_ctx* c) { return c && c->t_near ? c->t_near + (size_t)c->sel * frame_px(c) : nullptr; }
 
 int rto_ctx_set_kernel(rto_ctx* c, int kernel) {
     if (!c || kernel < RTO_KERNEL_AUTO || kernel > RTO_KERNEL_FAST)
@@ -706,6 +742,19 @@ int rto_ctx_download_aux(rto_ctx* c, void* stream_, float* host_out) {
     hipStream_t stream = (hipStream_t)stream_;
     const size_t bytes = (size_t)c->width * c->height * RTO_AUX_CHANNELS * sizeof(float);
     HIP_TRY(hipMemcpyAsync(host_out, rto_ctx_aux(c), bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RTO_OK;
+}
+
+int rto_ctx_download_depth(rto_ctx* c, void* stream_, float* host_depth, float* host_t_near) {
+    if (!c) return set_err(RTO_E_INVALID, "rto_ctx_download_depth: null context");
+    if (!c->depth) return set_err(RTO_E_INVALID, "rto_ctx_download_depth: the context keeps no depth outputs (rto_ctx_enable_depth)");
+    DeviceGuard guard(c->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t bytes = frame_px(c) * sizeof(float);
+    if (host_depth) HIP_TRY(hipMemcpyAsync(host_depth, rto_ctx_depth(c), bytes, hipMemcpyDeviceToHost, stream));
+    if (host_t_near) HIP_TRY(hipMemcpyAsync(host_t_near, rto_ctx_t_near(c), bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return RTO_OK;
 }

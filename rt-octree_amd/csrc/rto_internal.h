@@ -128,6 +128,9 @@ struct rto_ctx {
     // rto_ctx_set_layers (RenderContext::offscreen = false): borrowed device planes, one per frame slot; both null = offscreen
     const float* layer_depth = nullptr;  // [frames][H][W]
     const float* layer_color = nullptr;  // [frames][H][W][4]
+    // rto_ctx_enable_depth: the depth outputs of the frame slots, [frames][H][W] each; both null = disabled
+    float* depth = nullptr;
+    float* t_near = nullptr;
     float* probe_coeffs = nullptr;       // kProbeFloats: the probe point's leaf coefficients of the launch in flight (enable_probe)
     uint8_t* rgba8 = nullptr;
     rto::Pcg32 rng{};

@@ -202,6 +202,15 @@ struct LayerDev {
     const float4* color;  // [frames][H][W] (r, g, b, unread) the volume is composited over, or nullptr (background_brightness)
 };
 
+// The depth outputs (rto_launch_rays_ex, rto_ctx_enable_depth; include/rto.h "depth outputs") of the depth-carrying kernels
+// (render_rays_depth, render_rays_generic_depth, render_fast_layers_depth, render_generic_layers_depth): one float per ray or
+// pixel of the launch each, either may be nullptr (not stored).  A kernel argument of its own BEHIND the arguments of its
+// sibling, for LayerDev's reason: FrameOut, RayBatch and TreeDev keep their size and the existing kernels their arguments.
+struct DepthOut {
+    float* depth;   // (sum over the hits, in hit order, of (float)count * (t * delta_scale)) * (1.f / SPP); 0 without a hit
+    float* t_near;  // t * delta_scale of the first hit; +inf without one
+};
+
 // stats[0..5] = SURVEY 8d's units over EVERY ray (orc_stats order: rays, rays_in_box, steps, levels of a root-restart walk,
 // hit leaves, rays with a hit); stats[6..11] = the same frame as the batched path works through it: rays of marked tiles,
 // their march steps, top-grid entries loaded (8 B each), traversal-image words loaded (4 B each), hit entries written,

@@ -31,15 +31,19 @@ TileMap make_tile_map(int width, int height, int strip_rows);
 // kernel: 1 = generic, 2 = fast.  spp must be one of {1,2,3,4,6,8,16,32} (hipErrorInvalidValue otherwise)
 // layers != nullptr (rto_ctx_set_layers; never with fo.stats): the layered kernels -- pixel (x, y) stops at layers->depth[y W + x]
 // and is composited over layers->color[y W + x] (the caller has offset both to the frame's plane)
+// depth != nullptr (rto_ctx_enable_depth; never with fo.stats): the depth-carrying layered kernels, over `layers` or none -- the
+// same pixels, and pixel (x, y)'s depth / t_near at index y W + x of depth's planes (offset to the frame's by the caller)
 hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
                          const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, const LayerDev* layers,
-                         hipStream_t stream);
+                         const DepthOut* depth, hipStream_t stream);
 
 // rto_launch_rays: the rb.n rays of rb (rb.n * spp < 2^32, else hipErrorInvalidValue) with the fast (2: render_rays) or the generic
 // (1: render_rays_generic) kernel; ray i draws its samples from rng advanced by i * spp.  xcd_order: each XCD takes one contiguous
-// range of the rays (RayBatch::per_xcd) instead of every eighth block of 256
+// range of the rays (RayBatch::per_xcd) instead of every eighth block of 256.  depth != nullptr (rto_launch_rays_ex with depth or
+// t_near): render_rays_depth / render_rays_generic_depth, which also store ray i's depth / t_near at index i (either pointer may
+// be nullptr, and rb.out may then be nullptr too: no colour is computed); nullptr: the kernels of rto_launch_rays
 hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                       const RayBatch& rb, bool xcd_order, hipStream_t stream);
+                       const RayBatch& rb, const DepthOut* depth, bool xcd_order, hipStream_t stream);
 
 // tile marks of ONE frame for the single-frame kernel's culling (FrameOut::cull_marks): zeroes `mask` ((tiles + 31) / 32 + 1
 // words) on the stream and projects the tree's culling cells into the camera

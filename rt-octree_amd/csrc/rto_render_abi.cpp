@@ -1,6 +1,6 @@
-// rto_render_abi.cpp -- the three launch entries of the C ABI (include/rto.h): rto_launch_renderer (one frame),
-// rto_launch_renderer_batch (n frames in one launch of the persistent kernels) and rto_launch_rays, built from one set of
-// refusals and one set-up.  Every refusal for a call's arguments comes before the first change to the context.
+// rto_render_abi.cpp -- the launch entries of the C ABI (include/rto.h): rto_launch_renderer (one frame),
+// rto_launch_renderer_batch (n frames in one launch of the persistent kernels) and rto_launch_rays / rto_launch_rays_ex, built
+// from one set of refusals and one set-up.  Every refusal for a call's arguments comes before the first change to the context.
 #include <algorithm>
 #include <cstring>
 
@@ -55,6 +55,24 @@ int check_layers(const rto_tree* tree, const rto_ctx* ctx, bool layered) {
         return set_err(RTO_E_UNSUPPORTED, "layers (rto_ctx_set_layers) and work counters (rto_ctx_enable_stats) do not combine");
     if (layered && tree->quant)
         return set_err(RTO_E_UNSUPPORTED, "a quantised tree loaded with RTO_TREE_QUANT_DIRECT takes no layers (rto_ctx_set_layers): expand it");
+    return RTO_OK;
+}
+
+// the depth outputs of a launch into context slot `slot` (rto_ctx_enable_depth); false: the context keeps none
+bool ctx_depth_at(const rto_ctx* c, int slot, rto::DepthOut* out) {
+    if (!c->depth) return false;
+    out->depth = c->depth + (size_t)slot * frame_px(c);
+    out->t_near = c->t_near + (size_t)slot * frame_px(c);
+    return true;
+}
+// what a context with depth outputs refuses: the set the layers refuse (the depth kernels are layered kernels)
+int check_depth(const rto_tree* tree, const rto_options* o, const rto_ctx* ctx) {
+    if (!ctx->depth) return RTO_OK;
+    if (ctx->stats_on)
+        return set_err(RTO_E_UNSUPPORTED, "depth outputs (rto_ctx_enable_depth) and work counters (rto_ctx_enable_stats) do not combine");
+    if (tree->quant)
+        return set_err(RTO_E_UNSUPPORTED, "a quantised tree loaded with RTO_TREE_QUANT_DIRECT renders no depth outputs (rto_ctx_enable_depth): expand it");
+    if (o->enable_probe) return set_err(RTO_E_UNSUPPORTED, "enable_probe on a context with depth outputs (rto_ctx_enable_depth) is not built");
     return RTO_OK;
 }
 
@@ -158,13 +176,14 @@ int ensure_tile_buffers(rto_ctx* ctx, int mask_words, int chunks_cap) {
     return RTO_OK;
 }
 
-// One frame through `kernel` to where fo says, over `layers` (nullptr: none), the probe's disc on top when the options ask.
+// One frame through `kernel` to where fo says, over `layers` (nullptr: none), its depth outputs to `depth` (nullptr: none kept),
+// the probe's disc on top when the options ask.
 // tree_dev: the tree as that kernel takes it (choose_kernel's for the fast kernel, tree->dev itself for the generic one, whose
 // child[] / data[] ensure_reference_arrays may just have rebuilt)
 int render_frame(const rto_tree* tree, const rto::TreeDev& tree_dev, int kernel, const rto::CamDev& cd, const rto_options* o,
-                 const rto::OptDev& od, const rto::Pcg32& rng, const rto::FrameOut& fo, const rto::LayerDev* layers, rto_ctx* ctx,
-                 hipStream_t stream) {
-    const hipError_t e = rto::launch_render(kernel, o->spp, tree_dev, cd, od, rng, ctx->jump, fo, ctx->strip_rows, layers, stream);
+                 const rto::OptDev& od, const rto::Pcg32& rng, const rto::FrameOut& fo, const rto::LayerDev* layers,
+                 const rto::DepthOut* depth, rto_ctx* ctx, hipStream_t stream) {
+    const hipError_t e = rto::launch_render(kernel, o->spp, tree_dev, cd, od, rng, ctx->jump, fo, ctx->strip_rows, layers, depth, stream);
     if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("render launch failed: ") + hipGetErrorString(e));
     if (!o->enable_probe) return RTO_OK;
     rto::FrameDesc one = {};
@@ -193,7 +212,34 @@ int generic_frames(const rto_tree* tree, const rto_camera* cams, const int64_t* 
         rto::LayerDev layers;
         const bool layered = ctx_layers_at(ctx, slot0 + f, &layers);
         rc = render_frame(tree, tree->dev, RTO_KERNEL_GENERIC, cam_dev(cams[f]), o, od, rng_after(ctx, frame_jump(rng_jumps, f)),
-                          frame_out(ctx, slot0 + f, o->denoise), layered ? &layers : nullptr, ctx, stream);
+                          frame_out(ctx, slot0 + f, o->denoise), layered ? &layers : nullptr, nullptr, ctx, stream);
+        if (rc != RTO_OK) return rc;
+    }
+    return RTO_OK;
+}
+
+// The frames of a batched call on a context with depth outputs, one by one through the single-frame depth kernels
+// (render_persist carries no depth): frame f into slot slot0 + f with the RNG of a batch's frame f -- the bytes of n single
+// launches.  As after generic_frames: no tile marks, full outputs.  The caller has checked the cameras and the lean level.
+int depth_frames(const rto_tree* tree, const rto_camera* cams, const int64_t* rng_jumps, int n, const rto_options* o, rto_ctx* ctx,
+                 hipStream_t stream, int slot0) {
+    int kernel;
+    rto::TreeDev tdev;
+    int rc = choose_kernel(tree, o, ctx, &kernel, &tdev);
+    if (rc != RTO_OK) return rc;
+    const bool fast = kernel == RTO_KERNEL_FAST;
+    ctx->marks_n = 0;
+    for (int f = 0; f < n; ++f) ctx->lean_slot[(size_t)(slot0 + f)] = 0;
+    rc = fast ? ensure_jump_table(ctx) : ensure_reference_arrays(tree);
+    if (rc != RTO_OK) return rc;
+    const rto::OptDev od = make_opt_dev(o);
+    for (int f = 0; f < n; ++f) {
+        rto::LayerDev layers;
+        const bool layered = ctx_layers_at(ctx, slot0 + f, &layers);
+        rto::DepthOut depth;
+        ctx_depth_at(ctx, slot0 + f, &depth);
+        rc = render_frame(tree, fast ? tdev : tree->dev, kernel, cam_dev(cams[f]), o, od, rng_after(ctx, frame_jump(rng_jumps, f)),
+                          frame_out(ctx, slot0 + f, o->denoise), layered ? &layers : nullptr, &depth, ctx, stream);
         if (rc != RTO_OK) return rc;
     }
     return RTO_OK;
@@ -217,6 +263,11 @@ int check_batch(const rto_tree* tree, const rto_camera* cams, int n, const rto_o
     }
     rc = check_layers(tree, ctx, layered);
     if (rc != RTO_OK) return rc;
+    rc = check_depth(tree, o, ctx);
+    if (rc != RTO_OK) return rc;
+    if (ctx->depth && ctx->lean != 0)  // (the single-frame kernels the frames go through store full outputs)
+        return set_err(RTO_E_UNSUPPORTED, "a context with depth outputs (rto_ctx_enable_depth) renders its batches frame by frame: lean "
+                                          "outputs (rto_ctx_set_lean_outputs) must be off");
     // sparse lean outputs store nothing for unmarked tiles because those are the constant background -- not over a colour layer
     if (layered && layers.color && o->denoise && ctx->lean == 2)
         return set_err(RTO_E_UNSUPPORTED, "sparse lean outputs (rto_ctx_set_lean_outputs level 2) need a constant backdrop: not with a colour "
@@ -275,12 +326,13 @@ int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const int64_t*
     // generic kernel each -- same images, without the batching gain.
     rto::TreeDev tdev;
     const bool batched = spp_supported(o->spp) && fast_path_for_spp(tree, o->spp, ctx->test_wide_bits, &tdev) != 0 &&
-                         ctx->batch_fallback != 1;
+                         ctx->batch_fallback != 1 && !ctx->depth;
     int rc = check_batch(tree, cams, n, o, ctx, slot0, batched);
     if (rc != RTO_OK) return rc;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     hipStream_t stream = (hipStream_t)stream_;
+    if (ctx->depth) return depth_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
     if (!batched) return generic_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
 
     ctx->marks_n = 0;  // whatever happens below, the tile marks of an earlier launch no longer describe this context's frames
@@ -368,6 +420,7 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     rto::LayerDev layers;
     const bool layered = ctx_layers_at(ctx, ctx->sel, &layers);  // (a single-frame launch reads the selected slot's planes)
     int rc = check_layers(tree, ctx, layered);
+    if (rc == RTO_OK) rc = check_depth(tree, o, ctx);
     if (rc != RTO_OK) return rc;
     if (tree->quant) {  // codebook shading lives in the batched kernels: a batch of one into the selected slot
         if (ctx->kernel == RTO_KERNEL_GENERIC || ctx->stats_on)
@@ -382,7 +435,7 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     if (rc == RTO_OK) rc = choose_kernel(tree, o, ctx, &kernel, &tdev);
     if (rc != RTO_OK) return rc;
     const bool fast = kernel == RTO_KERNEL_FAST;
-    if (fast && ctx->frame_via_batch && ctx->kernel == RTO_KERNEL_AUTO && !ctx->stats_on)
+    if (fast && ctx->frame_via_batch && ctx->kernel == RTO_KERNEL_AUTO && !ctx->stats_on && !ctx->depth)
         return launch_batch_at(tree, cam, nullptr, 1, o, ctx, stream_, ctx->sel);
 
     DeviceGuard guard(ctx->device);
@@ -420,7 +473,10 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     }
     if (!keep_marks) ctx->marks_n = 0;  // (the generic kernel and the counting instantiation mark no tiles)
     ctx->lean_slot[(size_t)ctx->sel] = 0;  // (a single frame has full outputs; the other slots keep what they hold)
-    rc = render_frame(tree, fast ? tdev : tree->dev, kernel, cd, o, make_opt_dev(o), ctx->rng, fo, layered ? &layers : nullptr, ctx, stream);
+    rto::DepthOut depth;
+    const bool with_depth = ctx_depth_at(ctx, ctx->sel, &depth);
+    rc = render_frame(tree, fast ? tdev : tree->dev, kernel, cd, o, make_opt_dev(o), ctx->rng, fo, layered ? &layers : nullptr,
+                      with_depth ? &depth : nullptr, ctx, stream);
     if (rc != RTO_OK) return rc;
     // (over a colour layer an unmarked tile is not the constant background: the marks are kept from the denoise stage)
     if (cull_one && !(layered && layers.color)) {  // the selected slot's marks, for rto_ctx_tile_marks / the culled denoise stage
@@ -437,10 +493,23 @@ int rto_launch_renderer_batch(const rto_tree* tree, const rto_camera* cams, cons
 }
 
 int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_options* o, rto_ctx* ctx, float* out, void* stream_) {
-    if (!tree || !rays || !o || !ctx || !out) return set_err(RTO_E_INVALID, "rto_launch_rays: null argument");
+    if (!out) return set_err(RTO_E_INVALID, "rto_launch_rays: null argument");
+    const rto_rays_out ro = {out, nullptr, nullptr};
+    return rto_launch_rays_ex(tree, rays, o, ctx, &ro, stream_);
+}
+
+// (with only rgba asked for, the launches below are rto_launch_rays': the same kernels with the same arguments)
+int rto_launch_rays_ex(const rto_tree* tree, const rto_rays* rays, const rto_options* o, rto_ctx* ctx, const rto_rays_out* ro,
+                       void* stream_) {
+    if (!tree || !rays || !o || !ctx || !ro) return set_err(RTO_E_INVALID, "rto_launch_rays: null argument");
+    if (!ro->rgba && !ro->depth && !ro->t_near) return set_err(RTO_E_INVALID, "rto_launch_rays_ex: no output asked for");
     if (rays->n < 0 || rays->first_ray < 0) return set_err(RTO_E_INVALID, "rto_launch_rays: n and first_ray must be >= 0");
     if (rays->n > 0 && (!rays->origins || !rays->dirs)) return set_err(RTO_E_INVALID, "rto_launch_rays: null origins / dirs");
-    if ((uintptr_t)out % 16 != 0) return set_err(RTO_E_INVALID, "rto_launch_rays: out must be 16-byte aligned");
+    if ((uintptr_t)ro->rgba % 16 != 0) return set_err(RTO_E_INVALID, "rto_launch_rays: out must be 16-byte aligned");
+    if ((uintptr_t)ro->depth % 4 != 0 || (uintptr_t)ro->t_near % 4 != 0)
+        return set_err(RTO_E_INVALID, "rto_launch_rays_ex: depth and t_near must be 4-byte aligned");
+    float* const out = ro->rgba;
+    const bool with_depth = ro->depth || ro->t_near;
     if (tree->quant)
         return set_err(RTO_E_UNSUPPORTED, "a quantised tree loaded with RTO_TREE_QUANT_DIRECT is shaded by the batched kernels only: "
                                           "rto_launch_rays needs an expanded tree");
@@ -468,14 +537,16 @@ int rto_launch_rays(const rto_tree* tree, const rto_rays* rays, const rto_option
         rb.dirs = rays->dirs + 3 * i0;
         rb.t_max = rays->t_max ? rays->t_max + i0 : nullptr;
         rb.background = rays->background ? rays->background + 3 * i0 : nullptr;
-        rb.out = reinterpret_cast<float4*>(out) + i0;
+        rb.out = out ? reinterpret_cast<float4*>(out) + i0 : nullptr;
+        const rto::DepthOut depth = {ro->depth ? ro->depth + i0 : nullptr, ro->t_near ? ro->t_near + i0 : nullptr};
         rb.n = (uint32_t)std::min(per_launch, rays->n - i0);
         rb.per_xcd = 0;
         // ray i0 + i draws from ctx.rng advanced by (first_ray + i0 + i) * spp: the host takes (first_ray + i0) * spp (mod 2^64,
         // the generator's period), the kernel i * spp
         const rto::Pcg32 rng = rng_after(ctx, (uint64_t)(rays->first_ray + i0) * (uint64_t)o->spp);
         // (the generic kernel reads tree->dev itself: child[] / data[] may just have been rebuilt by ensure_reference_arrays)
-        const hipError_t e = rto::launch_rays(kernel, o->spp, fast ? tdev : tree->dev, od, rng, ctx->jump, rb, ctx->ray_order != 0, stream);
+        const hipError_t e = rto::launch_rays(kernel, o->spp, fast ? tdev : tree->dev, od, rng, ctx->jump, rb, with_depth ? &depth : nullptr,
+                                              ctx->ray_order != 0, stream);
         if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("ray launch failed: ") + hipGetErrorString(e));
     }
     return RTO_OK;

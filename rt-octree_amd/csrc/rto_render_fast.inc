@@ -2,6 +2,9 @@
 // RGBA trees), render_fast_lobes (LOBES = kFmtSG / kFmtASG) and render_rays (RTO_FAST_RAYS defined to 1 around the include: the
 // rays of rto_launch_rays instead of a camera's pixels) and render_fast_layers (RTO_FAST_LAYERS defined to 1: a camera's pixels,
 // each ray stopped at its pixel of the depth layer and composited over its pixel of the colour layer -- `layers`, rto_ctx_set_layers).
+// RTO_DEPTH defined to 1 as well (render_rays_depth, render_fast_layers_depth): the ray also keeps the distance of its hits -- d =
+// t * delta_scale at the top of the march step that collides -- and stores depth and t_near through `dout` (DepthOut,
+// include/rto.h "depth outputs"): two multiplies, an add and a select per hit, no load, two registers, two 4-byte stores.
 // In scope: the kernel parameters and SPP, STATS, WIDE, STACK, LOBES.
 // (The ray source is switched by the preprocessor, not by if constexpr: the frame kernels' text -- and so their code -- is
 // exactly what it was before the ray kernel existed.)
@@ -12,6 +15,9 @@
     const uint32_t ray = ray_index(rays, blockIdx.x, tid);
     if (ray >= rays.n) return;
     float out[4] = {0.f, 0.f, 0.f, 0.f};
+#if RTO_DEPTH
+    float dsum = 0.f, tnear = __builtin_inff();
+#endif
     float dir[3], vdir[3], cen[3], invdir[3], tmax_bg, bg[3];
     const bool live = ray_from_batch(rays, ray, tree, opt.background_brightness, dir, vdir, cen, tmax_bg, bg);  // (false: degenerate)
 #else
@@ -26,6 +32,9 @@
     const int idx = y * cam.width + x;
 
     float out[4] = {0.f, 0.f, 0.f, 0.f};
+#if RTO_DEPTH
+    float dsum = 0.f, tnear = __builtin_inff();
+#endif
 #if RTO_FAST_LAYERS
     float bg[3];
     layer_backdrop(layers, (uint32_t)idx, opt.background_brightness, bg);
@@ -35,6 +44,9 @@
         if (!(((fo.cull_marks[t >> 5] >> (t & 31u)) | fo.cull_marks[fo.cull_mask_words - 1]) & 1u)) {
 #if RTO_FAST_LAYERS
             write_pixel_over(fo, SIZE, idx, bg, out);  // no ray of this tile meets density, whatever its depth: the backdrop
+#if RTO_DEPTH
+            write_depth(dout, (uint32_t)idx, dsum, tnear);  // (... and no hit: 0, +inf)
+#endif
 #else
             write_pixel(fo, SIZE, idx, opt.background_brightness, out);  // no ray of this tile meets density: background
 #endif
@@ -265,6 +277,13 @@
 #pragma unroll
                         for (int i = 0; i < SPP; ++i) dst[i] = dst[i + 1];
                     } while (src + delta >= dst[0]);
+#if RTO_DEPTH
+                    {  // (t: the step's own, unscaled in every form -- STACK == 1 scales cen and dir, not t)
+                        const float d = t * delta_scale;
+                        dsum += (float)cnt * d;
+                        tnear = sh_nums == 0u ? d : tnear;
+                    }
+#endif
                     // (the counting instantiation walks the one-level image; a tree whose records follow the two-level image's
                     //  entries needs the leaf's entry there: found by that image's walk -- this kernel is never timed)
                     const uint32_t h = hit_pack<SPP>(!WIDE && tree.rec_by_entry ? wide_entry_of(tree, ix, iy, iz) : slot, cnt);
@@ -279,7 +298,14 @@
         }
 
         if (STATS) st_hits = sh_nums;
+#if RTO_DEPTH
+        dsum *= 1.0f / SPP;
+#endif
+#if RTO_DEPTH && RTO_FAST_RAYS
+        if (sh_nums != 0 && rays.out) {  // (uniform: a call that asks for no colour shades nothing)
+#else
         if (sh_nums != 0) {
+#endif
             float basis_fn[RTO_BASIS_MAX_DEV];
             ray_basis<LOBES>(tree, opt, vdir, basis_fn);
             constexpr bool kLobes = LOBES != 0;  // (an SG / ASG tree's records are laid out as an SH tree's of the same data_dim)
@@ -307,11 +333,18 @@
             out[3] *= INV_SPP;
         }
     }
-#if RTO_FAST_RAYS
+#if RTO_FAST_RAYS && RTO_DEPTH
+    if (rays.out) write_ray(rays, ray, bg, out);
+    write_depth(dout, ray, dsum, tnear);
+    (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
+#elif RTO_FAST_RAYS
     write_ray(rays, ray, bg, out);
     (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
 #elif RTO_FAST_LAYERS
     write_pixel_over(fo, SIZE, idx, bg, out);
+#if RTO_DEPTH
+    write_depth(dout, (uint32_t)idx, dsum, tnear);
+#endif
     (void)st_steps, (void)st_levels, (void)st_hits, (void)st_inbox, (void)st_grid, (void)st_words, (void)st_wide;  // (STATS only)
 #else
     write_pixel(fo, SIZE, idx, opt.background_brightness, out);

@@ -2,10 +2,16 @@
 // render_rays_generic (RTO_GENERIC_RAYS defined to 1 around the include: the rays of rto_launch_rays) and render_generic_layers
 // (RTO_GENERIC_LAYERS defined to 1: a camera's pixels over the layers of rto_ctx_set_layers).  In scope: the kernel
 // parameters and SPP.  (The ray source is switched by the preprocessor: render_generic's text and code are unchanged.)
+// RTO_DEPTH defined to 1 as well (render_rays_generic_depth, render_generic_layers_depth): the distance of the ray's hits, d = t *
+// delta_scale at the top of the iteration that collides, goes to `dout` (DepthOut; include/rto.h "depth outputs").  This loop is
+// the reference's own arithmetic: its values define the two outputs.
 #if RTO_GENERIC_RAYS
     const uint32_t ray = ray_index(rays, blockIdx.x, threadIdx.x);
     if (ray >= rays.n) return;
     float out[4] = {0.f, 0.f, 0.f, 0.f};
+#if RTO_DEPTH
+    float dsum = 0.f, tnear = __builtin_inff();
+#endif
     float dir[3], vdir[3], cen[3], invdir[3], tmax_bg, bg[3];
     const bool live = ray_from_batch(rays, ray, tree, opt.background_brightness, dir, vdir, cen, tmax_bg, bg);  // (false: degenerate)
 
@@ -20,6 +26,9 @@
     if (idx >= SIZE) return;
     const int x = idx % cam.width, y = idx / cam.width;
     float out[4] = {0.f, 0.f, 0.f, 0.f};
+#if RTO_DEPTH
+    float dsum = 0.f, tnear = __builtin_inff();
+#endif
     float dir[3], vdir[3], cen[3], invdir[3], bg[3];
     layer_backdrop(layers, (uint32_t)idx, opt.background_brightness, bg);
     ray_setup(x, y, cam, tree, dir, vdir, cen);
@@ -89,13 +98,27 @@
                             ++cnt;
                             ++spp;
                         } while (src + delta >= dst[spp]);
+#if RTO_DEPTH
+                        {
+                            const float d = t * delta_scale;
+                            dsum += cnt * d;
+                            tnear = sh_nums == 1u ? d : tnear;  // (sh_nums counts this hit already)
+                        }
+#endif
                         if (spp == SPP) break;
                     }
                     src += delta;
                 }
                 t += delta_t;
             }
+#if RTO_DEPTH
+            dsum *= 1.0f / SPP;
+#endif
+#if RTO_DEPTH && RTO_GENERIC_RAYS
+            if (sh_nums != 0 && rays.out) {  // (uniform: a call that asks for no colour shades nothing)
+#else
             if (sh_nums != 0) {
+#endif
                 float basis_fn[RTO_BASIS_MAX_DEV];
                 ray_basis_any(tree, opt, vdir, basis_fn);
                 for (uint32_t i = 0; i < sh_nums; i++)
@@ -108,10 +131,16 @@
             }
         }
     }
-#if RTO_GENERIC_RAYS
+#if RTO_GENERIC_RAYS && RTO_DEPTH
+    if (rays.out) write_ray(rays, ray, bg, out);
+    write_depth(dout, ray, dsum, tnear);
+#elif RTO_GENERIC_RAYS
     write_ray(rays, ray, bg, out);
 #elif RTO_GENERIC_LAYERS
     write_pixel_over(fo, SIZE, idx, bg, out);
+#if RTO_DEPTH
+    write_depth(dout, (uint32_t)idx, dsum, tnear);
+#endif
 #else
     write_pixel(fo, SIZE, idx, opt.background_brightness, out);
 #endif

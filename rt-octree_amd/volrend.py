@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COptions, CQueryOut, CRays, CTreeInfo, RtoError, check, lib
+from ._lib import CCamera, COptions, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoError, check, lib
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
@@ -382,6 +382,30 @@ class RenderContext:
         check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
+    def enable_depth(self, on=True):
+        """rto_ctx_enable_depth: launch_renderer / launch_renderer_batch also write depth and t_near [frames, H, W] (include/rto.h
+        "depth outputs"); batches are then rendered frame by frame through the single-frame kernels"""
+        check(lib().rto_ctx_enable_depth(self._h, int(bool(on))))
+
+    def depth_enabled(self):
+        return bool(lib().rto_ctx_depth_enabled(self._h))
+
+    def depth_view(self):
+        """zero-copy view of the selected slot's depth plane [H, W]; None while disabled"""
+        p = lib().rto_ctx_depth(self._h)
+        return _DevArray(p, (self.height, self.width), self) if p else None
+
+    def t_near_view(self):
+        p = lib().rto_ctx_t_near(self._h)
+        return _DevArray(p, (self.height, self.width), self) if p else None
+
+    def download_depth(self, stream=None):
+        """(depth, t_near) of the selected slot, float32 [H, W] numpy arrays"""
+        d = np.empty((self.height, self.width), np.float32)
+        t = np.empty((self.height, self.width), np.float32)
+        check(lib().rto_ctx_download_depth(self._h, _stream_ptr(stream), C.c_void_p(d.ctypes.data), C.c_void_p(t.ctypes.data)))
+        return d, t
+
     def timer(self):
         return self._timer
 
@@ -554,11 +578,15 @@ def _ray_tensor(a, name, cols, n, device):
     return a
 
 
-def render_rays(tree, origins, dirs, options, ctx, t_max=None, background=None, first_ray=0, out=None, stream=None):
+def render_rays(tree, origins, dirs, options, ctx, t_max=None, background=None, first_ray=0, out=None, stream=None,
+                depth=False, t_near=False, rgba=True):
     """rto_launch_rays: colour and opacity of n arbitrary rays.  origins / dirs [n, 3], t_max [n] (world distance along the unit
     direction; None = 1e9), background [n, 3] (None = options.background_brightness): contiguous float32 torch tensors on the
     tree's device, or numpy arrays (copied over).  Returns out, a float32 [n, 4] tensor (r, g, b composited over the backdrop,
     alpha = accumulated opacity); pass `out` to fill one.  Ray i draws its samples from ctx.rng advanced by (first_ray + i) * spp.
+    depth / t_near (rto_launch_rays_ex; include/rto.h "depth outputs"): when either is asked for the result is the tuple (out,
+    depth [n], t_near [n]) without the ones not asked for, in that order.  rgba=False (with depth or t_near): no colour is asked
+    for -- the kernel skips the shading -- and the tuple holds the depth outputs only; `out` must then be None.
     Asynchronous on `stream` (default: torch's current stream); no sync."""
     import torch
     device = torch.device("cuda", tree.device)
@@ -567,12 +595,19 @@ def render_rays(tree, origins, dirs, options, ctx, t_max=None, background=None, 
     d = _ray_tensor(dirs, "dirs", 3, n, device)
     tm = None if t_max is None else _ray_tensor(t_max, "t_max", 0, n, device)
     bg = None if background is None else _ray_tensor(background, "background", 3, n, device)
-    if out is None:
+    if not rgba:
+        if not (depth or t_near):
+            raise RtoError(-1, "render_rays: no output asked for")
+        if out is not None:
+            raise RtoError(-1, "render_rays: rgba=False takes no `out`")
+    elif out is None:
         out = torch.empty((n, 4), dtype=torch.float32, device=device)
     else:
         out = _ray_tensor(out, "out", 4, n, device)
+    extra = [torch.empty((n,), dtype=torch.float32, device=device) if want else None for want in (depth, t_near)]
+    res = out if not (depth or t_near) else tuple(([out] if rgba else []) + [e for e in extra if e is not None])
     if n == 0:
-        return out
+        return res
     if stream is None:
         stream = torch.cuda.current_stream(device)
     r = CRays()
@@ -581,8 +616,15 @@ def render_rays(tree, origins, dirs, options, ctx, t_max=None, background=None, 
     r.background = bg.data_ptr() if bg is not None else None
     r.n, r.first_ray = n, int(first_ray)
     co = options.to_c()
-    check(lib().rto_launch_rays(tree._h, C.byref(r), C.byref(co), ctx._h, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
-    return out
+    if not (depth or t_near):
+        check(lib().rto_launch_rays(tree._h, C.byref(r), C.byref(co), ctx._h, C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+        return out
+    ro = CRaysOut()
+    ro.rgba = out.data_ptr() if rgba else None
+    ro.depth = extra[0].data_ptr() if extra[0] is not None else None
+    ro.t_near = extra[1].data_ptr() if extra[1] is not None else None
+    check(lib().rto_launch_rays_ex(tree._h, C.byref(r), C.byref(co), ctx._h, C.byref(ro), _stream_ptr(stream)))
+    return res
 
 
 def _dev_ptr(t):
