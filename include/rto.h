@@ -443,13 +443,27 @@ int rto_launch_rays_ex(const rto_tree* tree, const rto_rays* rays, const rto_opt
  *     render_generic_layers_depth).  Pixel (x, y) equals, bit for bit, ray y * W + x of rto_launch_rays_ex on the camera's rays
  *     (origin = the camera centre, direction = M xyz) with t_max = the depth layer's value there, as rto_ctx_set_layers states
  *     for the colour.
- *   rto_launch_renderer_batch renders its frames ONE BY ONE through those kernels (the persistent batched kernels carry no
- *     depth): frame f into slot f with the RNG advanced by rng_jumps[f] * 2^32, the same bytes as n single launches.  Like any
- *     single-frame launch it leaves no tile marks (rto_ctx_tile_marks: RTO_E_INVALID) and writes full outputs; a lean level
+ *   rto_launch_renderer_batch, enable == 1 (or any non-zero value but RTO_DEPTH_BATCHED), renders its frames ONE BY ONE through
+ *     those kernels: frame f into slot f with the RNG advanced by rng_jumps[f] * 2^32, the same bytes as n single launches.  Like
+ *     any single-frame launch it leaves no tile marks (rto_ctx_tile_marks: RTO_E_INVALID) and writes full outputs; a lean level
  *     other than 0 is RTO_E_UNSUPPORTED.
- *   RTO_E_UNSUPPORTED: options->enable_probe, rto_ctx_enable_stats, a tree loaded with RTO_TREE_QUANT_DIRECT (what the layers
- *     refuse).
+ *   rto_launch_renderer_batch, enable == RTO_DEPTH_BATCHED, sends the batch through the persistent kernels like a batch of a context
+ *     without depth outputs; the traversal kernel (render_persist_depth, the default tuning's) also accumulates the two outputs.
+ *     Frame f's aux, image, depth and t_near in slot f are bit for bit what enable == 1 writes, and the planes of the launch's
+ *     slots are first filled with (0, +inf) on the stream (no synchronisation; other slots keep their contents).  The launch
+ *     leaves tile marks, takes lean levels 1 and 2 and lets rto_denoise take its culled routes under the rules of an ordinary
+ *     batch (no marks and no level 2 over a colour layer).  A launch the persistent kernels cannot take -- a tree without
+ *     traversal image, more leaf slots than a hit entry names at this spp, tuning key "batch_fallback" 1, or the device refusing the
+ *     traversal kernel's LDS ("batch_fallback" 2) -- goes frame by frame as with enable == 1: no marks, and with a lean level
+ *     other than 0 RTO_E_UNSUPPORTED before anything is rendered (a caller that set one turns it off and launches again:
+ *     volrend_headless --write_depth does, and keeps full outputs from then on).
+ *   rto_launch_renderer behaves the same in both modes.
+ *   RTO_E_UNSUPPORTED in both modes: options->enable_probe, rto_ctx_enable_stats, a tree loaded with RTO_TREE_QUANT_DIRECT (what
+ *     the layers refuse).
+ * Calling it on an enabled context with the other non-zero value changes the mode only: no allocation, no synchronisation, the
+ * planes keep their contents.  rto_ctx_depth_enabled returns the mode: 0, 1 or RTO_DEPTH_BATCHED.
  * While disabled nothing on the context behaves differently.  rto_launch_rays / _ex do not touch the context's planes. */
+#define RTO_DEPTH_BATCHED 2
 int rto_ctx_enable_depth(rto_ctx* c, int enable);
 int rto_ctx_depth_enabled(const rto_ctx* c);
 float* rto_ctx_depth(rto_ctx* c);  /* device, the selected slot's plane [H][W]; NULL while disabled */

@@ -116,7 +116,8 @@ void usage() {
         "  -o,--write_images DIR   write r_<i>.png (or buf_<name>.bin with --write_buffer)\n"
         "  --write_buffer  --max_imgs N  --scale S  -i intrin  -r,--reverse_yz\n"
         "  --write_depth      with -o: also write depth_<name>.bin per pose, float32 [2][H][W] = depth, t_near (rto.h \"depth\n"
-        "                     outputs\"); renders one launch per frame (as --batch 1)\n"
+        "                     outputs\"); batches go through the persistent kernels (rto_ctx_enable_depth, RTO_DEPTH_BATCHED);\n"
+        "                     a tree or launch those cannot take is rendered frame by frame, with full outputs\n"
         "  --shard i/N        render poses i, i+N, ... only     --warmup K (100)\n"
         "  --gpus N           frames sharded over N GPUs of this node: N child processes (--shard i/N, GPU i each), one\n"
         "                     report for their union; images do not depend on N (per-pose RNG jump-ahead)\n"
@@ -401,7 +402,6 @@ int main(int argc, char** argv) {
 
     int batch = std::max(1, std::min(128, std::atoi(args.get("batch", "100").c_str())));
     const int filter_mode = args.has("fast_filter") ? RTO_FILTER_FACTORISED : RTO_FILTER_EXACT;
-    if (write_depth) batch = 1;  // (the depth outputs come from the single-frame kernels: the per-frame loop below)
     {  // no more frame slots than this process has poses to render
         const size_t n_mine = (ps.trans.size() + (size_t)shard_n - 1 - (size_t)shard_i) / (size_t)shard_n;
         if ((size_t)batch > n_mine) batch = (int)std::max<size_t>(1, n_mine);
@@ -412,7 +412,9 @@ int main(int argc, char** argv) {
     }
     rto_ctx* ctx = nullptr;
     CHECK_RTO(rto_ctx_create_batch(width, height, batch, device, &ctx));
-    if (write_depth) CHECK_RTO(rto_ctx_enable_depth(ctx, 1));
+    // (depth outputs: batches through the persistent kernels; the per-frame loop's launches are the same in either mode)
+    if (write_depth) CHECK_RTO(rto_ctx_enable_depth(ctx, RTO_DEPTH_BATCHED));
+    std::printf("INFO: %d poses per launch\n", batch);
 
     std::unique_ptr<rto::TorchDenoiser> denoiser;
     if (options.denoise) {
@@ -498,7 +500,11 @@ int main(int argc, char** argv) {
     if (write_depth) depth2.resize((size_t)width * height * 2);
     // Batched launches whose aux planes nobody reads store the 16 bytes per pixel the fused denoise stage consumes instead of the
     // reference's 48 (rto_ctx_set_lean_outputs; same PNGs).  --write_buffer dumps the aux planes, the TorchScript module reads them.
-    if (batch > 1 && options.denoise && denoiser && denoiser->fused() && !write_buffer) CHECK_RTO(rto_ctx_set_lean_outputs(ctx, 1));
+    bool lean_on = false;
+    if (batch > 1 && options.denoise && denoiser && denoiser->fused() && !write_buffer) {
+        CHECK_RTO(rto_ctx_set_lean_outputs(ctx, 1));
+        lean_on = true;
+    }
 
     if (batch > 1) {
         // throughput form of the loop below: groups of `batch` poses per launch.  ctx.rng stays at its
@@ -519,7 +525,16 @@ int main(int argc, char** argv) {
             }
             rto_ctx_select_frame(ctx, 0);
             rto_timer_start(ctx, RTO_T_RENDER);
-            CHECK_RTO(rto_launch_renderer_batch(tree, cams.data(), jumps.data(), n, &options, ctx, stream));
+            int launched = rto_launch_renderer_batch(tree, cams.data(), jumps.data(), n, &options, ctx, stream);
+            if (launched == RTO_E_UNSUPPORTED && write_depth && lean_on) {
+                // --write_depth on a launch the persistent kernels cannot take (an N != 2 tree, too many leaf slots for the spp, the
+                // traversal kernel's LDS refused): the context renders it frame by frame, which stores full outputs only and
+                // refuses the lean level before anything is rendered.  Full outputs from here on, and the same launch again
+                CHECK_RTO(rto_ctx_set_lean_outputs(ctx, 0));
+                lean_on = false;
+                launched = rto_launch_renderer_batch(tree, cams.data(), jumps.data(), n, &options, ctx, stream);
+            }
+            CHECK_RTO(launched);
             rto_timer_stop(ctx, RTO_T_RENDER);
             if (options.denoise) CHECK_RTO(denoise_n(n, true, true));
             CHECK_RTO(rto_timer_record(ctx, options.denoise));
@@ -536,6 +551,16 @@ int main(int argc, char** argv) {
                     CHECK_RTO(rto_ctx_download_rgba8(ctx, stream, 0, rgba8.data()));
                     if (!rto::write_png_rgba8(out_dir + "/" + ps.basenames[i] + ".png", rgba8.data(), width, height)) {
                         std::fprintf(stderr, "ERROR: cannot write %s/%s.png\n", out_dir.c_str(), ps.basenames[i].c_str());
+                        return 1;
+                    }
+                }
+                if (write_depth) {
+                    CHECK_RTO(rto_ctx_download_depth(ctx, stream, depth2.data(), depth2.data() + (size_t)width * height));
+                    std::ofstream fd(out_dir + "/depth_" + ps.basenames[i] + ".bin", std::ios::binary);
+                    fd.write(reinterpret_cast<const char*>(depth2.data()), (std::streamsize)(depth2.size() * sizeof(float)));
+                    fd.close();
+                    if (!fd) {
+                        std::fprintf(stderr, "ERROR: cannot write %s/depth_%s.bin\n", out_dir.c_str(), ps.basenames[i].c_str());
                         return 1;
                     }
                 }

@@ -39,8 +39,8 @@ __global__ void __launch_bounds__(256) render_generic_layers_depth(const TreeDev
 }
 
 // The depth-carrying forms of render_rays and render_fast_layers (RTO_DEPTH; DepthOut behind their siblings' arguments).  One frame family
-// serves offscreen and layered contexts: both layer pointers null is the offscreen frame.  render_persist has none: its hit
-// hand-off has no room for t.
+// serves offscreen and layered contexts: both layer pointers null is the offscreen frame.  (render_persist's depth form is
+// render_persist_depth below: its hit hand-off has no room for t, so the traversal kernel itself accumulates.)
 // Waves per SIMD the two kernels are built for: their siblings' (RTO_FAST_WPS up to SPP 8, 4 above), one less where the two more
 // live registers would otherwise go to the private segment -- render_rays at SPP 8 on the two-level image already keeps 8 bytes
 // per lane at 5 waves, and the SPP-32 forms 132-136 at 4; with one wave less the depth forms hold no more than their siblings
@@ -73,7 +73,46 @@ __global__ void __launch_bounds__(256, depth_frame_wps(SPP)) render_fast_layers_
 #undef RTO_FAST_LAYERS
 }
 
+// The depth-carrying form of render_persist_layers (rto_ctx_enable_depth(RTO_DEPTH_BATCHED)): the layered body of
+// the batched traversal with RTO_DEPTH -- at a hit the ray adds (float)cnt * (t * delta_scale) to a sum and keeps its first hit's
+// distance, both in two LDS rows of their own, and stores its pixel's depth and t_near when its hit list leaves (DepthOut: plane f
+// = batch frame f).  Both layer pointers null is the offscreen batch.  The shading kernels take no part in it.  Instantiated for the
+// default tuning only (REFILL 32, RTO_WPS_DEFAULT waves per SIMD), as render_persist_layers is.
+// Waves per SIMD: the sibling's WPS, one less for the SPP-32 forms on the two-level image -- their 32-entry flush already keeps
+// 56-64 bytes per lane at 8 waves, and the depth store beside it 4-12 more; with 72 registers they hold less than the sibling
+// (tests/test_depth_batch.py::test_depth_batch_codegen).
+constexpr int persist_depth_wps(int spp, int wps, bool wide) { return spp == 32 && wide ? wps - 1 : wps; }
+template <int SPP, int REFILL, int WPS, bool WIDE, int STACK>
+__global__ void __launch_bounds__(256, persist_depth_wps(SPP, WPS, WIDE)) render_persist_depth(const TreeDev tree, const OptDev opt, const FrameBatch fb,
+                                                             unsigned long long* __restrict__ queue,
+                                                             uint32_t* __restrict__ hits, const uint32_t chunk, const LayerDev layers,
+                                                             const DepthOut dout) {
+#define RTO_PERSIST_LAYERS 1
+#define RTO_DEPTH 1
+#include "rto_render_persist.inc"
+#undef RTO_DEPTH
+#undef RTO_PERSIST_LAYERS
+}
+
 // ------------------------------------------------------------------ launchers (declared in rto_depth_launch.h)
+
+template <int SPP, bool WIDE>
+const void* persist_depth_kernel(bool regstack) {
+    return regstack ? reinterpret_cast<const void*>(&render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, WIDE ? 1 : 0>)
+                    : reinterpret_cast<const void*>(&render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, 0>);
+}
+
+template <int SPP, bool WIDE>
+void launch_persist_depth(bool regstack, int grid, size_t lds, hipStream_t stream, const TreeDev& tree, const OptDev& opt,
+                          const FrameBatch& fb, unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers,
+                          const DepthOut& depth) {
+    if (regstack)
+        hipLaunchKernelGGL((render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, WIDE ? 1 : 0>), dim3(grid), dim3(256), lds, stream, tree, opt,
+                           fb, queue, hits, chunk, layers, depth);
+    else
+        hipLaunchKernelGGL((render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
+                           hits, chunk, layers, depth);
+}
 
 template <int SPP, int LOBES>
 void launch_fast_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
@@ -132,9 +171,16 @@ void launch_rays_depth_generic(const TreeDev& tree, const OptDev& opt, const Pcg
                                             const DepthOut&, hipStream_t);                                                              \
     template void launch_rays_depth_generic<SPP>(const TreeDev&, const OptDev&, const Pcg32&, const RayBatch&, const DepthOut&, dim3,   \
                                                  hipStream_t);                                                                          \
+    template const void* persist_depth_kernel<SPP, true>(bool);                                                                         \
+    template const void* persist_depth_kernel<SPP, false>(bool);                                                                        \
+    RTO_DEPTH_INSTANCES_P(SPP, true)                                                                                                    \
+    RTO_DEPTH_INSTANCES_P(SPP, false)                                                                                                   \
     RTO_DEPTH_INSTANCES_L(SPP, 0)                                                                                                       \
     RTO_DEPTH_INSTANCES_L(SPP, kFmtSG)                                                                                                  \
     RTO_DEPTH_INSTANCES_L(SPP, kFmtASG)
+#define RTO_DEPTH_INSTANCES_P(SPP, WI)                                                                                                  \
+    template void launch_persist_depth<SPP, WI>(bool, int, size_t, hipStream_t, const TreeDev&, const OptDev&, const FrameBatch&,        \
+                                                unsigned long long*, uint32_t*, uint32_t, const LayerDev&, const DepthOut&);
 #define RTO_DEPTH_INSTANCES_L(SPP, L)                                                                                                   \
     template void launch_fast_depth<SPP, L>(const TreeDev&, const CamDev&, const OptDev&, const Pcg32&, const PcgJumpEntry*,            \
                                             const FrameOut&, int, const LayerDev&, const DepthOut&, hipStream_t);                       \
@@ -151,6 +197,7 @@ RTO_DEPTH_INSTANCES(32)
 #endif
 RTO_DEPTH_INSTANCES(6)
 #undef RTO_DEPTH_INSTANCES_L
+#undef RTO_DEPTH_INSTANCES_P
 #undef RTO_DEPTH_INSTANCES
 
 }  // namespace rto

@@ -247,29 +247,7 @@ __global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_
 //   * the end-of-queue drain happens once per batch instead of once per frame.
 // Per-ray arithmetic is exactly render_fast's; results are bit-identical.
 
-// the per-ray state that survives between march steps (thresholds live in LDS, hits go straight
-// to the hand-off buffer)
-struct RayState {
-    float cen[3], dir[3], invdir[3];
-    float pos[3];  // 2^24 * clamp(cen + t * dir, 0, 1 - 1e-6): the point the next march step starts from (scaled: kPos24)
-    float delta_scale, t, tmax, src, cur;      // cur = next threshold to cross (dst[spp])
-    uint32_t spp;
-    uint32_t pix, piy, piz;
-    int prev_lvl;   // level of the node about to be visited
-    uint32_t hoff, hnext;  // index of this pixel's next free hit entry in the hand-off buffer, and of the one behind it
-                           // (staged hit lists, the default: of its entries 0 and 1, fixed for the ray's life)
-    uint32_t nh;           // staged hit lists: hit entries of this ray parked in LDS, not yet written out
-    uint32_t node;  // node about to be visited; kGridNext = the top grid is visited next (two-level image: 0 = the grid)
-    uint32_t woff;  // two-level image: lowest of the coordinate bits that index the node about to be visited
-    uint32_t wb;    // two-level image: coordinate bits per axis that index it -- G at the grid, 2 at a wide node (round 5: kept with
-                    // the ray instead of re-derived from `node` by a compare + select in every iteration)
-    float cxy __attribute__((ext_vector_type(2)));  // cen[0], cen[1] as a register pair for the packed march arithmetic
-    // _dda_unit's max(t1, t1 + invdir) per axis is t1 + (invdir > 0 ? invdir : 0): the sign of invdir is the ray's, not the
-    // step's (exit_add below)
-    float exit_add[3];
-};
-constexpr uint32_t kGridNext = 0xffffffffu;
-constexpr int kCamFloats = 14;  // fx, fy, transform[12]: what a ray set-up reads of a FrameDesc
+// (RayState, kGridNext, kCamFloats: rto_render_shared.h -- depth_kernels.hip's render_persist_depth is the same body)
 
 // ------------------------------------------------------------------ empty-space culling + ray queues (round 3)
 // A ray that never meets a leaf of positive density composites nothing: its pixel is the background, its hit list empty
@@ -559,34 +537,7 @@ __global__ void __launch_bounds__(64 * kSampleWaves) sample_kernel(const FrameBa
     }
 }
 
-// Staged hit lists (round 4, VERDICT r3 task 5; -DRTO_HITS_DIRECT restores the store per hit): a ray's hit entries wait in LDS -- in the rows of its threshold column that
-// its consumed thresholds left free -- and are written to the hand-off buffer when the ray has ended: entry 0 into the dense
-// plane, entries 1.. as one contiguous run (4 * (n - 1) bytes of ONE 32-byte sector for SPP <= 9), back to back, instead of
-// one 4-byte store per hit at the moment it happens (71.6 M scattered dwords per 100 frames cost 2.48 GB of line-granular
-// HBM writes for 0.29 GB of payload: the L2 had evicted the sector long before the pixel's next entry arrived).
-template <int SPP, bool WIDE>
-RTO_DEV void flush_hits(RayState& rs, const TreeDev& tree, uint32_t* __restrict__ hits, const float* s_col, uint32_t hstride,
-                        bool translate = true) {
-    uint32_t e[SPP];
-#pragma unroll
-    for (int i = 0; i < SPP; ++i) {
-        e[i] = 0u;
-        if ((uint32_t)i < rs.nh) {
-            e[i] = __float_as_uint(s_col[i * 256]);
-            if constexpr (WIDE) {
-                constexpr uint32_t smask = (1u << hit_slot_bits(SPP)) - 1u;
-                // (off the march loop: the ray has ended; !translate: entry-ordered records, TreeDev::rec_by_entry -- the entry IS the record)
-                if (translate) e[i] = (e[i] & ~smask) | wide_to_slot(tree, e[i] & smask);
-            }
-        }
-    }
-    hits[rs.hoff] = e[0];
-    uint32_t* tp = hits + rs.hnext;
-#pragma unroll
-    for (int i = 1; i < SPP; ++i)
-        if ((uint32_t)i < rs.nh) tp[(uint32_t)(i - 1) * hstride] = e[i];
-    rs.nh = 0;
-}
+// (flush_hits, the staged hit lists of a ray: rto_render_shared.h)
 
 // REFILL = idle lanes that trigger a retire + refill round
 // Flat traversal: one node visit (one load) per lane per loop iteration -- a lane either descends one level or,
@@ -1018,12 +969,7 @@ hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev&
     }
 }
 
-// Waves per SIMD the default instantiation is built for.  Round 3: 7 (72 VGPRs).  Round 4: 8 (64 VGPRs; the spills this forces are
-// in the ray set-up) -- with the shorter two-level loop one more resident wave is worth more than the spills cost: C2 4.69 -> 4.57,
-// C4 13.27 -> 12.71, C5 2.96 -> 2.88 ms per 100 frames in one box (profiles/r4_u_ab_wps8.txt).  Tuning key refill = 732: the 7-wave build.
-#ifndef RTO_WPS_DEFAULT
-#define RTO_WPS_DEFAULT 8
-#endif
+// (RTO_WPS_DEFAULT, the waves per SIMD the default instantiation is built for: rto_render_shared.h)
 // the shading kernel of an SG / ASG tree (LOBES = kFmtSG / kFmtASG): the SH modes of the same record layouts
 template <int SPP, int SP, int LOBES>
 static void launch_shade_lobes(const dim3 sgrid, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb, const uint32_t* hits,
@@ -1059,17 +1005,22 @@ static void launch_shade_layers(const dim3 sgrid, const TreeDev& tree, const Opt
 
 // LAYERS: the launch may carry layers (`layers` != nullptr: rto_ctx_set_layers) -- a depth layer takes render_persist_layers, a
 // colour layer shade_kernel_layers; instantiated for the default tuning only
+// depth != nullptr (LAYERS only; rto_ctx_enable_depth(RTO_DEPTH_BATCHED)): the traversal is render_persist_depth, over the layers or
+// none, through the launcher of depth_kernels.hip; its planes are filled with (0, +inf) on the stream first.  Marks, queues,
+// thresholds and shading are what they are without
 template <int SPP, int REFILL, int WPS, bool WIDE, bool LAYERS = false>
 static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                     const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
                                     int chunk_override, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream,
-                                    const LayerDev* layers = nullptr) {
+                                    const LayerDev* layers = nullptr, const DepthOut* depth = nullptr) {
     // dynamic LDS: ancestor stack + thresholds per lane, then the frame table of THIS batch (96 B per frame: a batch of
     // one does not pay for 128)
     // (two pairs of levels below the grid at most: the ancestor stack is two registers and its LDS rows only park a ray's two
     //  hand-off offsets)
     const bool regstack = WIDE && (tree.max_depth - tree.top_levels + 1) / 2 <= 2;
-    const size_t lds = (size_t)((regstack ? 2 : tree.max_depth + 1 - tree.top_levels) + SPP + 1) * 256 * sizeof(uint32_t) + sizeof(float) * kCamFloats * (size_t)fb.n;
+    bool with_depth = false;  // (two more rows, the ray's hit distances; without the register stack four: rto_render_persist.inc)
+    if constexpr (LAYERS) with_depth = depth != nullptr;
+    const size_t lds = (size_t)((regstack ? 2 : tree.max_depth + 1 - tree.top_levels) + SPP + 1 + (with_depth ? (regstack ? 2 : 4) : 0)) * 256 * sizeof(uint32_t) + sizeof(float) * kCamFloats * (size_t)fb.n;
     const auto kern = regstack ? &render_persist<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0> : &render_persist<SPP, REFILL, WPS, WIDE, 0>;
     const void* fn = reinterpret_cast<const void*>(kern);
     bool depth_layer = false, color_layer = false;
@@ -1079,6 +1030,7 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
         if (depth_layer)
             fn = regstack ? reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>)
                           : reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, 0>);
+        if (with_depth) fn = persist_depth_kernel<SPP, WIDE>(regstack);  // (the occupancy query and the LDS request below are this kernel's)
     }
     OccupancyCache local;
     if (!occ) occ = &local;
@@ -1121,6 +1073,16 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     uint32_t* mask = const_cast<uint32_t*>(fb.tile_mask);
     const size_t mask_bytes = (size_t)fb.n * fb.mask_words * sizeof(uint32_t);
     if (hipMemsetAsync(mask, cull ? 0 : 0xff, mask_bytes, stream) != hipSuccess) return hipErrorLaunchFailure;
+    if constexpr (LAYERS) {
+        // a pixel whose ray never flushes -- culled tile, box miss, dead depth-layer pixel, no hit -- reads (0, +inf): the planes of
+        // the launch's slots are filled on the stream before the traversal stores the others (0x7f800000 = +inf)
+        if (with_depth) {
+            const size_t n_px = (size_t)fb.n * (size_t)fb.width * (size_t)fb.height;
+            if (hipMemsetAsync(depth->depth, 0, n_px * sizeof(float), stream) != hipSuccess ||
+                hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(depth->t_near), 0x7f800000, n_px, stream) != hipSuccess)
+                return hipErrorLaunchFailure;
+        }
+    }
     if (cull && tree.n_occ_cells > 0) {
         const dim3 mgrid((unsigned)((tree.n_occ_cells + kMarkCells - 1) / kMarkCells), fb.n);
         if (fb.mask_words <= kMarkLdsWords)
@@ -1135,7 +1097,10 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     hipLaunchKernelGGL(sample_kernel<SPP>, dim3((unsigned)(((tiles / fb.n + kSampleTiles - 1) / kSampleTiles + kSampleWaves - 1) / kSampleWaves), fb.n), dim3(64 * kSampleWaves), 0, stream, fb, jump);
     if (ev) (void)hipEventRecord(ev[1], stream);
     if constexpr (LAYERS) {
-        if (depth_layer) {
+        if (with_depth) {
+            launch_persist_depth<SPP, WIDE>(regstack, grid, lds, stream, tree, opt, fb, queue, hits, chunk,
+                                            layers ? *layers : LayerDev{nullptr, nullptr}, *depth);
+        } else if (depth_layer) {
             const LayerDev ld = *layers;
             if (regstack)
                 hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb,
@@ -1145,7 +1110,7 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
                                    hits, chunk, ld);
         }
     }
-    if (!depth_layer) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
+    if (!depth_layer && !with_depth) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
     if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
     if (ev) (void)hipEventRecord(ev[2], stream);
 #ifndef RTO_SHADE_P
@@ -1198,7 +1163,8 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
 template <int SPP>
 static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                    const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                                   int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream) {
+                                   int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, const DepthOut* depth,
+                                   hipStream_t stream) {
     // tuning: refill = 1000 * tiles_per_dequeue + 100 * waves/SIMD + threshold
     refill %= 100000;
     const int chunk_override = (refill / 1000) * 64;
@@ -1206,7 +1172,7 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     const bool wide = tree.widew != nullptr;
     if constexpr (SPP == 6) {  // tuning instantiations only for the benchmark configuration (and its usual two-level image)
 #define RTO_F(R, O) return launch_batch_impl<SPP, R, O, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream)
-        if (wide && !layers) switch (refill) {  // (a layered launch: the default instantiation whatever the key's A/B part says)  // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
+        if (wide && !layers && !depth) switch (refill) {  // (a layered launch: the default instantiation whatever the key's A/B part says)  // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
             case 808: RTO_F(8, 8);
             case 816: RTO_F(16, 8);
             case 824: RTO_F(24, 8);
@@ -1232,10 +1198,10 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     // memory: host/tree_layout.cpp build_wide_image), else the one-level image: the same pixels either way.
     // (Round 5's reservoir kernel -- whole-tile set-up, rays parked in LDS, refill rounds at 8-24 idle lanes -- lost its same-box
     //  A/B, 4.27-4.32 against 4.11-4.20 ms per 100 C2 frames, and lives in tools/experiments/r5_lab_switches.patch.)
-    if (layers) {
+    if (layers || depth) {  // (depth outputs: the default instantiation too, render_persist_depth has no other)
         if (wide)
-            return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers);
-        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers);
+            return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers, depth);
+        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers, depth);
     }
     if (wide)
         return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
@@ -1244,19 +1210,20 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
 
 hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream) {
+                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, const DepthOut* depth,
+                               hipStream_t stream) {
     switch (spp) {
 #ifndef RTO_DEV_SPP6_ONLY  // (development builds: compile the benchmark's instantiation only)
-        case 1: return launch_batch_spp<1>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
-        case 2: return launch_batch_spp<2>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
-        case 3: return launch_batch_spp<3>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
-        case 4: return launch_batch_spp<4>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 1: return launch_batch_spp<1>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+        case 2: return launch_batch_spp<2>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+        case 3: return launch_batch_spp<3>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+        case 4: return launch_batch_spp<4>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
 #endif
-        case 6: return launch_batch_spp<6>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 6: return launch_batch_spp<6>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
 #ifndef RTO_DEV_SPP6_ONLY
-        case 8: return launch_batch_spp<8>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
-        case 16: return launch_batch_spp<16>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
-        case 32: return launch_batch_spp<32>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, stream);
+        case 8: return launch_batch_spp<8>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+        case 16: return launch_batch_spp<16>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+        case 32: return launch_batch_spp<32>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
 #endif
         default: return hipErrorInvalidValue;
     }

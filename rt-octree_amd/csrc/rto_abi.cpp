@@ -387,7 +387,13 @@ int rto_ctx_layers(const rto_ctx* c, const float** depth, const float** color) {
 
 int rto_ctx_enable_depth(rto_ctx* c, int enable) {
     if (!c) return set_err(RTO_E_INVALID, "rto_ctx_enable_depth: null context");
-    if ((enable != 0) == (c->depth != nullptr)) return RTO_OK;
+    // (1 = frame by frame, RTO_DEPTH_BATCHED = through the persistent kernels, anything else non-zero = 1; between the two the
+    //  planes stay: the mode is all that changes)
+    const int mode = enable == 0 ? 0 : enable == RTO_DEPTH_BATCHED ? RTO_DEPTH_BATCHED : 1;
+    if ((enable != 0) == (c->depth != nullptr)) {
+        c->depth_mode = mode;
+        return RTO_OK;
+    }
     DeviceGuard guard(c->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     if (!enable) {  // (launches in flight may still write the planes)
@@ -395,6 +401,7 @@ int rto_ctx_enable_depth(rto_ctx* c, int enable) {
         float* const d = c->depth;
         float* const t = c->t_near;
         c->depth = c->t_near = nullptr;
+        c->depth_mode = 0;
         const hipError_t e1 = hipFree(d), e2 = hipFree(t);  // (both planes, whatever the first call says)
         if (e1 != hipSuccess || e2 != hipSuccess)
             return set_err(RTO_E_HIP, std::string("hipFree(depth outputs): ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
@@ -415,9 +422,10 @@ int rto_ctx_enable_depth(rto_ctx* c, int enable) {
     }
     c->depth = d;
     c->t_near = t;
+    c->depth_mode = mode;
     return RTO_OK;
 }
-int rto_ctx_depth_enabled(const rto_ctx* c) { return c && c->depth ? 1 : 0; }
+int rto_ctx_depth_enabled(const rto_ctx* c) { return c && c->depth ? c->depth_mode : 0; }
 float* rto_ctx_depth(rto_ctx* c) { return c && c->depth ? c->depth + (size_t)c->sel * frame_px(c) : nullptr; }
 float* rto_ctx_t_near(rto_ctx* c) { return c && c->t_near ? c->t_near + (size_t)c->sel * frame_px(c) : nullptr; }
 

@@ -24,4 +24,15 @@ template <int SPP>
 void launch_rays_depth_generic(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb, const DepthOut& depth,
                                dim3 grid, hipStream_t stream);
 
+// render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, STACK> (the batched traversal with depth outputs, default tuning only), for
+// launch_batch_impl: the kernel a launch takes -- regstack: STACK = 1, the two-level image's register-stack form -- as the identity
+// its OccupancyCache, occupancy query and dynamic-LDS request go by, and its launch.  lds: launch_batch_impl's size, which counts
+// the kernel's two more rows.  layers: both pointers null = offscreen.  depth: plane f = batch frame f, both pointers set.
+template <int SPP, bool WIDE>
+const void* persist_depth_kernel(bool regstack);
+template <int SPP, bool WIDE>
+void launch_persist_depth(bool regstack, int grid, size_t lds, hipStream_t stream, const TreeDev& tree, const OptDev& opt,
+                          const FrameBatch& fb, unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers,
+                          const DepthOut& depth);
+
 }  // namespace rto

@@ -131,6 +131,7 @@ struct rto_ctx {
     // rto_ctx_enable_depth: the depth outputs of the frame slots, [frames][H][W] each; both null = disabled
     float* depth = nullptr;
     float* t_near = nullptr;
+    int depth_mode = 0;  // 0 disabled, 1 batches frame by frame, RTO_DEPTH_BATCHED batches through render_persist_depth
     float* probe_coeffs = nullptr;       // kProbeFloats: the probe point's leaf coefficients of the launch in flight (enable_probe)
     uint8_t* rgba8 = nullptr;
     rto::Pcg32 rng{};

@@ -68,9 +68,13 @@ struct OccupancyCache {
 // persistent batched renderer (N == 2 trees): fb.n frames in one launch (traversal kernel, then the
 // shading kernel); layers != nullptr (rto_ctx_set_layers): frame f stops at plane f of layers->depth and is composited over plane
 // f of layers->color, by the layered kernels of the default tuning (the A/B part of `refill` is then ignored); `queue` = kQueueWords u64 (zeroed by queue_scan_kernel on the stream before every traversal launch); ev = nullptr or 4 events recorded before the thresholds kernel, before / after the traversal, after the shading
+// depth != nullptr (rto_ctx_enable_depth(RTO_DEPTH_BATCHED)): the traversal is render_persist_depth (depth_kernels.hip; default tuning,
+// over `layers` or none), which also stores pixel p of frame f's depth / t_near at index f * W * H + p of depth's planes; the
+// launch first fills those fb.n planes with (0, +inf) on the stream, for the pixels whose ray has no hit
 hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
-                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, hipStream_t stream);
+                               int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, const DepthOut* depth,
+                               hipStream_t stream);
 
 // quant_map [nq][ns] + data_retained [nr][ns][3] -> slot-major records of `rec` u16 (TreeDev::qrec)
 hipError_t launch_pack_quant(const uint16_t* qmap, const uint16_t* retained, int64_t ns, int nr, int nq, int rec,

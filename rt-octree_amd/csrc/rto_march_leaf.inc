@@ -1,6 +1,6 @@
 // The march step of render_persist at a leaf (rt_core.cuh:241-270) + the choice of the next step's restart node.
 // Included into the kernel's loop body; expects in scope: rs, w (the leaf's
-// word), slot, active, s_dst, stack, stack_g, step_size, sigma_thresh, G, SPP, WIDE, kStackInRegs (compile time:
+// word), slot, active, s_dst, (RTO_DEPTH: s_acc,) stack, stack_g, step_size, sigma_thresh, G, SPP, WIDE, kStackInRegs (compile time:
 // the ancestor stack is the two registers stk0 / stk1), regstack (the same, possibly a run-time value).
                     RTO_DBG_AT(2)
                     // (WIDE: a wide entry, or a grid entry of the wide image, carries its leaf's level)
@@ -56,6 +56,14 @@
                             // k < spp (every hit crosses at least one threshold; row 0 never held one).  The list leaves in one go
                             // when the ray has ended (flush_hits; one store per hit at the moment it happens wrote 3x the bytes)
                             s_dst[rs.nh * 256] = __uint_as_float(hit_pack<SPP>(slot, cnt));
+#if RTO_DEPTH
+                            {   // the hit's distance (include/rto.h "depth outputs"): rs.t is the step's own, unscaled in every form.
+                                // Every product and the add rounded; the sum left to right from 0.f
+                                const float d = rs.t * rs.delta_scale;
+                                s_acc[0] = (rs.nh == 0u ? 0.f : s_acc[0]) + (float)cnt * d;
+                                if (rs.nh == 0u) s_acc[256] = d;
+                            }
+#endif
                             ++rs.nh;
                             if (rs.spp == (uint32_t)SPP) rs.tmax = -1.f;  // the last threshold: the ray ends
                         }

@@ -218,9 +218,10 @@ int generic_frames(const rto_tree* tree, const rto_camera* cams, const int64_t* 
     return RTO_OK;
 }
 
-// The frames of a batched call on a context with depth outputs, one by one through the single-frame depth kernels
-// (render_persist carries no depth): frame f into slot slot0 + f with the RNG of a batch's frame f -- the bytes of n single
-// launches.  As after generic_frames: no tile marks, full outputs.  The caller has checked the cameras and the lean level.
+// The frames of a batched call on a context with depth outputs, one by one through the single-frame depth kernels: frame f into
+// slot slot0 + f with the RNG of a batch's frame f -- the bytes of n single launches.  The route of rto_ctx_enable_depth(1), and of
+// RTO_DEPTH_BATCHED for a launch the persistent kernels cannot take.  As after generic_frames: no tile marks, full outputs.  The
+// caller has checked the cameras and the lean level.
 int depth_frames(const rto_tree* tree, const rto_camera* cams, const int64_t* rng_jumps, int n, const rto_options* o, rto_ctx* ctx,
                  hipStream_t stream, int slot0) {
     int kernel;
@@ -265,9 +266,13 @@ int check_batch(const rto_tree* tree, const rto_camera* cams, int n, const rto_o
     if (rc != RTO_OK) return rc;
     rc = check_depth(tree, o, ctx);
     if (rc != RTO_OK) return rc;
-    if (ctx->depth && ctx->lean != 0)  // (the single-frame kernels the frames go through store full outputs)
+    if (ctx->depth && ctx->lean != 0 && ctx->depth_mode != RTO_DEPTH_BATCHED)  // (the single-frame kernels the frames go through store full outputs)
         return set_err(RTO_E_UNSUPPORTED, "a context with depth outputs (rto_ctx_enable_depth) renders its batches frame by frame: lean "
                                           "outputs (rto_ctx_set_lean_outputs) must be off");
+    if (ctx->depth && ctx->lean != 0 && !batched)  // (RTO_DEPTH_BATCHED, and the launch is known to go frame by frame all the same)
+        return set_err(RTO_E_UNSUPPORTED, "the persistent kernels cannot take this launch (no traversal image, too many leaf slots at this "
+                                          "spp, or tuning key batch_fallback): a context with depth outputs renders it frame by frame, and "
+                                          "lean outputs (rto_ctx_set_lean_outputs) must be off");
     // sparse lean outputs store nothing for unmarked tiles because those are the constant background -- not over a colour layer
     if (layered && layers.color && o->denoise && ctx->lean == 2)
         return set_err(RTO_E_UNSUPPORTED, "sparse lean outputs (rto_ctx_set_lean_outputs level 2) need a constant backdrop: not with a colour "
@@ -325,14 +330,18 @@ int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const int64_t*
     // hit-list entry can name at this SPP (2^28 at spp <= 8, 2^26 at spp 32): the same frames, one launch of the
     // generic kernel each -- same images, without the batching gain.
     rto::TreeDev tdev;
+    // A context with depth outputs: frame by frame through the single-frame depth kernels (depth_frames) -- unless it was enabled
+    // with RTO_DEPTH_BATCHED, whose batches take the persistent kernels like any other (render_persist_depth for the traversal)
+    // and depth_frames, not generic_frames, where those cannot take the launch.
+    const bool depth_batched = ctx->depth && ctx->depth_mode == RTO_DEPTH_BATCHED;
     const bool batched = spp_supported(o->spp) && fast_path_for_spp(tree, o->spp, ctx->test_wide_bits, &tdev) != 0 &&
-                         ctx->batch_fallback != 1 && !ctx->depth;
+                         ctx->batch_fallback != 1 && (!ctx->depth || depth_batched);
     int rc = check_batch(tree, cams, n, o, ctx, slot0, batched);
     if (rc != RTO_OK) return rc;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     hipStream_t stream = (hipStream_t)stream_;
-    if (ctx->depth) return depth_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
+    if (ctx->depth && !batched) return depth_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
     if (!batched) return generic_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
 
     ctx->marks_n = 0;  // whatever happens below, the tile marks of an earlier launch no longer describe this context's frames
@@ -385,11 +394,20 @@ int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const int64_t*
     ctx->occ.force_lds_refusal = ctx->batch_fallback == 2;
     rto::LayerDev layers;
     const bool layered = ctx_layers_at(ctx, slot0, &layers);  // (batch frame f = slot slot0 + f reads plane slot0 + f)
+    rto::DepthOut dout;  // (batch frame f = slot slot0 + f writes plane slot0 + f)
+    const bool with_depth = ctx_depth_at(ctx, slot0, &dout);
     hipError_t e = rto::launch_render_batch(o->spp, tdev, od, fb, ctx->jump, ctx->queue,
                                             frames[0].hits,  // the kernel indexes frames from here
-                                            ctx->num_cus, ctx->refill, cull, &ctx->occ, ev, layered ? &layers : nullptr, stream);
+                                            ctx->num_cus, ctx->refill, cull, &ctx->occ, ev, layered ? &layers : nullptr,
+                                            with_depth ? &dout : nullptr, stream);
     if (ctx->occ.lds_refused) {
         if (ev) --ctx->kt_count;  //  nothing was launched, nothing recorded the slot's events: give it back
+        if (with_depth) {  // (RTO_DEPTH_BATCHED) frame by frame through the single-frame depth kernels, which store full outputs
+            if (ctx->lean != 0)
+                return set_err(RTO_E_UNSUPPORTED, "the device refused the LDS the batched traversal kernel needs: a context with depth outputs "
+                                                  "renders this launch frame by frame, and lean outputs (rto_ctx_set_lean_outputs) must be off");
+            return depth_frames(tree, cams, rng_jumps, n, o, ctx, stream, slot0);
+        }
         // the device does not grant a workgroup the LDS the traversal kernel needs for this depth x SPP x frame count
         // ((max_depth + 1 - top_levels + spp + 1) KB for the ancestor stack and thresholds + 56 B per frame); nothing but
         // the frame table was written so far: the same frames through the generic kernel, frame by frame

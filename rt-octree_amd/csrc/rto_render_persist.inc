@@ -2,8 +2,11 @@
 // render_persist_layers (RTO_PERSIST_LAYERS defined to 1 around the include: a ray stops at its pixel of the depth layer, `layers`,
 // rto_ctx_set_layers).  In scope: the kernel parameters and SPP, REFILL, WPS, WIDE, STACK.  (Switched by the preprocessor:
 // render_persist's text and code are what they were before the layered kernel existed.)
+// RTO_DEPTH defined to 1 as well (render_persist_depth, depth_kernels.hip): a ray also keeps the distance of its hits (rto_march_leaf.inc)
+// in two more LDS rows -- the sum and the first hit's; the forms without the register stack park hoff / hnext in two further ones -- and stores depth and t_near of its pixel through `dout` (DepthOut, plane f =
+// batch frame f) when its hit list leaves.  Pixels whose ray never flushes are the launcher's fill: (0, +inf).
     // queue[8 + 8k]: next ray of queue k's list (zeroed on the stream before the launch)
-    // LDS: [max_depth+1-top_levels][256] ancestor stack | [SPP+1][256] sorted thresholds | frame table
+    // LDS: [max_depth+1-top_levels][256] ancestor stack | [SPP+1][256] sorted thresholds | (RTO_DEPTH: [2 or 4][256] hit distances, hand-off offsets |) frame table
     extern __shared__ uint32_t s_mem[];
     const int tid = threadIdx.x;
     uint32_t* stack = s_mem + tid;  // [level - G][256]
@@ -14,7 +17,18 @@
     float* s_dst = reinterpret_cast<float*>(s_mem + (size_t)stack_levels * 256) + tid;
     // the cameras of the batch: {fx, fy, transform[12]} per frame = the head of a FrameDesc (56 of its 96 bytes: at 100 frames
     // per launch the table then leaves room for 8 workgroups per CU)
+#if RTO_DEPTH
+    // the ray's depth accumulators: row 0 the running sum of (float)cnt * d over its hits, row 1 its first hit's d.  Written and
+    // read at hits only (rare next to node visits): no register of the march loop, whose budget the layered kernel has used up
+    float* s_acc = s_dst + (SPP + 1) * 256;
+    // (the forms whose ancestor stack lives in LDS rows park the ray's two hand-off offsets in two more: held in registers, as their
+    //  siblings hold them, these forms grow their private segment -- they are at 64 registers without the depth code)
+    constexpr int kDepthRows = STACK == 1 ? 2 : 4;
+    uint32_t* const s_offs = STACK == 1 ? stack : reinterpret_cast<uint32_t*>(s_acc) + 512;
+    float* s_cams = reinterpret_cast<float*>(s_mem + (size_t)(stack_levels + SPP + 1 + kDepthRows) * 256);
+#else
     float* s_cams = reinterpret_cast<float*>(s_mem + (size_t)(stack_levels + SPP + 1) * 256);
+#endif
     __shared__ int s_qstart[kMaxQueues + 1];
     __shared__ uint32_t s_qcount[kMaxQueues];  // live tile slots of each queue (queue_scan_kernel)
     static_assert(offsetof(FrameDesc, transform) == 8 && kCamFloats == 14, "s_cams copies the first 14 floats of a FrameDesc");
@@ -84,7 +98,9 @@
     uint32_t woff_grid_v = 24u - (uint32_t)tree.top_levels, woff_pair0_v = 22u - (uint32_t)tree.top_levels;
     uint32_t tgrid = 1u << (24 - tree.top_levels);
     asm volatile("" : "+v"(woff_grid_v), "+v"(woff_pair0_v), "+s"(tgrid));
+#if !RTO_DEPTH  // (RTO_DEPTH: every form parks them, in s_offs)
     constexpr bool kOffsInLds = STACK == 1;
+#endif
     RayState rs;
     // a lane marches a ray while rs.t < rs.tmax: that comparison IS the lane's state (an ended ray has t >= tmax or
     // tmax = -1), so the wave-level count of marching lanes is the ballot of one v_cmp instead of a loop-carried flag
@@ -137,10 +153,14 @@
                 const uint32_t first = res_next;
                 res_next += take;
                 if (idle && rs.nh) {  // the ended ray's hit list leaves in one go
+#if RTO_DEPTH
+                    depth_flush<SPP>(rs, s_offs, s_acc, dout, SIZE);  // (hoff / hnext back from their rows, depth and t_near stored)
+#else
                     if constexpr (kOffsInLds) {
                         rs.hoff = stack[0];
                         rs.hnext = stack[256];
                     }
+#endif
                     flush_hits<SPP, WIDE>(rs, tree, hits, s_dst, hstride, !tree.rec_by_entry);
                 }
                 if (idle) {
@@ -194,10 +214,15 @@
                             // buffer, where the ray's hit list will overwrite them)
                             rs.cur = __uint_as_float(hits[rs.hoff]);
                             const uint32_t* tp = hits + rs.hnext;
+#if RTO_DEPTH
+                            s_offs[0] = rs.hoff;  // (parked until the ray's flush)
+                            s_offs[256] = rs.hnext;
+#else
                             if constexpr (kOffsInLds) {  // (parked until the ray's flush)
                                 stack[0] = rs.hoff;
                                 stack[256] = rs.hnext;
                             }
+#endif
 #pragma unroll
                             for (int i = 1; i < SPP; ++i) s_dst[i * 256] = __uint_as_float(tp[(uint32_t)(i - 1) * hstride]);
                             s_dst[SPP * 256] = 3.402823466e+38f;
@@ -358,10 +383,14 @@
         } while (n_active > exit_at);
     }
     if (rs.nh) {  // rays that ended after the last refill round
+#if RTO_DEPTH
+        depth_flush<SPP>(rs, s_offs, s_acc, dout, SIZE);
+#else
         if constexpr (kOffsInLds) {
             rs.hoff = stack[0];
             rs.hnext = stack[256];
         }
+#endif
         flush_hits<SPP, WIDE>(rs, tree, hits, s_dst, hstride, !tree.rec_by_entry);
     }
 #ifdef RTO_DBG_COUNTERS

@@ -416,4 +416,88 @@ RTO_DEV void shade_leaf_packed(const TreeDev& tree, uint32_t slot, const float* 
 #define RTO_FAST_WPS 5
 #endif
 
+// ------------------------------------------------------------------ persistent kernel (N == 2): what rto_render_persist.inc is built from
+// (moved verbatim from render_kernels.hip: render_persist / render_persist_layers there and render_persist_depth in depth_kernels.hip
+//  are the same body)
+
+// the per-ray state that survives between march steps (thresholds live in LDS, hits go straight
+// to the hand-off buffer)
+struct RayState {
+    float cen[3], dir[3], invdir[3];
+    float pos[3];  // 2^24 * clamp(cen + t * dir, 0, 1 - 1e-6): the point the next march step starts from (scaled: kPos24)
+    float delta_scale, t, tmax, src, cur;      // cur = next threshold to cross (dst[spp])
+    uint32_t spp;
+    uint32_t pix, piy, piz;
+    int prev_lvl;   // level of the node about to be visited
+    uint32_t hoff, hnext;  // index of this pixel's next free hit entry in the hand-off buffer, and of the one behind it
+                           // (staged hit lists, the default: of its entries 0 and 1, fixed for the ray's life)
+    uint32_t nh;           // staged hit lists: hit entries of this ray parked in LDS, not yet written out
+    uint32_t node;  // node about to be visited; kGridNext = the top grid is visited next (two-level image: 0 = the grid)
+    uint32_t woff;  // two-level image: lowest of the coordinate bits that index the node about to be visited
+    uint32_t wb;    // two-level image: coordinate bits per axis that index it -- G at the grid, 2 at a wide node (round 5: kept with
+                    // the ray instead of re-derived from `node` by a compare + select in every iteration)
+    float cxy __attribute__((ext_vector_type(2)));  // cen[0], cen[1] as a register pair for the packed march arithmetic
+    // _dda_unit's max(t1, t1 + invdir) per axis is t1 + (invdir > 0 ? invdir : 0): the sign of invdir is the ray's, not the
+    // step's (exit_add below)
+    float exit_add[3];
+};
+constexpr uint32_t kGridNext = 0xffffffffu;
+constexpr int kCamFloats = 14;  // fx, fy, transform[12]: what a ray set-up reads of a FrameDesc
+
+// Staged hit lists (round 4, VERDICT r3 task 5; -DRTO_HITS_DIRECT restores the store per hit): a ray's hit entries wait in LDS -- in the rows of its threshold column that
+// its consumed thresholds left free -- and are written to the hand-off buffer when the ray has ended: entry 0 into the dense
+// plane, entries 1.. as one contiguous run (4 * (n - 1) bytes of ONE 32-byte sector for SPP <= 9), back to back, instead of
+// one 4-byte store per hit at the moment it happens (71.6 M scattered dwords per 100 frames cost 2.48 GB of line-granular
+// HBM writes for 0.29 GB of payload: the L2 had evicted the sector long before the pixel's next entry arrived).
+template <int SPP, bool WIDE>
+RTO_DEV void flush_hits(RayState& rs, const TreeDev& tree, uint32_t* __restrict__ hits, const float* s_col, uint32_t hstride,
+                        bool translate = true) {
+    uint32_t e[SPP];
+#pragma unroll
+    for (int i = 0; i < SPP; ++i) {
+        e[i] = 0u;
+        if ((uint32_t)i < rs.nh) {
+            e[i] = __float_as_uint(s_col[i * 256]);
+            if constexpr (WIDE) {
+                constexpr uint32_t smask = (1u << hit_slot_bits(SPP)) - 1u;
+                // (off the march loop: the ray has ended; !translate: entry-ordered records, TreeDev::rec_by_entry -- the entry IS the record)
+                if (translate) e[i] = (e[i] & ~smask) | wide_to_slot(tree, e[i] & smask);
+            }
+        }
+    }
+    hits[rs.hoff] = e[0];
+    uint32_t* tp = hits + rs.hnext;
+#pragma unroll
+    for (int i = 1; i < SPP; ++i)
+        if ((uint32_t)i < rs.nh) tp[(uint32_t)(i - 1) * hstride] = e[i];
+    rs.nh = 0;
+}
+
+// Waves per SIMD the default instantiation is built for.  Round 3: 7 (72 VGPRs).  Round 4: 8 (64 VGPRs; the spills this forces are
+// in the ray set-up) -- with the shorter two-level loop one more resident wave is worth more than the spills cost: C2 4.69 -> 4.57,
+// C4 13.27 -> 12.71, C5 2.96 -> 2.88 ms per 100 frames in one box (profiles/r4_u_ab_wps8.txt).  Tuning key refill = 732: the 7-wave build.
+#ifndef RTO_WPS_DEFAULT
+#define RTO_WPS_DEFAULT 8
+#endif
+
+// render_persist_depth: a ray's index into the depth planes of a batched launch (DepthOut: plane f = batch frame f) from the offset
+// of its first hit entry, rs.hoff = frame * SPP * SIZE + pixel (hit_index): frame * SIZE + pixel.  Derived at the ray's flush
+// (one integer division per ray that hit something) instead of parked beside hoff / hnext
+template <int SPP>
+RTO_DEV uint32_t depth_plane_index(uint32_t hoff, uint32_t SIZE) {
+    if constexpr (SPP == 1) return hoff;
+    const uint32_t frame = hoff / ((uint32_t)SPP * SIZE);
+    return hoff - frame * ((uint32_t)(SPP - 1) * SIZE);
+}
+
+// render_persist_depth, at a ray's flush (both sites, in front of flush_hits): the ray's two hand-off offsets back from the rows
+// they were parked in at its set-up (s_offs), and its pixel's depth outputs from the two accumulator rows (s_acc: the sum over
+// its hits, its first hit's distance) stored to plane `frame` of dout
+template <int SPP>
+RTO_DEV void depth_flush(RayState& rs, const uint32_t* s_offs, const float* s_acc, const DepthOut& dout, uint32_t SIZE) {
+    rs.hoff = s_offs[0];
+    rs.hnext = s_offs[256];
+    write_depth(dout, depth_plane_index<SPP>(rs.hoff, SIZE), s_acc[0] * (1.0f / SPP), s_acc[256]);
+}
+
 }  // namespace rto

@@ -22,6 +22,7 @@ from ._lib import CCamera, COptions, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoE
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
+DEPTH_BATCHED = 2  # RTO_DEPTH_BATCHED (RenderContext.enable_depth(batched=True))
 AUX_CHANNELS = 8  # render_context.hpp:23
 _FORMAT_NAMES = {0: "RGBA", 1: "SH", 2: "SG", 3: "ASG"}
 
@@ -382,13 +383,19 @@ class RenderContext:
         check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
-    def enable_depth(self, on=True):
+    def enable_depth(self, on=True, batched=False):
         """rto_ctx_enable_depth: launch_renderer / launch_renderer_batch also write depth and t_near [frames, H, W] (include/rto.h
-        "depth outputs"); batches are then rendered frame by frame through the single-frame kernels"""
-        check(lib().rto_ctx_enable_depth(self._h, int(bool(on))))
+        "depth outputs").  Batches are then rendered frame by frame through the single-frame kernels -- or, with batched=True
+        (RTO_DEPTH_BATCHED), through the persistent kernels like any other batch: the same bytes, tile marks and lean outputs kept.
+        Calling it again on an enabled context switches between the two without touching the planes."""
+        check(lib().rto_ctx_enable_depth(self._h, (DEPTH_BATCHED if batched else 1) if on else 0))
 
     def depth_enabled(self):
         return bool(lib().rto_ctx_depth_enabled(self._h))
+
+    def depth_mode(self):
+        """0 = no depth outputs, 1 = batches frame by frame, DEPTH_BATCHED (2) = batches through the persistent kernels"""
+        return int(lib().rto_ctx_depth_enabled(self._h))
 
     def depth_view(self):
         """zero-copy view of the selected slot's depth plane [H, W]; None while disabled"""

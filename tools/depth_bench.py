@@ -6,7 +6,13 @@ each with rgba alone (render_rays: the yardstick, the kernel rto_launch_rays run
 (render_rays_depth) and with the two depth outputs alone (no colour computed).  Frames: launch_renderer on that camera, the
 fast kernel, without depth (render_fast), with it (render_fast_layers_depth), and over a depth + colour layer without / with it
 (render_fast_layers / render_fast_layers_depth).  Prints one JSON line per measurement -- the median of --reps timed runs of
---iters back-to-back launches each (HIP events) -- and one line of ratios (with / without) at the end."""
+--iters back-to-back launches each (HIP events) -- and one line of ratios (with / without) at the end.
+
+Batch (--cases batch): --batch-frames frames (100) of the C2 orbit in one rto_launch_renderer_batch, render only, on three contexts --
+(a) no depth outputs, (b) rto_ctx_enable_depth(1): frame by frame through the single-frame depth kernels, (c) RTO_DEPTH_BATCHED:
+the persistent kernels with render_persist_depth.  ms per launch from HIP events: 3 warm-up launches each, then 7 rounds in which
+the three take turns with 5 back-to-back launches each, all in this one process; median and minimum of the 7 per route, the
+ratios (c) / (b) and (c) / (a), and whether the median of (c) lies below the fastest repeat of (b)."""
 import argparse
 import json
 import os
@@ -34,7 +40,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--cases", default="rays,frames,batch", help="comma-separated: rays, frames, batch")
+    ap.add_argument("--batch-frames", type=int, default=100)
     args = ap.parse_args()
+    cases = set(args.cases.split(","))
     import ctypes as C
 
     import torch
@@ -74,7 +83,7 @@ def main():
         print(json.dumps(dict(case=case, spp=args.spp, ms=round(ms, 4), rate=round(rate / 1e9, 4) if unit == "Grays/s" else round(rate, 1),
                               unit=unit, **kw)), flush=True)
 
-    for name, (ro, rd) in (("raster", raster), ("random", rand)):
+    for name, (ro, rd) in (("raster", raster), ("random", rand)) if "rays" in cases else ():
         k = ro.shape[0]
         r = _lib.CRays()
         r.origins, r.dirs, r.n, r.first_ray = ro.data_ptr(), rd.data_ptr(), k, 0
@@ -90,7 +99,7 @@ def main():
 
     layer_depth = torch.full((1, H, W), 1e9, dtype=torch.float32, device=dev)
     layer_color = torch.ones((1, H, W, 4), dtype=torch.float32, device=dev)
-    for layered in (False, True):
+    for layered in (False, True) if "frames" in cases else ():
         for with_depth in (False, True):
             fctx = R.RenderContext(W, H)
             fctx.rng_seed()
@@ -101,11 +110,63 @@ def main():
                 fctx.enable_depth()
             ms = timed(lambda: R.launch_renderer(dt, cam, opt, fctx, stream=stream.value or None), args.iters, args.reps)
             line("frame%s%s" % ("_layers" if layered else "", "_depth" if with_depth else ""), 1, ms, "frames/s")
-    ratios = {"rays_raster": results["rays_raster_rgba_depth_tnear"] / results["rays_raster_rgba"],
-              "rays_random": results["rays_random_rgba_depth_tnear"] / results["rays_random_rgba"],
-              "rays_raster_depth_only": results["rays_raster_depth_tnear"] / results["rays_raster_rgba"],
-              "frame": results["frame_depth"] / results["frame"], "frame_layers": results["frame_layers_depth"] / results["frame_layers"]}
-    print(json.dumps(dict(case="ratios_time_with_over_without", **{k: round(v, 4) for k, v in ratios.items()})), flush=True)
+    ratios = {}
+    if "rays" in cases:
+        ratios.update({"rays_raster": results["rays_raster_rgba_depth_tnear"] / results["rays_raster_rgba"],
+                       "rays_random": results["rays_random_rgba_depth_tnear"] / results["rays_random_rgba"],
+                       "rays_raster_depth_only": results["rays_raster_depth_tnear"] / results["rays_raster_rgba"]})
+    if "frames" in cases:
+        ratios.update({"frame": results["frame_depth"] / results["frame"], "frame_layers": results["frame_layers_depth"] / results["frame_layers"]})
+    if ratios:
+        print(json.dumps(dict(case="ratios_time_with_over_without", **{k: round(v, 4) for k, v in ratios.items()})), flush=True)
+    if "batch" in cases:
+        batch_case(dt, args, W, H, fx, opt, stream)
+
+
+def batch_case(dt, args, W, H, fx, opt, stream):
+    """(a) no depth, (b) mode 1, (c) mode 2: ms per launch of one batch of args.batch_frames frames, the three alternating"""
+    import torch
+    n = args.batch_frames
+    cams = []
+    for p in synth.orbit_poses(200)[:n]:
+        c = R.Camera(W, H, fx, fx)
+        c.set_c2w(p)
+        cams.append(c)
+    jumps = list(range(n))
+    routes = {}
+    for name, mode in (("a_no_depth", 0), ("b_mode_1", 1), ("c_mode_2", 2)):
+        ctx = R.RenderContext(W, H, frames=n)
+        ctx.rng_seed()
+        if mode:
+            ctx.enable_depth(batched=mode == 2)
+        routes[name] = ctx
+
+    def launch(ctx):
+        R.launch_renderer_batch(dt, cams, opt, ctx, stream.value or None, rng_jumps=jumps)
+
+    for ctx in routes.values():
+        for _ in range(3):
+            launch(ctx)
+    torch.cuda.synchronize()
+    assert routes["c_mode_2"].tile_marks() is not None and routes["b_mode_1"].tile_marks() is None  # (the routes are what they claim)
+    ms = {name: [] for name in routes}
+    for _ in range(7):
+        for name, ctx in routes.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(5):
+                launch(ctx)
+            b.record()
+            b.synchronize()
+            ms[name].append(a.elapsed_time(b) / 5)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for name, v in ms.items():
+        print(json.dumps(dict(case="batch_" + name, frames=n, size=W, spp=args.spp, ms_per_launch_median=round(med[name], 4),
+                              ms_per_launch_min=round(min(v), 4), ms_per_launch_max=round(max(v), 4),
+                              frames_per_s=round(n / med[name] * 1e3, 1), repeats=[round(x, 4) for x in v])), flush=True)
+    print(json.dumps(dict(case="batch_ratios", c_over_b=round(med["c_mode_2"] / med["b_mode_1"], 4),
+                          c_over_a=round(med["c_mode_2"] / med["a_no_depth"], 4),
+                          median_c_below_fastest_b=bool(med["c_mode_2"] < min(ms["b_mode_1"])))), flush=True)
 
 
 if __name__ == "__main__":
