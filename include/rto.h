@@ -528,11 +528,33 @@ int rto_timer_report(const rto_ctx* c, float ms_out[3], float* fps_out, int* fra
  * Denoiser::denoise runs, denoiser.cpp:46): relu6(conv3x3(8 -> c1)) -> relu6(conv3x3(c1 -> 2*levels))
  * -> softmax over the first `levels` channels.  Weights in PyTorch layout, fp32:
  * w1 [c1][8][3][3], b1 [c1], w2 [2*levels][c1][3][3], b2 [2*levels]; they are rounded to fp16 like the
- * reference's `.half()` module.  Supported: c1 = 32, levels = 4 (denoiser/configs/blender.txt:21-25);
- * anything else returns RTO_E_UNSUPPORTED and the caller keeps using the TorchScript module. */
+ * reference's `.half()` module.  Supported: c1 in 1..64, levels in 1..6 (the trainer's --mid_channels / --kernel_levels,
+ * denoiser/main.py:101-110); anything else returns RTO_E_UNSUPPORTED.  This is rto_guidance_net_create_layers for two layers. */
 typedef struct rto_guidance_net rto_guidance_net;
 int rto_guidance_net_create(const float* w1, const float* b1, const float* w2, const float* b2, int c1, int levels,
                             int device, rto_guidance_net** out);
+/* Any compact stack the trainer can produce: 8 -> c1 [-> c1] -> 2*levels, i.e. num_layers 2 or 3, c1 in 1..64, levels in 1..6;
+ * every layer conv3x3 "same" + ReLU6 with fp16 rounding after it, softmax over the first `levels` channels of the last.
+ * RTO_E_INVALID (checked before any device is touched): a null pointer, layers[0].cin != 8, layers[i].cin != layers[i-1].cout,
+ * last cout != 2*levels, a non-finite weight or bias.  RTO_E_UNSUPPORTED: num_layers outside 2..3, c1 outside 1..64, a middle
+ * layer that is not c1 -> c1, levels outside 1..6.
+ * c1 = 32, levels = 4, two layers (denoiser/configs/blender.txt:21-25) is the reference shape: it runs the kernel tuned for it
+ * and has every route below.  Every other shape is a GENERAL net: one fused kernel as well (guidance_general.inc), on fp32
+ * planes -- rto_guidance_net_forward / _forward_ex / _forward_culled, rto_filtering_culled and rto_denoise (both modes; lean
+ * level-1 frames included) work with the net's own `levels`; the packed fp16 maps and sparse frames do not exist for it:
+ * rto_guidance_net_forward_packed[_culled], rto_filtering_packed[_culled], rto_guidance_net_reserve, RTO_NET_INPUT_SPARSE and
+ * rto_denoise on sparse (lean level 2) frames return RTO_E_UNSUPPORTED and leave the handle usable. */
+typedef struct rto_guidance_layer {
+    const float* weight; /* host, [cout][cin][3][3] */
+    const float* bias;   /* host, [cout] */
+    int cin, cout;
+} rto_guidance_layer;
+int rto_guidance_net_create_layers(const rto_guidance_layer* layers, int num_layers, int levels, int device, rto_guidance_net** out);
+/* halo = pixels of aux around a map value that it depends on (= num_layers); packed_route = 1 for the reference shape */
+typedef struct rto_guidance_net_info {
+    int c1, levels, num_layers, halo, packed_route;
+} rto_guidance_net_info;
+int rto_guidance_net_get_info(const rto_guidance_net* net, rto_guidance_net_info* info);
 /* aux: device [n][8][H][W] fp32; outputs: device [n][levels][H][W] fp32 (weight_map, guidance_map) */
 int rto_guidance_net_forward(const rto_guidance_net* net, void* stream, const float* aux, int n, int H, int W,
                              float* weight_map, float* guidance_map);
@@ -588,8 +610,9 @@ int rto_filtering_packed_culled(rto_guidance_net* net, void* stream, const float
                                 const uint32_t* tile_marks, int words_per_frame, float background);
 /* Denoiser::denoise (denoiser.cpp:31-61) in one call, for the n frames of `ctx` from its selected slot on: the network on the
  * context's aux buffer, the filter from its noisy buffer into its image buffer.  mode RTO_FILTER_FACTORISED: packed fp16
- * maps + factorised filter (the throughput route); RTO_FILTER_EXACT: fp32 planes (a scratch the handle owns, 32 B per
- * pixel) + the bit-exact filter.  When the frames are those of the last rto_launch_renderer_batch on `ctx` its tile marks
+ * maps + factorised filter (the throughput route; a general net: fp32 planes + the factorised filter); RTO_FILTER_EXACT: fp32
+ * planes (a scratch the handle owns, 8 * levels B per pixel) + the bit-exact filter.  A three-layer net culls its network
+ * tiles only: the filter kernels' tile test covers the receptive field of two layers.  When the frames are those of the last rto_launch_renderer_batch on `ctx` its tile marks
  * are used (the *_culled calls above); after a single-frame launch the plain kernels run.  Same results either way.
  * Like the packed scratch, the plane scratch grows on demand and growing synchronises the device once: call it once at the
  * largest extent before a timed or captured region. */

@@ -52,6 +52,15 @@ class CQueryOut(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sigma", C.c_void_p), ("level", C.c_void_p), ("cube", C.c_void_p)]
 
 
+class CGuidanceLayer(C.Structure):
+    """rto_guidance_layer (include/rto.h): host pointers to one convolution's fp32 weights [cout][cin][3][3] and bias"""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("cin", C.c_int), ("cout", C.c_int)]
+
+
+class CGuidanceNetInfo(C.Structure):
+    _fields_ = [("c1", C.c_int), ("levels", C.c_int), ("num_layers", C.c_int), ("halo", C.c_int), ("packed_route", C.c_int)]
+
+
 class CTreeInfo(C.Structure):
     _fields_ = [
         ("capacity", C.c_int64), ("N", C.c_int), ("data_dim", C.c_int), ("format", C.c_int),
@@ -136,6 +145,8 @@ SYMBOLS = {
     "rto_ctx_download_image": (C.c_int, [_P, _P, C.c_int, _P]),
     "rto_ctx_download_aux": (C.c_int, [_P, _P, _P]),
     "rto_guidance_net_create": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "rto_guidance_net_create_layers": (C.c_int, [C.POINTER(CGuidanceLayer), C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "rto_guidance_net_get_info": (C.c_int, [_P, C.POINTER(CGuidanceNetInfo)]),
     "rto_guidance_net_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rto_guidance_net_forward_ex": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
     "rto_guidance_net_forward_packed": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),

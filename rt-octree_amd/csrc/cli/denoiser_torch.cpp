@@ -57,39 +57,47 @@ TorchDenoiser::TorchDenoiser(const std::string& path, int device, bool use_fused
         throw std::runtime_error("Error when loading torchscript model from " + path);
     }
     if (use_fused) {
-        torch::Tensor w1, b1, w2, b2;
+        // the compact stack: layers.<i>.conv.{weight, bias} for i = 0..N-1 and nothing else (or, in a reference-format file, N
+        // convolution constants of the graph).  Every stack librto supports (8 -> c1 [-> c1] -> 2 levels) runs fused.
+        std::vector<std::pair<torch::Tensor, torch::Tensor>> convs;
         int n_params = 0;
-        for (const auto& p : impl_->module.named_parameters()) {
-            ++n_params;
-            if (p.name == "layers.0.conv.weight") w1 = p.value;
-            if (p.name == "layers.0.conv.bias") b1 = p.value;
-            if (p.name == "layers.1.conv.weight") w2 = p.value;
-            if (p.name == "layers.1.conv.bias") b2 = p.value;
+        {
+            std::vector<torch::Tensor> ws(8), bs(8);
+            for (const auto& p : impl_->module.named_parameters()) {
+                ++n_params;
+                for (int i = 0; i < 8; ++i) {
+                    if (p.name == "layers." + std::to_string(i) + ".conv.weight") ws[i] = p.value;
+                    if (p.name == "layers." + std::to_string(i) + ".conv.bias") bs[i] = p.value;
+                }
+            }
+            for (int i = 0; i < 8 && ws[i].defined() && bs[i].defined(); ++i) convs.emplace_back(ws[i], bs[i]);
+            if (n_params != 2 * (int)convs.size()) convs.clear();  // other parameters: not the compact network
         }
         if (n_params == 0) {  // a reference-format file: weights are graph constants
             try {
-                const auto convs = conv_constants(impl_->module);
-                if (convs.size() == 2) {
-                    w1 = convs[0].first;
-                    b1 = convs[0].second;
-                    w2 = convs[1].first;
-                    b2 = convs[1].second;
-                    n_params = 4;
-                }
+                convs = conv_constants(impl_->module);
             } catch (const std::exception&) {  // unknown graph shape: stay on libtorch
-                n_params = 0;
+                convs.clear();
             }
         }
-        if (n_params == 4 && w1.defined() && b1.defined() && w2.defined() && b2.defined() && w1.dim() == 4 &&
-            w2.dim() == 4 && w1.size(1) == 8 && w1.size(2) == 3 && w1.size(3) == 3 && w2.size(1) == w1.size(0) &&
-            w2.size(2) == 3 && w2.size(3) == 3) {
+        bool shaped = convs.size() >= 2;
+        for (const auto& c : convs)
+            shaped = shaped && c.first.dim() == 4 && c.first.size(2) == 3 && c.first.size(3) == 3 && c.second.dim() == 1 &&
+                     c.second.size(0) == c.first.size(0);
+        if (shaped) {
             auto host = [](const torch::Tensor& t) { return t.detach().to(torch::kCPU, torch::kFloat32).contiguous(); };
-            const torch::Tensor hw1 = host(w1), hb1 = host(b1), hw2 = host(w2), hb2 = host(b2);
+            std::vector<torch::Tensor> keep;
+            std::vector<rto_guidance_layer> layers;
+            for (const auto& c : convs) {
+                keep.push_back(host(c.first));
+                keep.push_back(host(c.second));
+                layers.push_back({keep[keep.size() - 2].data_ptr<float>(), keep[keep.size() - 1].data_ptr<float>(), (int)c.first.size(1),
+                                  (int)c.first.size(0)});
+            }
             rto_guidance_net* net = nullptr;
-            const int c1 = (int)w1.size(0), levels = (int)w2.size(0) / 2;
-            if (rto_guidance_net_create(hw1.data_ptr<float>(), hb1.data_ptr<float>(), hw2.data_ptr<float>(),
-                                        hb2.data_ptr<float>(), c1, levels, device, &net) == RTO_OK) {
-                impl_->fused = net;  // (RTO_E_UNSUPPORTED for other widths: stay on libtorch)
+            const int levels = (int)convs.back().first.size(0) / 2;
+            if (rto_guidance_net_create_layers(layers.data(), (int)layers.size(), levels, device, &net) == RTO_OK) {
+                impl_->fused = net;  // (RTO_E_UNSUPPORTED / RTO_E_INVALID for any other stack: stay on libtorch)
                 impl_->fused_levels = levels;
                 // Recognising a module by its tensors says nothing about the rest of its graph: run both
                 // routes once on a small random input and keep the fused kernel only if they agree to fp16
@@ -125,6 +133,10 @@ TorchDenoiser::~TorchDenoiser() {
 }
 
 bool TorchDenoiser::fused() const { return impl_->fused != nullptr; }
+bool TorchDenoiser::packed_route() const {
+    rto_guidance_net_info info;
+    return impl_->fused && rto_guidance_net_get_info(impl_->fused, &info) == RTO_OK && info.packed_route != 0;
+}
 rto_guidance_net* TorchDenoiser::fused_handle() const { return impl_->fused; }
 
 void TorchDenoiser::forward(float* aux, int n, int H, int W, const float** weight, const float** guidance, int* levels, bool input_rgba) {

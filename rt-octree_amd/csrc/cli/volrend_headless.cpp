@@ -122,8 +122,9 @@ void usage() {
         "  --gpus N           frames sharded over N GPUs of this node: N child processes (--shard i/N, GPU i each), one\n"
         "                     report for their union; images do not depend on N (per-pose RNG jump-ahead)\n"
         "  --batch B          poses per launch (1..128, default 100; 1 = one launch per frame like the reference's loop)\n"
-        "  --torch_net        run the TorchScript GuidanceNet through libtorch even when it is the compact two-layer\n"
-        "                     network the fused HIP kernel implements (default: fused)\n"
+        "  --torch_net        run the TorchScript GuidanceNet through libtorch even when it is a compact network the\n"
+        "                     fused HIP kernels implement: 8 -> c1 [-> c1] -> 2 x levels, c1 1..64, levels 1..6, two or\n"
+        "                     three layers (default: fused)\n"
         "  --fast_filter      guided filter with factorised exponentials (4 exps per pixel instead of 164; agrees with\n"
         "                     the default, bit-exact form to ~1e-6 relative)\n"
         "  --quant_direct     render a quantised tree.npz from its codebooks (no expansion to dense fp16)\n"
@@ -450,7 +451,7 @@ int main(int argc, char** argv) {
             (rto_ctx_tile_marks(ctx, &marks, &mark_words, &mark_slot, &mark_frames, &mark_bg) != RTO_OK || mark_slot != 0 || mark_frames < n))
             marks = nullptr;
         if (timed) rto_timer_start(ctx, RTO_T_TORCH);
-        const bool packed = denoiser->fused() && filter_mode == RTO_FILTER_FACTORISED;
+        const bool packed = denoiser->packed_route() && filter_mode == RTO_FILTER_FACTORISED;  // (other fused shapes: fp32 planes)
         // frames of a lean batched launch (below): no aux planes, the noisy image holds (r, g, b, alpha) -- the network reads that
         const int lean_state = rto_ctx_frames_are_lean(ctx, 0, n);
         if (lean_state < 0) return RTO_E_INVALID;  // (cannot happen here: every batch rewrites all the slots it denoises)

@@ -439,6 +439,8 @@ __global__ void __launch_bounds__(256, IN ? 4 : RTO_NET_SQ0_WG) guidance_fused(c
     }  // strip
 }
 
+#include "guidance_general.inc"
+
 }  // namespace
 
 hipError_t launch_guidance_net(const float* aux, const void* w1, const void* w2, const float* b2, int c1,
@@ -472,6 +474,46 @@ hipError_t launch_guidance_net(const float* aux, const void* w1, const void* w2,
     }
 #undef RTO_NET
     return hipGetLastError();
+}
+
+hipError_t launch_guidance_general(const float* aux, const void* w1, const void* wm, const void* wl, const float* bm, const float* bl,
+                                   int c1p, int num_layers, int levels, int n, int H, int W, float* weight_out, float* guidance_out,
+                                   int in_mode, const uint32_t* tile_mask, int mask_words, const float* fill_planes, hipStream_t stream) {
+    if ((c1p != 16 && c1p != 32 && c1p != 64) || (num_layers != 2 && num_layers != 3) || levels < 1 || levels > 6 || in_mode < 0 ||
+        in_mode > 2 || !weight_out || !guidance_out)
+        return hipErrorInvalidValue;
+    const int tiles_x = (W + kGW - 1) / kGW, tiles_y = (H + kGH - 1) / kGH;
+    int strip = kStrip;  // (as launch_guidance_net)
+    while (strip > 1 && (int64_t)((tiles_x + strip - 1) / strip) * tiles_y * n < 2048) --strip;
+    const dim3 grid((tiles_x + strip - 1) / strip, tiles_y, n);
+    NetCullG cull;
+    cull.mask = fill_planes ? tile_mask : nullptr;
+    cull.mask_words = mask_words;
+    cull.tiles_x = (W + 7) / 8;
+    for (int i = 0; i < 12; ++i) cull.planes[i] = 0.f;
+    if (cull.mask)
+        for (int l = 0; l < levels; ++l) {  // fill_planes: `levels` weights, then `levels` guidance values
+            cull.planes[l] = fill_planes[l];
+            cull.planes[6 + l] = fill_planes[levels + l];
+        }
+#define RTO_GEN(C, NLAYERS, IN) \
+    return launch_general_one<C, NLAYERS, IN>(grid, stream, aux, w1, wm, wl, bm, bl, weight_out, guidance_out, H, W, levels, cull, strip)
+#define RTO_GEN_IN(C, NLAYERS)                                         \
+    do {                                                               \
+        if (in_mode == 2) RTO_GEN(C, NLAYERS, 2);                      \
+        if (in_mode == 1) RTO_GEN(C, NLAYERS, 1);                      \
+        RTO_GEN(C, NLAYERS, 0);                                        \
+    } while (0)
+    if (num_layers == 2) {
+        if (c1p == 16) RTO_GEN_IN(16, 2);
+        if (c1p == 32) RTO_GEN_IN(32, 2);
+        RTO_GEN_IN(64, 2);
+    }
+    if (c1p == 16) RTO_GEN_IN(16, 3);
+    if (c1p == 32) RTO_GEN_IN(32, 3);
+    RTO_GEN_IN(64, 3);
+#undef RTO_GEN_IN
+#undef RTO_GEN
 }
 
 }  // namespace rto

@@ -57,4 +57,12 @@ hipError_t launch_guidance_net(const float* aux, const void* w1, const void* w2,
                                int in_mode, const uint32_t* tile_mask, int mask_words, const uint32_t* fill_k,
                                const float* fill_planes, int sparse, float background, hipStream_t stream);
 
+// the same network for every other shape (guidance_general.inc): 8 -> c1p [-> c1p] -> 2 levels, c1p in {16, 32, 64} (the host
+// packer pads c1 with zero channels), num_layers 2 or 3, levels 1..6; fp32 planes only.
+// w1 fp16 [c1p][96]; wm fp16 [c1p][KS*32] and bm [c1p] (num_layers = 3, else unused); wl fp16 [16][KS*32], bl [16];
+// KS = 5 / 9 / 18 for c1p = 16 / 32 / 64, k = tap * c1p + ci.  fill_planes: `levels` weights, then `levels` guidance values
+hipError_t launch_guidance_general(const float* aux, const void* w1, const void* wm, const void* wl, const float* bm, const float* bl,
+                                   int c1p, int num_layers, int levels, int n, int H, int W, float* weight_out, float* guidance_out,
+                                   int in_mode, const uint32_t* tile_mask, int mask_words, const float* fill_planes, hipStream_t stream);
+
 }  // namespace rto

@@ -1,6 +1,7 @@
 // rto_guidance_abi.cpp -- C ABI of the fused GuidanceNet forward (include/rto.h, guidance_kernels.hip).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -13,22 +14,29 @@
 extern "C" const char* rto_last_error(void);
 
 struct rto_guidance_net {
-    int device = 0, c1 = 0, levels = 0;
+    int device = 0, c1 = 0, levels = 0, num_layers = 2;
     void* w1 = nullptr;   // fp16 [c1][96]
     void* w2 = nullptr;   // fp16 [16][9*c1]
     float* b2 = nullptr;  // [16]
+    // every shape but c1 = 32, levels = 4, two layers is a "general" net (guidance_general.inc): c1 padded to c1p in {16, 32, 64},
+    // w1 fp16 [c1p][96], w2 fp16 [16][KS*32] and b2 [16] = the LAST layer, wm fp16 [c1p][KS*32] and bm [c1p] = the middle layer of
+    // three; fp32 planes only -- no packed maps, no sparse frames
+    bool general = false;
+    int c1p = 0;
+    void* wm = nullptr;
+    float* bm = nullptr;
     void* packed = nullptr;      // scratch of the packed route: fp16 [n][H][W][8]
     size_t packed_bytes = 0;
     int packed_n = 0, packed_h = 0, packed_w = 0;  // what the scratch currently holds
     // rto_filtering_packed_culled: the filter's output tile over pure background of brightness fill_bg (see ensure_fill_tile)
     std::mutex fill_mu;
     float* fill_tile = nullptr;  // device [32][32][4] (factorised filter) then [8][32][4] (exact filter)
-    float fill_planes[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the background maps as fp32 planes hold them: 4 softmax weights, 4 guidance values
+    float fill_planes[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the background maps as fp32 planes hold them: `levels` softmax weights, `levels` guidance values
     bool packed_sparse = false;  // the packed maps hold nothing for the tiles the network skipped (RTO_NET_INPUT_SPARSE)
     uint32_t fill_k[4] = {0, 0, 0, 0};  // ... and the network's 8 fp16 outputs for a pixel whose neighbourhood is background
     float fill_bg = 0.f;
     bool fill_valid = false;
-    float* planes = nullptr;  // rto_denoise(EXACT): weight + guidance planes, 2 x [n][4][H][W]
+    float* planes = nullptr;  // rto_denoise(EXACT): weight + guidance planes, 2 x [n][levels][H][W]
     size_t planes_bytes = 0;
 };
 
@@ -52,29 +60,66 @@ struct DeviceScope {
 
 extern "C" {
 
-int rto_guidance_net_create(const float* w1, const float* b1, const float* w2, const float* b2, int c1, int levels,
-                            int device, rto_guidance_net** out) {
-    if (!w1 || !b1 || !w2 || !b2 || !out) return fail(RTO_E_INVALID, "rto_guidance_net_create: null argument");
-    if (c1 != 32 || levels != 4)
-        return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet supports mid_channels = 32, kernel_levels = 4 (configs/blender.txt)");
+int rto_guidance_net_create_layers(const rto_guidance_layer* layers, int num_layers, int levels, int device, rto_guidance_net** out) {
+    // ---- validation, before any device use
+    if (!layers || !out || num_layers < 1) return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: null argument");
+    for (int i = 0; i < num_layers; ++i)
+        if (!layers[i].weight || !layers[i].bias || layers[i].cin < 1 || layers[i].cout < 1)
+            return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: layer " + std::to_string(i) + " has a null pointer or no channels");
+    if (layers[0].cin != 8) return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: the first layer reads the 8 aux channels, not " + std::to_string(layers[0].cin));
+    for (int i = 1; i < num_layers; ++i)
+        if (layers[i].cin != layers[i - 1].cout)
+            return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: layer " + std::to_string(i) + " reads " + std::to_string(layers[i].cin) +
+                                           " channels, the layer before it writes " + std::to_string(layers[i - 1].cout));
+    if (levels < 1 || layers[num_layers - 1].cout != 2 * levels)
+        return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: the last layer writes " + std::to_string(layers[num_layers - 1].cout) +
+                                       " channels, kernel_levels = " + std::to_string(levels) + " needs twice that number");
+    const int c1 = layers[0].cout;
+    const std::string shape = "8 -> " + std::to_string(c1) + " x " + std::to_string(num_layers - 1) + " -> 2 x " + std::to_string(levels);
+    if (num_layers < 2 || num_layers > 3) return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet: two or three layers, not " + std::to_string(num_layers));
+    if (c1 > 64) return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet: mid_channels 1..64 (" + shape + ")");
+    if (num_layers == 3 && layers[1].cout != c1) return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet: the middle layer keeps mid_channels (" + shape + ")");
+    if (levels > 6) return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet: kernel_levels 1..6 (" + shape + ")");
+    for (int i = 0; i < num_layers; ++i) {
+        const size_t nw = (size_t)layers[i].cout * layers[i].cin * 9;
+        for (size_t k = 0; k < nw; ++k)
+            if (!std::isfinite(layers[i].weight[k])) return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: layer " + std::to_string(i) + " has a non-finite weight");
+        for (int k = 0; k < layers[i].cout; ++k)
+            if (!std::isfinite(layers[i].bias[k])) return fail(RTO_E_INVALID, "rto_guidance_net_create_layers: layer " + std::to_string(i) + " has a non-finite bias");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RTO_E_HIP, "no HIP device available");
     if (device < 0 || device >= ndev) return fail(RTO_E_INVALID, "device index out of range");
+
+    const bool general = !(c1 == 32 && levels == 4 && num_layers == 2);
     const int cout = 2 * levels;
-    // pack: k = tap*Cin + ci, tap = ky*3 + kx; layer 1 rows padded to 96 (12 taps), layer 2 to 16 rows
-    std::vector<_Float16> p1((size_t)c1 * 96, (_Float16)0.f), p2((size_t)16 * 9 * c1, (_Float16)0.f);
-    for (int co = 0; co < c1; ++co)
+    const int c1p = !general ? c1 : c1 <= 16 ? 16 : c1 <= 32 ? 32 : 64;  // zero channels: relu6(0) = +0 adds exact zeros downstream
+    // rows of a c1p-input layer: k = tap*c1p + ci, tap = ky*3 + kx; the reference shape keeps its 9*c1, a general net has
+    // KS k-steps of 32 (c1p = 16: 5, the tenth half-step -- "tap 9" -- zero)
+    const size_t row = !general ? (size_t)9 * c1 : (size_t)(c1p == 16 ? 5 : 9 * c1p / 32) * 32;
+    const rto_guidance_layer &first = layers[0], &last = layers[num_layers - 1];
+    // layer 1: rows padded to 96 (12 taps).  The reference runs the module after `.half()` (network.py:194-201): its biases are
+    // fp16 values too.  Layer 1's occupies the first padding slot of its weight row (k = 72; the kernel multiplies it by a constant 1).
+    std::vector<_Float16> p1((size_t)c1p * 96, (_Float16)0.f), p2((size_t)16 * row, (_Float16)0.f), pm;
+    for (int co = 0; co < c1; ++co) {
         for (int ci = 0; ci < 8; ++ci)
-            for (int t = 0; t < 9; ++t) p1[(size_t)co * 96 + t * 8 + ci] = (_Float16)w1[((size_t)co * 8 + ci) * 9 + t];
-    // the reference runs the module after `.half()` (network.py:194-201): its biases are fp16 values too.  Layer 1's
-    // occupies the first padding slot of its weight row (k = 72; the kernel multiplies it by a constant 1).
-    for (int co = 0; co < c1; ++co) p1[(size_t)co * 96 + 72] = (_Float16)b1[co];
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < c1; ++ci)
-            for (int t = 0; t < 9; ++t)
-                p2[(size_t)co * 9 * c1 + (size_t)t * c1 + ci] = (_Float16)w2[((size_t)co * c1 + ci) * 9 + t];
-    std::vector<float> pb2(16, 0.f);
-    for (int co = 0; co < cout; ++co) pb2[co] = (float)(_Float16)b2[co];
+            for (int t = 0; t < 9; ++t) p1[(size_t)co * 96 + t * 8 + ci] = (_Float16)first.weight[((size_t)co * 8 + ci) * 9 + t];
+        p1[(size_t)co * 96 + 72] = (_Float16)first.bias[co];
+    }
+    auto pack_rows = [&](std::vector<_Float16>& dst, const rto_guidance_layer& l) {  // (l.cin == c1)
+        for (int co = 0; co < l.cout; ++co)
+            for (int ci = 0; ci < c1; ++ci)
+                for (int t = 0; t < 9; ++t) dst[(size_t)co * row + (size_t)t * c1p + ci] = (_Float16)l.weight[((size_t)co * c1 + ci) * 9 + t];
+    };
+    pack_rows(p2, last);
+    std::vector<float> pb2(16, 0.f), pbm;
+    for (int co = 0; co < cout; ++co) pb2[co] = (float)(_Float16)last.bias[co];
+    if (num_layers == 3) {
+        pm.assign((size_t)c1p * row, (_Float16)0.f);
+        pack_rows(pm, layers[1]);
+        pbm.assign((size_t)c1p, 0.f);
+        for (int co = 0; co < c1; ++co) pbm[co] = (float)(_Float16)layers[1].bias[co];
+    }
 
     int prev = 0;
     (void)hipGetDevice(&prev);
@@ -83,11 +128,18 @@ int rto_guidance_net_create(const float* w1, const float* b1, const float* w2, c
     n->device = device;
     n->c1 = c1;
     n->levels = levels;
+    n->num_layers = num_layers;
+    n->general = general;
+    n->c1p = c1p;
     bool ok = hipMalloc(&n->w1, p1.size() * 2) == hipSuccess && hipMalloc(&n->w2, p2.size() * 2) == hipSuccess &&
               hipMalloc((void**)&n->b2, 16 * sizeof(float)) == hipSuccess;
     ok = ok && hipMemcpy(n->w1, p1.data(), p1.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(n->w2, p2.data(), p2.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(n->b2, pb2.data(), 16 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && num_layers == 3)
+        ok = hipMalloc(&n->wm, pm.size() * 2) == hipSuccess && hipMalloc((void**)&n->bm, pbm.size() * sizeof(float)) == hipSuccess &&
+             hipMemcpy(n->wm, pm.data(), pm.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(n->bm, pbm.data(), pbm.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     (void)hipSetDevice(prev);
     if (!ok) {
         rto_guidance_net_free(n);
@@ -95,6 +147,43 @@ int rto_guidance_net_create(const float* w1, const float* b1, const float* w2, c
     }
     *out = n;
     return RTO_OK;
+}
+
+int rto_guidance_net_create(const float* w1, const float* b1, const float* w2, const float* b2, int c1, int levels,
+                            int device, rto_guidance_net** out) {
+    if (!w1 || !b1 || !w2 || !b2 || !out) return fail(RTO_E_INVALID, "rto_guidance_net_create: null argument");
+    if (c1 < 1 || c1 > 64 || levels < 1 || levels > 6)
+        return fail(RTO_E_UNSUPPORTED, "fused GuidanceNet supports mid_channels 1..64, kernel_levels 1..6");
+    const rto_guidance_layer layers[2] = {{w1, b1, 8, c1}, {w2, b2, c1, 2 * levels}};
+    return rto_guidance_net_create_layers(layers, 2, levels, device, out);
+}
+
+int rto_guidance_net_get_info(const rto_guidance_net* net, rto_guidance_net_info* info) {
+    if (!net || !info) return fail(RTO_E_INVALID, "rto_guidance_net_get_info: null argument");
+    info->c1 = net->c1;
+    info->levels = net->levels;
+    info->num_layers = net->num_layers;
+    info->halo = net->num_layers;
+    info->packed_route = net->general ? 0 : 1;
+    return RTO_OK;
+}
+
+// the network on fp32 planes, by the kernel of its shape.  fill_planes != nullptr (with marks): tile skipping
+static hipError_t launch_planes(const rto_guidance_net* net, const float* aux, int n, int H, int W, float* weight_map, float* guidance_map,
+                                int in_mode, const uint32_t* marks, int words, const float* fill_planes, hipStream_t stream) {
+    if (net->general)
+        return rto::launch_guidance_general(aux, net->w1, net->wm, net->w2, net->bm, net->b2, net->c1p, net->num_layers, net->levels, n, H, W,
+                                            weight_map, guidance_map, in_mode, marks, words, fill_planes, stream);
+    return rto::launch_guidance_net(aux, net->w1, net->w2, net->b2, net->c1, net->levels, n, H, W, weight_map, guidance_map, in_mode, marks,
+                                    words, nullptr, fill_planes, 0, 0.f, stream);
+}
+
+// the packed fp16 maps and sparse frames exist for the reference shape only (filter_fast<4, true>)
+static int refuse_general(const char* who, const rto_guidance_net* net) {
+    if (!net->general) return RTO_OK;
+    return fail(RTO_E_UNSUPPORTED, std::string(who) + ": the packed / sparse route serves mid_channels = 32, kernel_levels = 4, two layers only; this net is 8 -> " +
+                                       std::to_string(net->c1) + (net->num_layers == 3 ? " -> " + std::to_string(net->c1) : std::string()) + " -> 2 x " +
+                                       std::to_string(net->levels) + " (" + std::to_string(net->num_layers) + " layers): use the fp32 planes (rto_guidance_net_forward*, rto_filtering_culled, rto_denoise)");
 }
 
 // flags of the forward calls -> launch_guidance_net's in_mode
@@ -109,10 +198,10 @@ int rto_guidance_net_forward_ex(const rto_guidance_net* net, void* stream, const
                                 float* weight_map, float* guidance_map, int flags) {
     if (!net || !aux || !weight_map || !guidance_map || n < 1 || H < 1 || W < 1)
         return fail(RTO_E_INVALID, "rto_guidance_net_forward: bad argument");
+    if ((flags & RTO_NET_INPUT_SPARSE) && net->general)
+        if (const int rc = refuse_general("rto_guidance_net_forward_ex(RTO_NET_INPUT_SPARSE)", net)) return rc;
     DeviceScope scope(net->device);
-    const hipError_t e = rto::launch_guidance_net(aux, net->w1, net->w2, net->b2, net->c1, net->levels, n, H, W,
-                                                  weight_map, guidance_map, net_in_mode(flags), nullptr, 0, nullptr, nullptr, 0, 0.f,
-                                                  (hipStream_t)stream);
+    const hipError_t e = launch_planes(net, aux, n, H, W, weight_map, guidance_map, net_in_mode(flags), nullptr, 0, nullptr, (hipStream_t)stream);
     if (e != hipSuccess) return fail(RTO_E_HIP, std::string("GuidanceNet launch failed: ") + hipGetErrorString(e));
     return RTO_OK;
 }
@@ -144,6 +233,7 @@ static int pointer_device(const void* p) {
 
 int rto_guidance_net_reserve(rto_guidance_net* net, int n, int H, int W) {
     if (!net || n < 1 || H < 1 || W < 1) return fail(RTO_E_INVALID, "rto_guidance_net_reserve: bad argument");
+    if (const int rc = refuse_general("rto_guidance_net_reserve", net)) return rc;
     DeviceScope scope(net->device);
     return reserve_packed(net, n, H, W);
 }
@@ -162,6 +252,7 @@ static int check_marks(const char* who, const rto_guidance_net* net, const uint3
 int rto_guidance_net_forward_packed_culled(rto_guidance_net* net, void* stream, const float* aux, int n, int H, int W, int flags,
                                            const uint32_t* tile_marks, int words_per_frame, float background) {
     if (!net || !aux || n < 1 || H < 1 || W < 1) return fail(RTO_E_INVALID, "rto_guidance_net_forward_packed: bad argument");
+    if (const int rc = refuse_general("rto_guidance_net_forward_packed", net)) return rc;
     if (pointer_device(aux) != net->device)
         return fail(RTO_E_INVALID, "rto_guidance_net_forward_packed: aux is not memory of the network's device");
     DeviceScope scope(net->device);
@@ -191,6 +282,7 @@ int rto_guidance_net_forward_packed(rto_guidance_net* net, void* stream, const f
 
 int rto_filtering_packed(const rto_guidance_net* net, void* stream, const float* img_in, float* img_out, int n, int H, int W) {
     if (!net || !img_in || !img_out || img_in == img_out) return fail(RTO_E_INVALID, "rto_filtering_packed: bad argument");
+    if (const int rc = refuse_general("rto_filtering_packed", net)) return rc;
     if (!net->packed || net->packed_n < 1) return fail(RTO_E_INVALID, "rto_filtering_packed: no packed maps (call rto_guidance_net_forward_packed first)");
     // the images are the caller's: their extent must be the one the maps were computed for, or the kernel would read and
     // write past a smaller buffer
@@ -239,24 +331,33 @@ static int ensure_fill_tile(rto_guidance_net* net, float bg, hipStream_t stream)
     constexpr int TE = rto::kFilterExactFillH, YE = (S / 2 / TE) * TE;  // the exact filter's tile: 32 x 8; its row in the frame
     if (!net->fill_tile && !ok(hipMalloc((void**)&net->fill_tile, (size_t)(T + TE) * T * 4 * sizeof(float))))
         return fail(RTO_E_HIP, std::string("fill tile: ") + hipGetErrorString(e));
-    if (!ok(hipMalloc((void**)&d_aux, aux.size() * sizeof(float))) || !ok(hipMalloc((void**)&d_img, img.size() * sizeof(float))) ||
-        !ok(hipMalloc((void**)&d_out, img.size() * sizeof(float))) || !ok(hipMalloc(&d_maps, px * 8 * sizeof(uint16_t))) ||
-        !ok(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice, stream)) ||
-        !ok(hipMemcpyAsync(d_img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, stream)) ||
-        !ok(rto::launch_guidance_net(d_aux, net->w1, net->w2, net->b2, net->c1, net->levels, 1, S, S, (float*)d_maps, nullptr, false, nullptr, 0, nullptr, nullptr, 0, 0.f, stream)) ||
-        !ok(rto::launch_filter_fast_packed(d_maps, S, S, 1, d_img, d_out, nullptr, 0, nullptr, 0, 0.f, nullptr, stream)) ||
-        !ok(hipMemcpy2DAsync(net->fill_tile, (size_t)T * 4 * sizeof(float), d_out + ((size_t)T * S + T) * 4, (size_t)S * 4 * sizeof(float),
-                             (size_t)T * 4 * sizeof(float), T, hipMemcpyDeviceToDevice, stream)) ||
-        !ok(hipMemcpyAsync(net->fill_k, (const char*)d_maps + ((size_t)(S / 2) * S + S / 2) * 16, 16, hipMemcpyDeviceToHost, stream)) ||
-        // the same through fp32 planes and the exact filter (rto_guidance_net_forward_culled / rto_filtering_culled)
-        !ok(hipMalloc((void**)&d_w, 4 * px * sizeof(float))) || !ok(hipMalloc((void**)&d_g, 4 * px * sizeof(float))) ||
-        !ok(rto::launch_guidance_net(d_aux, net->w1, net->w2, net->b2, net->c1, net->levels, 1, S, S, d_w, d_g, false, nullptr, 0, nullptr, nullptr, 0, 0.f, stream)) ||
-        !ok(rto::launch_filter(d_w, d_g, net->levels, S, S, 1, d_img, d_out, stream)) ||
+    const int L = net->levels;
+    bool good = ok(hipMalloc((void**)&d_aux, aux.size() * sizeof(float))) && ok(hipMalloc((void**)&d_img, img.size() * sizeof(float))) &&
+                ok(hipMalloc((void**)&d_out, img.size() * sizeof(float))) && ok(hipMalloc((void**)&d_w, L * px * sizeof(float))) &&
+                ok(hipMalloc((void**)&d_g, L * px * sizeof(float))) &&
+                ok(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice, stream)) &&
+                ok(hipMemcpyAsync(d_img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (good && !net->general)  // the factorised filter's tile and the packed background maps, by the packed route
+        good = ok(hipMalloc(&d_maps, px * 8 * sizeof(uint16_t))) &&
+               ok(rto::launch_guidance_net(d_aux, net->w1, net->w2, net->b2, net->c1, net->levels, 1, S, S, (float*)d_maps, nullptr, false, nullptr, 0, nullptr, nullptr, 0, 0.f, stream)) &&
+               ok(rto::launch_filter_fast_packed(d_maps, S, S, 1, d_img, d_out, nullptr, 0, nullptr, 0, 0.f, nullptr, stream)) &&
+               ok(hipMemcpy2DAsync(net->fill_tile, (size_t)T * 4 * sizeof(float), d_out + ((size_t)T * S + T) * 4, (size_t)S * 4 * sizeof(float),
+                                   (size_t)T * 4 * sizeof(float), T, hipMemcpyDeviceToDevice, stream)) &&
+               ok(hipMemcpyAsync(net->fill_k, (const char*)d_maps + ((size_t)(S / 2) * S + S / 2) * 16, 16, hipMemcpyDeviceToHost, stream));
+    // the same through fp32 planes and the exact filter (rto_guidance_net_forward_culled / rto_filtering_culled), by the net's own
+    // kernel and levels; a general net has no packed route: its factorised tile comes from the planes too
+    good = good && ok(launch_planes(net, d_aux, 1, S, S, d_w, d_g, 0, nullptr, 0, nullptr, stream));
+    if (good && net->general)
+        good = ok(rto::launch_filter_fast(d_w, d_g, L, S, S, 1, d_img, d_out, stream)) &&
+               ok(hipMemcpy2DAsync(net->fill_tile, (size_t)T * 4 * sizeof(float), d_out + ((size_t)T * S + T) * 4, (size_t)S * 4 * sizeof(float),
+                                   (size_t)T * 4 * sizeof(float), T, hipMemcpyDeviceToDevice, stream));
+    if (!good ||
+        !ok(rto::launch_filter(d_w, d_g, L, S, S, 1, d_img, d_out, stream)) ||
         !ok(hipMemcpy2DAsync(net->fill_tile + (size_t)T * T * 4, (size_t)T * 4 * sizeof(float), d_out + ((size_t)YE * S + T) * 4,
                              (size_t)S * 4 * sizeof(float), (size_t)T * 4 * sizeof(float), TE, hipMemcpyDeviceToDevice, stream)) ||
-        !ok(hipMemcpy2DAsync(net->fill_planes, sizeof(float), d_w + (size_t)(S / 2) * S + S / 2, px * sizeof(float), sizeof(float), 4,
+        !ok(hipMemcpy2DAsync(net->fill_planes, sizeof(float), d_w + (size_t)(S / 2) * S + S / 2, px * sizeof(float), sizeof(float), L,
                              hipMemcpyDeviceToHost, stream)) ||
-        !ok(hipMemcpy2DAsync(net->fill_planes + 4, sizeof(float), d_g + (size_t)(S / 2) * S + S / 2, px * sizeof(float), sizeof(float), 4,
+        !ok(hipMemcpy2DAsync(net->fill_planes + L, sizeof(float), d_g + (size_t)(S / 2) * S + S / 2, px * sizeof(float), sizeof(float), L,
                              hipMemcpyDeviceToHost, stream)) ||
         !ok(hipStreamSynchronize(stream))) {
         cleanup();
@@ -273,6 +374,7 @@ int rto_filtering_packed_culled(rto_guidance_net* net, void* stream, const float
                                 const uint32_t* tile_marks, int words_per_frame, float background) {
     if (!tile_marks) return rto_filtering_packed(net, stream, img_in, img_out, n, H, W);
     if (!net || !img_in || !img_out || img_in == img_out) return fail(RTO_E_INVALID, "rto_filtering_packed_culled: bad argument");
+    if (const int rc = refuse_general("rto_filtering_packed_culled", net)) return rc;
     if (!net->packed || net->packed_n < 1)
         return fail(RTO_E_INVALID, "rto_filtering_packed_culled: no packed maps (call rto_guidance_net_forward_packed first)");
     if (n != net->packed_n || H != net->packed_h || W != net->packed_w)
@@ -296,12 +398,13 @@ int rto_guidance_net_forward_culled(rto_guidance_net* net, void* stream, const f
     if (!tile_marks) return rto_guidance_net_forward_ex(net, stream, aux, n, H, W, weight_map, guidance_map, flags);
     if (!net || !aux || !weight_map || !guidance_map || n < 1 || H < 1 || W < 1)
         return fail(RTO_E_INVALID, "rto_guidance_net_forward_culled: bad argument");
+    if ((flags & RTO_NET_INPUT_SPARSE) && net->general)
+        if (const int rc = refuse_general("rto_guidance_net_forward_culled(RTO_NET_INPUT_SPARSE)", net)) return rc;
     if (const int rc = check_marks("rto_guidance_net_forward_culled", net, tile_marks, words_per_frame, H, W)) return rc;
     DeviceScope scope(net->device);
     if (const int rc = ensure_fill_tile(net, background, (hipStream_t)stream)) return rc;
-    const hipError_t e = rto::launch_guidance_net(aux, net->w1, net->w2, net->b2, net->c1, net->levels, n, H, W, weight_map, guidance_map,
-                                                  net_in_mode(flags), tile_marks, words_per_frame, nullptr,
-                                                  net->fill_planes, 0, 0.f, (hipStream_t)stream);
+    const hipError_t e = launch_planes(net, aux, n, H, W, weight_map, guidance_map, net_in_mode(flags), tile_marks, words_per_frame,
+                                       net->fill_planes, (hipStream_t)stream);
     if (e != hipSuccess) return fail(RTO_E_HIP, std::string("GuidanceNet launch failed: ") + hipGetErrorString(e));
     return RTO_OK;
 }
@@ -314,6 +417,10 @@ int rto_filtering_culled(rto_guidance_net* net, void* stream, const float* weigh
         return fail(RTO_E_INVALID, "rto_filtering_culled: bad argument");
     if (mode != RTO_FILTER_EXACT && mode != RTO_FILTER_FACTORISED) return fail(RTO_E_INVALID, "rto_filtering_culled: unknown mode");
     if (const int rc = check_marks("rto_filtering_culled", net, tile_marks, words_per_frame, H, W)) return rc;
+    // The filter kernels skip a tile whose staged region grown by TWO pixels (the receptive field of two 3x3 layers) is background.
+    // A map value of a three-layer net depends on the aux pixels three away: those nets run the plain kernels here (only their
+    // network is culled) -- the same bits either way, since the skipped tiles are copies of what the plain kernels compute.
+    if (net->num_layers > 2) return rto_filtering_batch_mode(stream, weight_map, guidance_map, net->levels, H, W, n, img_in, img_out, mode);
     if (pointer_device(img_out) != net->device || pointer_device(img_in) != net->device)
         return fail(RTO_E_INVALID, "rto_filtering_culled: the images are not memory of the network's device");
     DeviceScope scope(net->device);
@@ -362,10 +469,13 @@ int rto_denoise(rto_guidance_net* net, rto_ctx* ctx, int n, int mode, void* stre
             net_flags |= RTO_NET_INPUT_SPARSE;
         }
     }
-    if (mode == RTO_FILTER_FACTORISED) {
+    if (lean == 2)
+        if (const int rc = refuse_general("rto_denoise on sparse lean frames (rto_ctx_set_lean_outputs level 2)", net)) return rc;
+    if (mode == RTO_FILTER_FACTORISED && !net->general) {
         if (const int rc = rto_guidance_net_forward_packed_culled(net, stream, aux, n, H, W, net_flags, marks, words, bg)) return rc;
         return rto_filtering_packed_culled(net, stream, noisy, image, n, H, W, marks, words, bg);
     }
+    // fp32 planes: the exact route, and both routes of a general net (no packed maps for it)
     const size_t plane_floats = (size_t)n * net->levels * H * W;
     {
         DeviceScope scope(net->device);
@@ -379,7 +489,7 @@ int rto_denoise(rto_guidance_net* net, rto_ctx* ctx, int n, int mode, void* stre
     }
     float *wm = net->planes, *gm = net->planes + plane_floats;
     if (const int rc = rto_guidance_net_forward_culled(net, stream, aux, n, H, W, wm, gm, net_flags, marks, words, bg)) return rc;
-    return rto_filtering_culled(net, stream, wm, gm, H, W, n, noisy, image, RTO_FILTER_EXACT, marks, words, bg);
+    return rto_filtering_culled(net, stream, wm, gm, H, W, n, noisy, image, mode, marks, words, bg);
 }
 
 void rto_guidance_net_free(rto_guidance_net* net) {
@@ -390,6 +500,8 @@ void rto_guidance_net_free(rto_guidance_net* net) {
     if (net->planes) (void)hipFree(net->planes);
     if (net->w1) (void)hipFree(net->w1);
     if (net->w2) (void)hipFree(net->w2);
+    if (net->wm) (void)hipFree(net->wm);
+    if (net->bm) (void)hipFree(net->bm);
     if (net->b2) (void)hipFree(net->b2);
     delete net;
 }

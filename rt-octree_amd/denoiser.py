@@ -148,6 +148,9 @@ def compact_and_compile(model, device=None, example_hw=(800, 800)):
 class FusedGuidanceNet:
     """The compact GuidanceNet as ONE hand-written gfx950 kernel (csrc/guidance_kernels.hip, MFMA fp16
     with fp32 accumulation) instead of two MIOpen convolutions plus seven elementwise launches.
+    Any stack the trainer produces runs fused: 8 -> c1 [-> c1] -> 2 * levels with c1 in 1..64, levels in 1..6, two or three
+    layers (`c1`, `levels`, `num_layers`); forward_packed / filter_packed / reserve exist for the reference shape only
+    (`packed_route`) and raise RtoError otherwise.
     Built from a GuidanceNetCompact, from a TorchScript trace of that module (parameters named
     layers.<i>.conv.weight / .bias), or from a ts_*.ts as the REFERENCE's exporter writes it -- a traced
     closure without parameters whose conv weights are constants of the graph (network.py:194-201);
@@ -169,25 +172,34 @@ class FusedGuidanceNet:
 
     def __init__(self, module, device=0):
         import ctypes as C
-        from ._lib import check, lib
+        from ._lib import CGuidanceLayer, CGuidanceNetInfo, check, lib
         sd = {k: v.detach().float().cpu().contiguous() for k, v in module.state_dict().items()}
-        keys = ("layers.0.conv.weight", "layers.0.conv.bias", "layers.1.conv.weight", "layers.1.conv.bias")
-        if not sd and isinstance(module, torch.jit.ScriptModule):  # reference-format export
-            convs = self.graph_conv_constants(module)
-            if len(convs) == 2:
-                sd = {k: v.detach().float().cpu().contiguous()
-                      for k, v in zip(keys, (convs[0][0], convs[0][1], convs[1][0], convs[1][1]))}
-        if not all(k in sd for k in keys) or any(k.startswith("layers.2.") for k in sd):
-            raise ValueError("FusedGuidanceNet needs a two-layer compact GuidanceNet (layers.{0,1}.conv.*)")
-        w1, b1, w2, b2 = (sd[k] for k in keys)
-        if tuple(w1.shape[1:]) != (8, 3, 3) or tuple(w2.shape[2:]) != (3, 3) or w2.shape[1] != w1.shape[0]:
-            raise ValueError("unexpected GuidanceNet weight shapes")
-        self.c1, self.levels = int(w1.shape[0]), int(w2.shape[0]) // 2
+        if not sd and isinstance(module, torch.jit.ScriptModule):  # reference-format export: N convolution constants
+            sd = {}
+            for i, (w, b) in enumerate(self.graph_conv_constants(module)):
+                sd["layers.%d.conv.weight" % i] = w.detach().float().cpu().contiguous()
+                sd["layers.%d.conv.bias" % i] = b.detach().float().cpu().contiguous()
+        convs = []
+        while "layers.%d.conv.weight" % len(convs) in sd and "layers.%d.conv.bias" % len(convs) in sd:
+            convs.append((sd["layers.%d.conv.weight" % len(convs)], sd["layers.%d.conv.bias" % len(convs)]))
+        if len(convs) < 2 or len(sd) != 2 * len(convs):
+            raise ValueError("FusedGuidanceNet needs a compact GuidanceNet (layers.<i>.conv.weight / .bias, two or three layers)")
+        for w, b in convs:
+            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or tuple(b.shape) != (w.shape[0],):
+                raise ValueError("unexpected GuidanceNet weight shapes")
+        if convs[-1][0].shape[0] % 2:
+            raise ValueError("the last GuidanceNet layer writes 2 * kernel_levels channels")
         self.device = torch.device("cuda", device)
+        layers = (CGuidanceLayer * len(convs))()
+        for l, (w, b) in zip(layers, convs):
+            l.weight, l.bias, l.cin, l.cout = w.data_ptr(), b.data_ptr(), int(w.shape[1]), int(w.shape[0])
         h = C.c_void_p(0)
-        check(lib().rto_guidance_net_create(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), self.c1,
-                                            self.levels, device, C.byref(h)))
+        check(lib().rto_guidance_net_create_layers(layers, len(convs), int(convs[-1][0].shape[0]) // 2, device, C.byref(h)))
         self._h = h
+        info = CGuidanceNetInfo()
+        check(lib().rto_guidance_net_get_info(self._h, C.byref(info)))
+        self.c1, self.levels, self.num_layers = int(info.c1), int(info.levels), int(info.num_layers)
+        self.packed_route = bool(info.packed_route)  # packed fp16 maps / sparse frames: the reference shape (32, 4, two layers) only
         self._out = {}
 
     def __call__(self, aux, stream=None, squares_implied=False, cull=None, rgba=False):
@@ -361,7 +373,9 @@ class Denoiser:
     the (weight_map, guidance_map) contract is accepted too.  An empty path raises the reference's
     "No torchscript module is given to denoiser." (denoiser.cpp:13-16)."""
 
-    def __init__(self, ts_module, device=0):
+    def __init__(self, ts_module, device=0, fused=False):
+        """fused=True: run the network as the fused HIP kernel (FusedGuidanceNet: every compact stack 8 -> c1 [-> c1] ->
+        2 * levels with c1 in 1..64, levels in 1..6; anything else raises) instead of through PyTorch"""
         self.device = torch.device("cuda", device)
         if isinstance(ts_module, (str, bytes)):
             if not ts_module:
@@ -373,6 +387,7 @@ class Denoiser:
         else:
             self.module = ts_module.to(self.device)
         self.module.eval()
+        self.fused = FusedGuidanceNet(self.module, device=device) if fused else None
 
     @torch.no_grad()
     def denoise(self, cam, ctx, stream=None):
@@ -383,7 +398,10 @@ class Denoiser:
         with torch.cuda.stream(s) if hasattr(s, "cuda_stream") else _null():
             tm.torch_start()
             aux = torch.as_tensor(ctx.aux_view(), device=self.device)
-            weight_map, guidance_map = self.module(aux)
+            if self.fused is not None:  # (the renderer's aux buffer: planes 4..7 are the squares of planes 0..3)
+                weight_map, guidance_map = self.fused(aux.contiguous(), stream=s, squares_implied=True)
+            else:
+                weight_map, guidance_map = self.module(aux)
             weight_map = weight_map.squeeze(0).contiguous()
             guidance_map = guidance_map.squeeze(0).contiguous()
             tm.torch_stop()

@@ -1,7 +1,10 @@
 """Exports a trained GuidanceNet state_dict (default: the committed rt-octree_amd/weights/guidance_synth_lego.pt)
 as the TorchScript module volrend_headless loads with --ts_module -- the reference's own artefact
 (denoiser/network.py:170-208 compact_and_compile: fold the branches, cast to fp16, jit.trace).
-usage: python tools/export_ts.py [weights.pt] [out.ts]   (needs a HIP device: the fp16 module is traced on it)"""
+usage: python tools/export_ts.py [weights.pt] [out.ts] [--mid-channels C] [--layers N] [--levels L]
+(needs a HIP device: the fp16 module is traced on it; the shape options are those the weights were trained with,
+tools/train_guidance.py)"""
+import argparse
 import os
 import sys
 
@@ -13,9 +16,15 @@ from rt_octree_amd import denoiser  # noqa: E402
 
 
 def main():
-    wpath = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "rt-octree_amd", "weights", "guidance_synth_lego.pt")
-    out = sys.argv[2] if len(sys.argv) > 2 else "ts_latest.ts"
-    model = denoiser.GuidanceNet(8, 32, 5, 2, 4)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("weights", nargs="?", default=os.path.join(ROOT, "rt-octree_amd", "weights", "guidance_synth_lego.pt"))
+    ap.add_argument("out", nargs="?", default="ts_latest.ts")
+    ap.add_argument("--mid-channels", type=int, default=32)
+    ap.add_argument("--layers", type=int, default=2, choices=[2, 3])
+    ap.add_argument("--levels", type=int, default=4, choices=[1, 2, 3, 4, 5, 6])
+    args = ap.parse_args()
+    wpath, out = args.weights, args.out
+    model = denoiser.GuidanceNet(8, args.mid_channels, 5, args.layers, args.levels)
     model.load_state_dict(torch.load(wpath, map_location="cpu"))
     dev = "cuda:0" if torch.cuda.is_available() else None
     ts = denoiser.compact_and_compile(model, device=dev, example_hw=(800, 800))

@@ -1,5 +1,8 @@
 """Development harness: the fused GuidanceNet kernel alone (the bench's route: squares implied, packed fp16 maps) and
-the factorised filter behind it, ms per 50-frame batch at 800x800."""
+the factorised filter behind it, ms per 50-frame batch at 800x800.
+--shapes: the general kernel (guidance_general.inc) per network shape against torch's compact.half(), which is what such a
+net cost before it ran fused: same process, alternating, warm-up, median of 7 repetitions of 5 launches each."""
+import copy
 import os
 import sys
 
@@ -10,7 +13,46 @@ import torch  # noqa: E402
 from rt_octree_amd import denoiser  # noqa: E402
 
 
+SHAPES = [(8, 6, 2), (16, 3, 2), (64, 1, 2), (32, 4, 3), (64, 6, 3), (20, 2, 3), (8, 5, 3), (8, 4, 2), (16, 4, 2), (32, 6, 2), (64, 4, 2)]
+
+
+def shapes():
+    n, H, W, reps, inner = 50, 800, 800, 7, 5
+    aux = torch.rand(n, 8, H, W, device="cuda:0")
+    aux[:, 4:] = aux[:, :4] * aux[:, :4]
+    print("ms per %d frames at %dx%d, median of %d repetitions (min .. max); fp32 planes, all 8 aux planes read" % (n, W, H, reps))
+    for c1, levels, layers in SHAPES:
+        torch.manual_seed(0)
+        compact = denoiser.GuidanceNetCompact.from_full(denoiser.GuidanceNet(8, c1, 5, layers, levels)).eval()
+        fused = denoiser.FusedGuidanceNet(compact, device=0)
+        half = copy.deepcopy(compact).half().cuda()
+
+        def run_torch():
+            with torch.no_grad():
+                return half(aux)
+        times = {"fused": [], "torch": []}
+        for f in (lambda: fused(aux), run_torch):  # warm-up (MIOpen picks its algorithm here)
+            for _ in range(2):
+                f()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for name, f in (("fused", lambda: fused(aux)), ("torch", run_torch)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(inner):
+                    f()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) / inner)
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        print("c1 %2d levels %d layers %d: general kernel %7.3f (%.3f .. %.3f)   torch compact.half() %7.3f (%.3f .. %.3f)   x%.1f"
+              % (c1, levels, layers, med["fused"], min(times["fused"]), max(times["fused"]), med["torch"], min(times["torch"]),
+                 max(times["torch"]), med["torch"] / med["fused"]), flush=True)
+
+
 def main():
+    if "--shapes" in sys.argv[1:]:
+        return shapes()
     n, H, W = 50, 800, 800
     torch.manual_seed(0)
     full = denoiser.GuidanceNet(8, 32, 5, 2, 4)

@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--basis", type=int, default=16)
     ap.add_argument("--shell", type=float, default=2.5)
     ap.add_argument("--target-frames", type=int, default=32, help="SPP-32 frames averaged into a target")
+    ap.add_argument("--mid-channels", type=int, default=32, help="1..64 (the reference trainer's mid_channels); every such net runs as the fused HIP kernel")
+    ap.add_argument("--layers", type=int, default=2, choices=[2, 3], help="the reference trainer's num_layers")
+    ap.add_argument("--levels", type=int, default=4, choices=[1, 2, 3, 4, 5, 6], help="the reference trainer's kernel_levels")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "guidance_synth_lego.pt"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -95,7 +98,7 @@ def main():
     print("dataset: %d train + %d test poses in %.1fs" % (len(train_idx), len(test_idx), time.time() - t0), flush=True)
 
     torch.manual_seed(0)
-    model = denoiser.GuidanceNet(8, 32, 5, 2, 4).to(dev)  # denoiser/configs/blender.txt:21-25
+    model = denoiser.GuidanceNet(8, args.mid_channels, 5, args.layers, args.levels).to(dev)  # defaults: denoiser/configs/blender.txt:21-25
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999), weight_decay=5e-4)
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda it: 0.1 ** min(it / (args.iters + 1), 1))
     rs = np.random.RandomState(0)
