@@ -617,6 +617,15 @@ int rto_filtering_packed_culled(rto_guidance_net* net, void* stream, const float
  * Like the packed scratch, the plane scratch grows on demand and growing synchronises the device once: call it once at the
  * largest extent before a timed or captured region. */
 int rto_denoise(rto_guidance_net* net, rto_ctx* ctx, int n, int mode, void* stream);
+/* The launch shape of the denoise kernels for n frames of H x W.  In the factorised filter (filter_fast, tiles 32 x 16) and in
+ * the GuidanceNet kernels (tiles 32 x 8) a workgroup walks a STRIP of tiles along x, the next tile's loads in flight while the
+ * current one computes; the launchers choose the strip from the launch size: s = 5 (filter) / 13 (network), and while s > 1 and
+ * ceil(tiles_x / s) * tiles_y * n < 2048 one less -- a batch gets full strips, a lone frame short ones.  This call reports what
+ * a launch of that extent uses, computed by the functions the launchers call (the filter kernel derives its strip from the
+ * grid, ceil(tiles_x / ceil(tiles_x / s)): the same number unless tiles_x splits evenly into shorter strips).  No result
+ * depends on the strip; the tests use the query to prove which strips they reach.
+ * Touches no device.  RTO_E_INVALID: a non-positive extent or a null output. */
+int rto_denoise_launch_strips(int n, int H, int W, int* filter_strip, int* net_strip);
 void rto_guidance_net_free(rto_guidance_net* net);
 
 /* ---- profiling aid ---- */

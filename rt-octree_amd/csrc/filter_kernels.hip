@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(256, (PACKED || L <= 4) ? RTO_FAST_WGS : 3) fi
     const int tiles_x = (W + kFastW - 1) / kFastW;
     // the strip's length follows from the launch: ceil(tiles_x / gridDim.x) <= kFastStrip.  A batch of frames is launched with
     // full strips (the prefetch pays); a LONE frame with as short ones as it takes to put a few workgroups on every CU -- 250
-    // workgroups of 5 tiles each left three quarters of the chip idle while each walked its strip (fast_strip_for)
+    // workgroups of 5 tiles each left three quarters of the chip idle while each walked its strip (filter_fast_strip)
     const int strip = (tiles_x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int tx_first = blockIdx.x * strip;
     const int y0 = blockIdx.y * kFastH - L;
@@ -865,8 +865,10 @@ __global__ void __launch_bounds__(256, (PACKED || L <= 4) ? RTO_FAST_WGS : 3) fi
     }
 }
 
-// tiles per workgroup of filter_fast: kFastStrip when that still gives every CU its 8 workgroups, else shorter strips
-static int fast_strip_for(int tiles_x, int tiles_y, int n) {
+// tiles per workgroup of filter_fast for a launch of n frames of H x W: kFastStrip when that still gives every CU its 8
+// workgroups, else shorter strips.  The one statement of the rule: both launchers below and rto_denoise_launch_strips call it.
+int filter_fast_strip(int n, int H, int W) {
+    const int tiles_x = (W + kFastW - 1) / kFastW, tiles_y = (H + kFastH - 1) / kFastH;
     int s = kFastStrip;
     while (s > 1 && (int64_t)((tiles_x + s - 1) / s) * tiles_y * n < 2048) --s;
     return s;
@@ -876,7 +878,7 @@ hipError_t launch_filter_fast_packed(const void* packed_maps, int H, int W, int 
                                      const uint32_t* tile_mask, int mask_words, const float* fill_tile, int sparse, float background,
                                      const uint32_t* fill_maps, hipStream_t stream) {
     if (sparse && (!tile_mask || !fill_maps)) return hipErrorInvalidValue;
-    const int tiles_x = (W + kFastW - 1) / kFastW, tiles_y = (H + kFastH - 1) / kFastH, strip = fast_strip_for(tiles_x, tiles_y, n);
+    const int tiles_x = (W + kFastW - 1) / kFastW, tiles_y = (H + kFastH - 1) / kFastH, strip = filter_fast_strip(n, H, W);
     // (grid.x such that ceil(tiles_x / grid.x) == the strip the kernel derives: ceil(tiles_x / strip) workgroups per tile row)
     const dim3 grid((tiles_x + strip - 1) / strip, tiles_y, n), block(256);
     const size_t lds = (size_t)(2 * (kFastH + 8) * kFastRowStride) * sizeof(float4);  // P_l tile + window-row sums, parity-split rows
@@ -902,7 +904,7 @@ hipError_t launch_filter_fast_culled(const float* weight, const float* guidance,
                                      float* img_out, const uint32_t* tile_mask, int mask_words, const float* fill_tile,
                                      hipStream_t stream) {
     const FilterCull cull{tile_mask, mask_words, (W + 7) / 8, reinterpret_cast<const float4*>(fill_tile)};
-    const int tiles_x = (W + kFastW - 1) / kFastW, tiles_y = (H + kFastH - 1) / kFastH, strip = fast_strip_for(tiles_x, tiles_y, n);
+    const int tiles_x = (W + kFastW - 1) / kFastW, tiles_y = (H + kFastH - 1) / kFastH, strip = filter_fast_strip(n, H, W);
     // (grid.x such that ceil(tiles_x / grid.x) == the strip the kernel derives: ceil(tiles_x / strip) workgroups per tile row)
     const dim3 grid((tiles_x + strip - 1) / strip, tiles_y, n), block(256);
     const float4* in4 = reinterpret_cast<const float4*>(img_in);

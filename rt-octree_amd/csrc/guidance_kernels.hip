@@ -443,16 +443,22 @@ __global__ void __launch_bounds__(256, IN ? 4 : RTO_NET_SQ0_WG) guidance_fused(c
 
 }  // namespace
 
+// tiles per workgroup of guidance_fused / guidance_general for a launch of n frames of H x W: strips of kStrip tiles when that
+// still leaves every CU its workgroups (a batch of frames), shorter ones for a lone frame.  The one statement of the rule: both
+// launchers below and rto_denoise_launch_strips call it.
+int guidance_net_strip(int n, int H, int W) {
+    const int tiles_x = (W + kGW - 1) / kGW, tiles_y = (H + kGH - 1) / kGH;
+    int strip = kStrip;
+    while (strip > 1 && (int64_t)((tiles_x + strip - 1) / strip) * tiles_y * n < 2048) --strip;
+    return strip;
+}
+
 hipError_t launch_guidance_net(const float* aux, const void* w1, const void* w2, const float* b2, int c1,
                                int levels, int n, int H, int W, float* weight_out, float* guidance_out,
                                int in_mode, const uint32_t* tile_mask, int mask_words, const uint32_t* fill_k,
                                const float* fill_planes, int sparse, float background, hipStream_t stream) {
     if (c1 != 32 || levels != 4 || in_mode < 0 || in_mode > 2) return hipErrorInvalidValue;  // the reference configuration (blender.txt:21-25)
-    const int tiles_x = (W + kGW - 1) / kGW;
-    // strips of kStrip tiles when that still leaves every CU its workgroups (a batch of frames), shorter ones for a lone frame
-    const int tiles_y = (H + kGH - 1) / kGH;
-    int strip = kStrip;
-    while (strip > 1 && (int64_t)((tiles_x + strip - 1) / strip) * tiles_y * n < 2048) --strip;
+    const int tiles_x = (W + kGW - 1) / kGW, tiles_y = (H + kGH - 1) / kGH, strip = guidance_net_strip(n, H, W);
     const dim3 grid((tiles_x + strip - 1) / strip, tiles_y, n), block(256);
     const bool pack = guidance_out == nullptr;  // weight_out is then the packed fp16 buffer [n][H][W][8]
     NetCull cull;
@@ -482,9 +488,7 @@ hipError_t launch_guidance_general(const float* aux, const void* w1, const void*
     if ((c1p != 16 && c1p != 32 && c1p != 64) || (num_layers != 2 && num_layers != 3) || levels < 1 || levels > 6 || in_mode < 0 ||
         in_mode > 2 || !weight_out || !guidance_out)
         return hipErrorInvalidValue;
-    const int tiles_x = (W + kGW - 1) / kGW, tiles_y = (H + kGH - 1) / kGH;
-    int strip = kStrip;  // (as launch_guidance_net)
-    while (strip > 1 && (int64_t)((tiles_x + strip - 1) / strip) * tiles_y * n < 2048) --strip;
+    const int tiles_x = (W + kGW - 1) / kGW, tiles_y = (H + kGH - 1) / kGH, strip = guidance_net_strip(n, H, W);  // (as launch_guidance_net)
     const dim3 grid((tiles_x + strip - 1) / strip, tiles_y, n);
     NetCullG cull;
     cull.mask = fill_planes ? tile_mask : nullptr;

@@ -65,4 +65,10 @@ hipError_t launch_guidance_general(const float* aux, const void* w1, const void*
                                    int c1p, int num_layers, int levels, int n, int H, int W, float* weight_out, float* guidance_out,
                                    int in_mode, const uint32_t* tile_mask, int mask_words, const float* fill_planes, hipStream_t stream);
 
+// Tiles a workgroup walks along x ("strip") in a launch of n frames of H x W: filter_fast (both forms; tiles 32 x 16) and the
+// GuidanceNet kernels (guidance_fused, guidance_general; tiles 32 x 8).  Host arithmetic only; the launchers above call these
+// very functions (rto_denoise_launch_strips reports them).
+int filter_fast_strip(int n, int H, int W);
+int guidance_net_strip(int n, int H, int W);
+
 }  // namespace rto

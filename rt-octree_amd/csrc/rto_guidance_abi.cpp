@@ -492,6 +492,13 @@ int rto_denoise(rto_guidance_net* net, rto_ctx* ctx, int n, int mode, void* stre
     return rto_filtering_culled(net, stream, wm, gm, H, W, n, noisy, image, mode, marks, words, bg);
 }
 
+int rto_denoise_launch_strips(int n, int H, int W, int* filter_strip, int* net_strip) {
+    if (n < 1 || H < 1 || W < 1 || !filter_strip || !net_strip) return fail(RTO_E_INVALID, "rto_denoise_launch_strips: bad argument");
+    *filter_strip = rto::filter_fast_strip(n, H, W);
+    *net_strip = rto::guidance_net_strip(n, H, W);
+    return RTO_OK;
+}
+
 void rto_guidance_net_free(rto_guidance_net* net) {
     if (!net) return;
     DeviceScope scope(net->device);

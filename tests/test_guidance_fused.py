@@ -19,7 +19,7 @@ def _nets(seed=0):
     return compact, denoiser.FusedGuidanceNet(compact)
 
 
-@pytest.mark.parametrize("shape", [(1, 64, 96), (2, 37, 53), (1, 8, 32), (3, 5, 7), (1, 20, 333), (2, 9, 161)])  # 333: strips of 5 + 5 + 1 tiles
+@pytest.mark.parametrize("shape", [(1, 64, 96), (2, 37, 53), (1, 8, 32), (3, 5, 7), (1, 20, 333), (2, 9, 161)])  # 333: 11 tile columns, the last 13 pixels wide (these launches walk strips of 1: rto_denoise_launch_strips)
 def test_fused_matches_fp32_network(shape):
     n, H, W = shape
     compact, fused = _nets()

@@ -234,25 +234,10 @@ def cull_scene():
 
 def _net_tiles_skipped_and_computed(marks, n, H, W, halo):
     """from the tile marks: (network tiles 32 x 8 whose input region lies inside the image and in unmarked render tiles, others)"""
+    from denoise_synth import net_tiles_skipped_and_computed  # (the predicate lives with the other restated skip decisions)
     ptr, words, _s0, _frames, _bg = marks
     m = torch.as_tensor(volrend._DevArray(ptr, (n, words), None), device="cuda:0").view(torch.int32).cpu().numpy().view(np.uint32)
-    tx_n = (W + 7) // 8
-    skipped = computed = 0
-    for f in range(n):
-        keep_all = int(m[f, words - 1]) & 1
-        for ty in range((H + 7) // 8):
-            for tx in range((W + 31) // 32):
-                x0, y0 = tx * 32 - halo, ty * 8 - halo
-                x1, y1 = x0 + 32 + 2 * halo, y0 + 8 + 2 * halo
-                live = keep_all or x0 < 0 or y0 < 0 or x1 > W or y1 > H
-                if not live:
-                    for ry in range(y0 >> 3, ((y1 - 1) >> 3) + 1):
-                        for rx in range(x0 >> 3, ((x1 - 1) >> 3) + 1):
-                            t = ry * tx_n + rx
-                            live = live or ((int(m[f, t >> 5]) >> (t & 31)) & 1)
-                skipped += 0 if live else 1
-                computed += 1 if live else 0
-    return skipped, computed
+    return net_tiles_skipped_and_computed(m, H, W, halo)
 
 
 @gpu
