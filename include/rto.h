@@ -67,8 +67,8 @@ typedef struct rto_options {
     float render_bbox[6];         /* {0,0,0,1,1,1} */
     int basis_minmax[2];          /* {0,24} */
     float rot_dirs[3];            /* {0,0,0} */
-    int show_grid;                /* false; GUI */
-    int grid_max_depth;           /* 4; GUI */
+    int show_grid;                /* false; no launch reads it: rto_draw_grid_layers draws the grid into layers (rto_ctx_set_layers) */
+    int grid_max_depth;           /* 4; rto_grid_params_default takes it as the grid's max_depth */
     int render_depth;             /* false; unused by the kernel */
     int enable_probe;             /* false; draws the lumisphere of the leaf at `probe` into the frame's top right corner (see rto_launch_renderer) */
     float probe[3];               /* {0,0,1} */
@@ -341,6 +341,43 @@ typedef struct rto_query_out {
  * with sigma > 0 only -- load it with RTO_TREE_KEEP_REFERENCE as well. */
 int rto_tree_query(const rto_tree* tree, const float* points /* device [n][3] world space */, int64_t n,
                    const rto_query_out* out, void* stream);
+
+/* The octree grid of RenderOptions::show_grid (the reference's GL wireframe pass, cuda_renderer.cpp:112-124 over
+ * N3Tree::gen_wireframe, n3tree.cpp:390-434) ray-traced into a depth and a colour layer, the inputs of rto_ctx_set_layers.
+ * Cells: the tree's leaves cut off at level max_depth + 1 (levels of child[] visited; max_depth = 0: the root's eight children,
+ * gen_wireframe's `child == 0 || depth >= max_depth`), empty leaves included.  A pixel is a line pixel when its ray -- the
+ * pixel's ray of rto_launch_renderer -- passes within 0.5 * line_px pixels (perpendicular distance r = 0.5 * line_px / fx times
+ * the distance along the ray) of a cell edge at a cell face it crosses inside the volume; DESIGN.md section 7f has the exact
+ * float32 rule, tests/grid_ref.py restates it bit for bit.  No antialiasing; a ray that misses the volume's box is never a line
+ * pixel, however close it passes to the box's silhouette.
+ *   depth: device [n][H][W] float32 or NULL: the world distance along the pixel's unit ray to the line (the measure of
+ *          rto_rays.t_max and of the depth layer); +inf where there is none.
+ *   color: device [n][H][W][4] float32, 16-byte aligned, or NULL: (params->color, 1) on a line pixel, (background x 3, 1) elsewhere.
+ * RTO_GRID_MERGE: the GL depth test against what the buffers already hold (a mesh pass of the caller's): a line pixel replaces
+ * depth and colour only where the existing depth is greater than the line's; a pixel whose existing depth is <= 0 or NaN (not
+ * traced, see rto_ctx_set_layers) is left alone; nothing else is written.  It needs `depth`.
+ * All n cameras share width and height; frame f goes to plane f.  The cameras are read before the call returns and travel to the
+ * kernel BY VALUE, 32 per launch: the call does no allocation, no host synchronisation and no host-to-device copy, and is
+ * asynchronous on `stream`.  n == 0 launches nothing; n calls of one frame give the same bytes as one call of n frames.
+ * RTO_E_INVALID (checked before any device use; the buffers are untouched): a null tree / cams / params, both outputs NULL,
+ * n < 0, line_px not finite or <= 0, max_depth < 0 (above 22 it is clamped to 22), a non-finite colour or background, an
+ * unknown flag, RTO_GRID_MERGE without depth, color not 16-byte aligned, cameras of differing size, a camera whose width or
+ * height is <= 0 or whose fx / fy is zero or not finite.  RTO_E_UNSUPPORTED: a tree with NDC set (the line width is defined in
+ * unwarped space), N != 2, a tree with neither a traversal image nor child[] resident.  Trees loaded with
+ * RTO_TREE_QUANT_DIRECT work: the walk reads no values. */
+#define RTO_GRID_MERGE 1
+typedef struct rto_grid_params {
+    int max_depth;     /* >= 0 */
+    float line_px;     /* line width in pixels, > 0 */
+    float color[3];    /* the lines' rgb */
+    float background;  /* rgb of every other pixel of `color` */
+    int flags;         /* 0 or RTO_GRID_MERGE */
+} rto_grid_params;
+/* max_depth = o->grid_max_depth, line_px = 1, black lines, background = o->background_brightness, flags = 0 (o == NULL: the
+ * default options) */
+void rto_grid_params_default(rto_grid_params* p, const rto_options* o);
+int rto_draw_grid_layers(const rto_tree* tree, const rto_camera* cams /* host [n] */, int n, const rto_grid_params* p,
+                         float* depth, float* color, void* stream);
 
 /* ---- the operator ---- */
 /* launch_renderer(tree, cam, options, ctx, stream, offscreen) (volrend.cu:236-285); offscreen = false is a context with

@@ -8,10 +8,12 @@ from ._lib import LIB_PATH, RtoError, build_library, lib  # noqa: F401
 from .volrend import (  # noqa: F401
     Camera, N3Tree, RenderContext, RenderOptions, Timer, launch_renderer, launch_renderer_batch, filtering, render_rays, camera_rays,
     SUPPORTED_SPP, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST, FILTER_EXACT, FILTER_FAST, DEPTH_BATCHED,
+    GridParams, draw_grid_layers, GRID_MERGE,
 )
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
     "RenderOptions", "Timer", "launch_renderer", "launch_renderer_batch", "filtering", "render_rays", "camera_rays", "SUPPORTED_SPP",
     "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_FAST", "FILTER_EXACT", "FILTER_FAST", "DEPTH_BATCHED",
+    "GridParams", "draw_grid_layers", "GRID_MERGE",
 ]

@@ -52,6 +52,12 @@ class CQueryOut(C.Structure):
     _fields_ = [("values", C.c_void_p), ("sigma", C.c_void_p), ("level", C.c_void_p), ("cube", C.c_void_p)]
 
 
+class CGridParams(C.Structure):
+    """rto_grid_params (include/rto.h)"""
+    _fields_ = [("max_depth", C.c_int), ("line_px", C.c_float), ("color", C.c_float * 3), ("background", C.c_float),
+                ("flags", C.c_int)]
+
+
 class CGuidanceLayer(C.Structure):
     """rto_guidance_layer (include/rto.h): host pointers to one convolution's fp32 weights [cout][cin][3][3] and bias"""
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("cin", C.c_int), ("cout", C.c_int)]
@@ -94,6 +100,8 @@ SYMBOLS = {
     "rto_tree_set_ndc": (C.c_int, [_P, C.c_float, C.c_float, C.c_float]),
     "rto_tree_get_info": (C.c_int, [_P, C.POINTER(CTreeInfo)]),
     "rto_tree_query": (C.c_int, [_P, _P, C.c_int64, C.POINTER(CQueryOut), _P]),
+    "rto_grid_params_default": (None, [C.POINTER(CGridParams), C.POINTER(COptions)]),
+    "rto_draw_grid_layers": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(CGridParams), _P, _P, _P]),
     "rto_tree_probe_npz": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "rto_tree_free": (None, [_P]),
     "rto_ctx_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

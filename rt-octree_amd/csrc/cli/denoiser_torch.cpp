@@ -167,4 +167,14 @@ void TorchDenoiser::forward(float* aux, int n, int H, int W, const float** weigh
     *levels = (int)impl_->guidance.size(1);
 }
 
+struct DeviceFloats::Impl {
+    torch::Tensor t;
+};
+
+DeviceFloats::DeviceFloats(size_t n, int device) : impl_(new Impl) {
+    impl_->t = torch::empty({(int64_t)n}, torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA, device));
+}
+DeviceFloats::~DeviceFloats() = default;
+float* DeviceFloats::data() const { return impl_->t.data_ptr<float>(); }
+
 }  // namespace rto

@@ -3,6 +3,7 @@
 // guidance_map).  Kept behind a torch-free interface so volrend_headless.cpp itself compiles without
 // the libtorch headers.
 #pragma once
+#include <cstddef>
 #include <memory>
 #include <string>
 
@@ -31,6 +32,18 @@ public:
     // input_rgba (fused network only): `aux` is the noisy image [n][H][W][4] = (r, g, b, alpha) a lean batched launch leaves
     // (rto_ctx_set_lean_outputs, RTO_NET_INPUT_RGBA) instead of the 8-plane aux buffer
     void forward(float* aux, int n, int H, int W, const float** weight, const float** guidance, int* levels, bool input_rgba = false);
+
+private:
+    struct Impl;
+    std::unique_ptr<Impl> impl_;
+};
+
+// n floats of device memory on `device` that live as long as the object (libtorch's allocator): the layers --grid draws into
+class DeviceFloats {
+public:
+    DeviceFloats(size_t n, int device);
+    ~DeviceFloats();
+    float* data() const;
 
 private:
     struct Impl;

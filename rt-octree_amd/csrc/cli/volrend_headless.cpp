@@ -111,6 +111,9 @@ void usage() {
         "  -s,--step_size -e,--stop_thresh -a,--sigma_thresh   render options when no --options file\n"
         "  --probe x,y,z      (no --options file) draw the lumisphere of the leaf at that world point into the top right corner\n"
         "  --options opt.json render options (spp, denoise, ...)\n"
+        "  --grid N           show the octree grid cut off at depth N: sets show_grid and grid_max_depth (also over --options); every\n"
+        "                     launch's cameras get the grid drawn into a depth and a colour layer (rto_draw_grid_layers) and are\n"
+        "                     rendered over them (rto_ctx_set_layers)\n"
         "  --dataset blender|tt|llff (blender)\n"
         "  --ts_module ts.ts  TorchScript GuidanceNet (needed when denoise = true)\n"
         "  -o,--write_images DIR   write r_<i>.png (or buf_<name>.bin with --write_buffer)\n"
@@ -401,6 +404,11 @@ int main(int argc, char** argv) {
         }
     }
 
+    if (args.has("grid")) {  // opts.cpp: --grid <max depth>
+        options.show_grid = 1;
+        options.grid_max_depth = std::atoi(args.get("grid", "4").c_str());
+    }
+
     int batch = std::max(1, std::min(128, std::atoi(args.get("batch", "100").c_str())));
     const int filter_mode = args.has("fast_filter") ? RTO_FILTER_FACTORISED : RTO_FILTER_EXACT;
     {  // no more frame slots than this process has poses to render
@@ -434,6 +442,20 @@ int main(int argc, char** argv) {
     cam.fx = fx;
     cam.fy = fy;
     void* stream = nullptr;  // the default stream: libtorch's current stream in this process
+
+    // --grid: the grid of each launch's cameras goes into layers this program owns, one plane per frame slot, bound once
+    std::unique_ptr<rto::DeviceFloats> grid_depth, grid_color;
+    rto_grid_params grid_params;
+    rto_grid_params_default(&grid_params, &options);
+    const bool grid_on = args.has("grid");
+    if (grid_on) {
+        grid_depth = std::make_unique<rto::DeviceFloats>((size_t)batch * width * height, device);
+        grid_color = std::make_unique<rto::DeviceFloats>((size_t)batch * width * height * 4, device);
+        CHECK_RTO(rto_ctx_set_layers(ctx, grid_depth->data(), grid_color->data()));
+    }
+    auto draw_grid = [&](const rto_camera* cams_, int n) -> int {
+        return grid_on ? rto_draw_grid_layers(tree, cams_, n, &grid_params, grid_depth->data(), grid_color->data(), stream) : RTO_OK;
+    };
 
     // Denoiser::denoise (denoiser.cpp:31-61) for the n frames in context slots 0..n-1 (the selected slot must be 0 for
     // n > 1).  Fused network + --fast_filter: the maps stay packed fp16 between the two kernels (same pixels as fp32 maps).
@@ -476,6 +498,7 @@ int main(int argc, char** argv) {
     rto_timer_reset(ctx, stream);
     const int warmup = std::atoi(args.get("warmup", "100").c_str());
     std::memcpy(cam.transform, ps.trans[0].data(), sizeof(cam.transform));
+    if (warmup > 0) CHECK_RTO(draw_grid(&cam, 1));
     for (int i = 0; i < warmup; ++i) {
         CHECK_RTO(rto_launch_renderer(tree, &cam, &options, ctx, stream));
         if (options.denoise) CHECK_RTO(denoise());
@@ -526,6 +549,7 @@ int main(int argc, char** argv) {
             }
             rto_ctx_select_frame(ctx, 0);
             rto_timer_start(ctx, RTO_T_RENDER);
+            CHECK_RTO(draw_grid(cams.data(), n));
             int launched = rto_launch_renderer_batch(tree, cams.data(), jumps.data(), n, &options, ctx, stream);
             if (launched == RTO_E_UNSUPPORTED && write_depth && lean_on) {
                 // --write_depth on a launch the persistent kernels cannot take (an N != 2 tree, too many leaf slots for the spp, the
@@ -589,6 +613,7 @@ int main(int argc, char** argv) {
         if ((int)(i % shard_n) == shard_i) {
             std::memcpy(cam.transform, ps.trans[i].data(), sizeof(cam.transform));
             rto_timer_start(ctx, RTO_T_RENDER);
+            CHECK_RTO(draw_grid(&cam, 1));
             CHECK_RTO(rto_launch_renderer(tree, &cam, &options, ctx, stream));
             rto_timer_stop(ctx, RTO_T_RENDER);
             if (options.denoise) CHECK_RTO(denoise());

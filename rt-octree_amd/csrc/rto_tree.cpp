@@ -1,6 +1,7 @@
 // rto_tree.cpp -- the rto_tree_* half of the C ABI (include/rto.h): a tree's upload in stages, its lazily rebuilt reference
 // arrays, point queries and the basis probe.  The layouts themselves are computed in host/tree_layout.cpp.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -650,6 +651,80 @@ int rto_tree_query(const rto_tree* tree, const float* points, int64_t n, const r
         qo.cube = out->cube ? out->cube + 4 * i0 : nullptr;
         const hipError_t e = rto::launch_query(tree->dev, walk, vs, points + 3 * i0, std::min(per_launch, n - i0), qo, (hipStream_t)stream_);
         if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("query launch failed: ") + hipGetErrorString(e));
+    }
+    return RTO_OK;
+}
+
+void rto_grid_params_default(rto_grid_params* p, const rto_options* o) {
+    if (!p) return;
+    rto_options def;
+    if (!o) {
+        rto_options_default(&def);
+        o = &def;
+    }
+    p->max_depth = o->grid_max_depth;
+    p->line_px = 1.f;
+    p->color[0] = p->color[1] = p->color[2] = 0.f;  // black lines
+    p->background = o->background_brightness;
+    p->flags = 0;
+}
+
+int rto_draw_grid_layers(const rto_tree* tree, const rto_camera* cams, int n, const rto_grid_params* p, float* depth, float* color,
+                         void* stream_) {
+    if (!tree || !cams || !p) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: null tree, cams or params");
+    if (!depth && !color) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: depth and color are both null");
+    if (n < 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: n must be >= 0");
+    if (!(std::isfinite(p->line_px) && p->line_px > 0.f)) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: line_px must be finite and > 0");
+    if (p->max_depth < 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: max_depth must be >= 0");
+    if (!(std::isfinite(p->color[0]) && std::isfinite(p->color[1]) && std::isfinite(p->color[2]) && std::isfinite(p->background)))
+        return set_err(RTO_E_INVALID, "rto_draw_grid_layers: the line colour and the background must be finite");
+    if (p->flags & ~RTO_GRID_MERGE) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: unknown flag");
+    if ((p->flags & RTO_GRID_MERGE) && !depth)
+        return set_err(RTO_E_INVALID, "rto_draw_grid_layers: RTO_GRID_MERGE tests against the depth buffer, which is null");
+    if ((uintptr_t)color % 16 != 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: color must be 16-byte aligned");
+    for (int f = 0; f < n; ++f) {
+        const rto_camera& c = cams[f];
+        if (c.width != cams[0].width || c.height != cams[0].height)
+            return set_err(RTO_E_INVALID, "rto_draw_grid_layers: the cameras of one call share width and height");
+        if (c.width <= 0 || c.height <= 0 || c.height > 65535 * 16 || !std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.f || c.fy == 0.f)
+            return set_err(RTO_E_INVALID, "rto_draw_grid_layers: a camera's width, height (<= 1048560), fx or fy is out of range");
+    }
+    if (tree->dev.ndc_width > 0)
+        return set_err(RTO_E_UNSUPPORTED, "rto_draw_grid_layers: the line width is defined in unwarped space: NDC trees are not drawn");
+    if (tree->dev.N != 2) return set_err(RTO_E_UNSUPPORTED, "rto_draw_grid_layers: N != 2");
+    int walk;
+    rto::ValuesSrc vs;
+    (void)query_plan(tree, false, &walk, &vs);
+    if (walk == rto::kWalkChild && !tree->dev.child)
+        return set_err(RTO_E_UNSUPPORTED, "rto_draw_grid_layers: the tree has neither a traversal image nor child[] resident");
+    if (n == 0) return RTO_OK;
+    DeviceGuard guard(tree->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    rto::GridDraw gd;
+    gd.width = cams[0].width;
+    gd.height = cams[0].height;
+    gd.max_depth = std::min(p->max_depth, 22);
+    gd.merge = (p->flags & RTO_GRID_MERGE) ? 1 : 0;
+    gd.line_px = p->line_px;
+    for (int i = 0; i < 3; ++i) gd.color_rgb[i] = p->color[i];
+    gd.background = p->background;
+    const size_t px = (size_t)gd.width * gd.height;
+    for (int f0 = 0; f0 < n; f0 += rto::kGridCamChunk) {
+        const int m = std::min(rto::kGridCamChunk, n - f0);
+        rto::GridCams gc;
+        for (int f = 0; f < m; ++f) {
+            const rto_camera& c = cams[f0 + f];
+            gc.c[f].width = c.width;
+            gc.c[f].height = c.height;
+            gc.c[f].fx = c.fx;
+            gc.c[f].fy = c.fy;
+            std::memcpy(gc.c[f].transform, c.transform, sizeof(c.transform));
+        }
+        for (int f = m; f < rto::kGridCamChunk; ++f) gc.c[f] = gc.c[0];
+        gd.depth = depth ? depth + (size_t)f0 * px : nullptr;
+        gd.color = color ? reinterpret_cast<float4*>(color) + (size_t)f0 * px : nullptr;
+        const hipError_t e = rto::launch_grid_layers(tree->dev, walk, gd, gc, m, (hipStream_t)stream_);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("grid launch failed: ") + hipGetErrorString(e));
     }
     return RTO_OK;
 }

@@ -18,10 +18,11 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, COptions, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoError, check, lib
+from ._lib import CCamera, CGridParams, COptions, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoError, check, lib
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
+GRID_MERGE = 1  # RTO_GRID_MERGE (draw_grid_layers(merge=True))
 DEPTH_BATCHED = 2  # RTO_DEPTH_BATCHED (RenderContext.enable_depth(batched=True))
 AUX_CHANNELS = 8  # render_context.hpp:23
 _FORMAT_NAMES = {0: "RGBA", 1: "SH", 2: "SG", 3: "ASG"}
@@ -383,6 +384,29 @@ class RenderContext:
         check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
+    def show_grid(self, tree, cams, options, params=None, stream=None):
+        """RenderOptions.show_grid for this context: draws the octree grid of `tree` cut off at options.grid_max_depth
+        (draw_grid_layers; `params`: a GridParams instead of the defaults taken from `options`) for `cams` -- one Camera per frame
+        slot, or a single Camera for a single-slot context -- into a depth and a colour tensor the context keeps alive, and binds
+        them with set_layers: the launches that follow render over the grid.  Returns (depth [frames, H, W], color [frames, H, W,
+        4]).  set_layers() with no arguments restores the offscreen behaviour."""
+        import torch
+        if isinstance(cams, Camera):
+            cams = [cams]
+        if len(cams) != self.frames:
+            raise RtoError(-1, "show_grid: %d cameras for a context of %d frame slots" % (len(cams), self.frames))
+        device = torch.device("cuda", self.device)
+        keep = getattr(self, "_grid_layers", None)
+        if keep is None:
+            keep = (torch.empty((self.frames, self.height, self.width), dtype=torch.float32, device=device),
+                    torch.empty((self.frames, self.height, self.width, 4), dtype=torch.float32, device=device))
+            self._grid_layers = keep
+        if params is None:
+            params = GridParams(options)
+        draw_grid_layers(tree, cams, params, depth=keep[0], color=keep[1], stream=stream)
+        self.set_layers(keep[0], keep[1])
+        return keep
+
     def enable_depth(self, on=True, batched=False):
         """rto_ctx_enable_depth: launch_renderer / launch_renderer_batch also write depth and t_near [frames, H, W] (include/rto.h
         "depth outputs").  Batches are then rendered frame by frame through the single-frame kernels -- or, with batched=True
@@ -538,6 +562,72 @@ def launch_renderer_batch(tree, cams, options, ctx, stream=None, rng_jumps=None)
         jumps = (C.c_int64 * n)(*[int(j) for j in rng_jumps])
     co = options.to_c()
     check(lib().rto_launch_renderer_batch(tree._h, arr, jumps, n, C.byref(co), ctx._h, _stream_ptr(stream)))
+
+
+class GridParams:
+    """rto_grid_params: max_depth, line_px, color (the lines' rgb), background.  GridParams(options) takes max_depth =
+    options.grid_max_depth and background = options.background_brightness (rto_grid_params_default)."""
+
+    def __init__(self, options=None, **kw):
+        c = CGridParams()
+        co = options.to_c() if options is not None else None
+        lib().rto_grid_params_default(C.byref(c), C.byref(co) if co is not None else None)
+        self.max_depth, self.line_px = c.max_depth, c.line_px
+        self.color = list(c.color)
+        self.background = c.background
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError("GridParams has no field '%s'" % k)
+            setattr(self, k, v)
+
+    def to_c(self, merge=False):
+        c = CGridParams()
+        c.max_depth, c.line_px, c.background = int(self.max_depth), float(self.line_px), float(self.background)
+        for i in range(3):
+            c.color[i] = float(self.color[i])
+        c.flags = GRID_MERGE if merge else 0
+        return c
+
+
+def draw_grid_layers(tree, cams, params=None, depth=None, color=None, merge=False, stream=None):
+    """rto_draw_grid_layers: the octree grid of `tree` (RenderOptions.show_grid) ray-traced for the n cameras `cams` (one size)
+    into depth [n, H, W] and color [n, H, W, 4], contiguous float32 torch tensors on the tree's device -- allocated here when not
+    given; pass depth=False / color=False for an output that is not wanted.  params: a GridParams (None: the defaults of the
+    default options).  merge=True (RTO_GRID_MERGE): depth-test the lines against what the given tensors hold instead of
+    overwriting them.  Returns (depth, color) (None for an output not asked for), the inputs of RenderContext.set_layers.
+    Asynchronous on `stream` (default: torch's current stream); no sync."""
+    import torch
+    device = torch.device("cuda", tree.device)
+    if isinstance(cams, Camera):
+        cams = [cams]
+    n = len(cams)
+    if params is None:
+        params = GridParams()
+    H, W = (cams[0].height, cams[0].width) if n else (0, 0)
+    if merge and (depth is None or depth is False):
+        raise RtoError(-1, "draw_grid_layers: merge=True tests against a depth tensor of the caller's")
+
+    def plane(t, shape, name):
+        if t is False:
+            return None
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape)
+                or t.device != device):
+            raise RtoError(-1, "%s must be a contiguous float32 tensor of shape %s on %s" % (name, list(shape), device))
+        return t
+
+    d = plane(depth, (n, H, W), "depth")
+    c = plane(color, (n, H, W, 4), "color")
+    if n == 0:
+        return d, c
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    arr = (CCamera * n)(*[cam.to_c() for cam in cams])
+    cp = params.to_c(merge)
+    check(lib().rto_draw_grid_layers(tree._h, arr, n, C.byref(cp), C.c_void_p(d.data_ptr()) if d is not None else None,
+                                     C.c_void_p(c.data_ptr()) if c is not None else None, _stream_ptr(stream)))
+    return d, c
 
 
 def camera_rays(cam):
