@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 
 #include "rto_depth_launch.h"
+#include "rto_dispatch.h"
 #include "rto_render_shared.h"
 
 namespace rto {
@@ -95,109 +96,72 @@ __global__ void __launch_bounds__(256, persist_depth_wps(SPP, WPS, WIDE)) render
 }
 
 // ------------------------------------------------------------------ launchers (declared in rto_depth_launch.h)
+// spp, lobe form and traversal image are dispatched here, by the helpers render_kernels.hip's launchers use (rto_dispatch.h)
 
-template <int SPP, bool WIDE>
-const void* persist_depth_kernel(bool regstack) {
-    return regstack ? reinterpret_cast<const void*>(&render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, WIDE ? 1 : 0>)
-                    : reinterpret_cast<const void*>(&render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, 0>);
+const void* persist_depth_kernel(int spp, const TreeDev& tree) {
+    const void* fn = nullptr;
+    (void)with_spp(spp, [&](auto SPP) {
+        with_image(tree, [&](auto wide, auto stack) { fn = reinterpret_cast<const void*>(&render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, wide, stack>); });
+        return hipSuccess;
+    });
+    return fn;
 }
 
-template <int SPP, bool WIDE>
-void launch_persist_depth(bool regstack, int grid, size_t lds, hipStream_t stream, const TreeDev& tree, const OptDev& opt,
-                          const FrameBatch& fb, unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers,
-                          const DepthOut& depth) {
-    if (regstack)
-        hipLaunchKernelGGL((render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, WIDE ? 1 : 0>), dim3(grid), dim3(256), lds, stream, tree, opt,
-                           fb, queue, hits, chunk, layers, depth);
-    else
-        hipLaunchKernelGGL((render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
-                           hits, chunk, layers, depth);
+hipError_t launch_persist_depth(int spp, const TreeDev& tree, int grid, size_t lds, hipStream_t stream, const OptDev& opt, const FrameBatch& fb,
+                                unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers, const DepthOut& depth) {
+    return with_spp(spp, [&](auto SPP) {
+        with_image(tree, [&](auto wide, auto stack) {
+            hipLaunchKernelGGL((render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, wide, stack>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
+                               hits, chunk, layers, depth);
+        });
+        return hipGetLastError();
+    });
 }
 
-template <int SPP, int LOBES>
-void launch_fast_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                       const FrameOut& fo, int strip_rows, const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
+hipError_t launch_fast_depth(int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                             const FrameOut& fo, int strip_rows, const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
     const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
-    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
     const dim3 grid(8 * tm.per_xcd), block(256);
-#define RTO_FAST_D(WI, SK) \
-    hipLaunchKernelGGL((render_fast_layers_depth<SPP, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, layers, depth)
-    if (tree.widew) {  // (launch_fast's choice of the image)
-        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
-            RTO_FAST_D(true, 1);
-        } else {
-            RTO_FAST_D(true, 0);
-        }
-    } else {
-        RTO_FAST_D(false, 0);
-    }
-#undef RTO_FAST_D
+    return with_spp(spp, [&](auto SPP) {
+        with_lobes(tree, [&](auto LOBES) {
+            with_image(tree, [&](auto wide, auto stack) {
+                hipLaunchKernelGGL((render_fast_layers_depth<SPP, wide, stack, LOBES>), grid, block, fast_lds_bytes(tree), stream, tree, cam, opt, rng,
+                                   jump, tm, fo, layers, depth);
+            });
+        });
+        return hipGetLastError();
+    });
 }
 
-template <int SPP>
-void launch_generic_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const FrameOut& fo,
-                          const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
+hipError_t launch_generic_depth(int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const FrameOut& fo,
+                                const LayerDev& layers, const DepthOut& depth, hipStream_t stream) {
     const int64_t size = (int64_t)cam.width * cam.height;
-    hipLaunchKernelGGL(render_generic_layers_depth<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam, opt, rng, fo,
-                       layers, depth);
+    return with_spp(spp, [&](auto SPP) {
+        hipLaunchKernelGGL(render_generic_layers_depth<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam, opt, rng, fo,
+                           layers, depth);
+        return hipGetLastError();
+    });
 }
 
-template <int SPP, int LOBES>
-void launch_rays_depth_fast(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump, const RayBatch& rb,
-                            const DepthOut& depth, dim3 grid, hipStream_t stream) {
-    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
-#define RTO_RAYS_D(WI, SK) hipLaunchKernelGGL((render_rays_depth<SPP, WI, SK, LOBES>), grid, dim3(256), lds, stream, tree, opt, rng, jump, rb, depth)
-    if (tree.widew) {  // (launch_fast's choice)
-        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
-            RTO_RAYS_D(true, 1);
-        } else {
-            RTO_RAYS_D(true, 0);
-        }
-    } else {
-        RTO_RAYS_D(false, 0);
-    }
-#undef RTO_RAYS_D
+hipError_t launch_rays_depth_fast(int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                                  const RayBatch& rb, const DepthOut& depth, dim3 grid, hipStream_t stream) {
+    return with_spp(spp, [&](auto SPP) {
+        with_lobes(tree, [&](auto LOBES) {
+            with_image(tree, [&](auto wide, auto stack) {
+                hipLaunchKernelGGL((render_rays_depth<SPP, wide, stack, LOBES>), grid, dim3(256), fast_lds_bytes(tree), stream, tree, opt, rng, jump,
+                                   rb, depth);
+            });
+        });
+        return hipGetLastError();
+    });
 }
 
-template <int SPP>
-void launch_rays_depth_generic(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb, const DepthOut& depth,
-                               dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL(render_rays_generic_depth<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb, depth);
+hipError_t launch_rays_depth_generic(int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb,
+                                     const DepthOut& depth, dim3 grid, hipStream_t stream) {
+    return with_spp(spp, [&](auto SPP) {
+        hipLaunchKernelGGL(render_rays_generic_depth<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb, depth);
+        return hipGetLastError();
+    });
 }
-
-// every SPP of launch_render / launch_rays (RTO_DEV_SPP6_ONLY: the development build's one)
-#define RTO_DEPTH_INSTANCES(SPP)                                                                                                       \
-    template void launch_generic_depth<SPP>(const TreeDev&, const CamDev&, const OptDev&, const Pcg32&, const FrameOut&, const LayerDev&, \
-                                            const DepthOut&, hipStream_t);                                                              \
-    template void launch_rays_depth_generic<SPP>(const TreeDev&, const OptDev&, const Pcg32&, const RayBatch&, const DepthOut&, dim3,   \
-                                                 hipStream_t);                                                                          \
-    template const void* persist_depth_kernel<SPP, true>(bool);                                                                         \
-    template const void* persist_depth_kernel<SPP, false>(bool);                                                                        \
-    RTO_DEPTH_INSTANCES_P(SPP, true)                                                                                                    \
-    RTO_DEPTH_INSTANCES_P(SPP, false)                                                                                                   \
-    RTO_DEPTH_INSTANCES_L(SPP, 0)                                                                                                       \
-    RTO_DEPTH_INSTANCES_L(SPP, kFmtSG)                                                                                                  \
-    RTO_DEPTH_INSTANCES_L(SPP, kFmtASG)
-#define RTO_DEPTH_INSTANCES_P(SPP, WI)                                                                                                  \
-    template void launch_persist_depth<SPP, WI>(bool, int, size_t, hipStream_t, const TreeDev&, const OptDev&, const FrameBatch&,        \
-                                                unsigned long long*, uint32_t*, uint32_t, const LayerDev&, const DepthOut&);
-#define RTO_DEPTH_INSTANCES_L(SPP, L)                                                                                                   \
-    template void launch_fast_depth<SPP, L>(const TreeDev&, const CamDev&, const OptDev&, const Pcg32&, const PcgJumpEntry*,            \
-                                            const FrameOut&, int, const LayerDev&, const DepthOut&, hipStream_t);                       \
-    template void launch_rays_depth_fast<SPP, L>(const TreeDev&, const OptDev&, const Pcg32&, const PcgJumpEntry*, const RayBatch&,      \
-                                                 const DepthOut&, dim3, hipStream_t);
-#ifndef RTO_DEV_SPP6_ONLY
-RTO_DEPTH_INSTANCES(1)
-RTO_DEPTH_INSTANCES(2)
-RTO_DEPTH_INSTANCES(3)
-RTO_DEPTH_INSTANCES(4)
-RTO_DEPTH_INSTANCES(8)
-RTO_DEPTH_INSTANCES(16)
-RTO_DEPTH_INSTANCES(32)
-#endif
-RTO_DEPTH_INSTANCES(6)
-#undef RTO_DEPTH_INSTANCES_L
-#undef RTO_DEPTH_INSTANCES_P
-#undef RTO_DEPTH_INSTANCES
 
 }  // namespace rto

@@ -745,6 +745,7 @@ __global__ void rgba8_kernel(const float4* __restrict__ in, uchar4* __restrict__
 
 // ------------------------------------------------------------------ host launchers (C++ linkage,
 // declared in rto_launch.h)
+#include "rto_dispatch.h"
 #include "rto_launch.h"
 
 namespace rto {
@@ -806,135 +807,48 @@ template <int SPP, int LOBES>
 static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
                         const FrameOut& fo, int strip_rows, const LayerDev* layers, hipStream_t stream) {
     const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
-    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
+    const size_t lds = fast_lds_bytes(tree);
     const dim3 grid(8 * tm.per_xcd), block(256);
-#define RTO_FAST(ST, WI, SK)                                                                                                         \
-    if constexpr (LOBES == 0)                                                                                                        \
-        hipLaunchKernelGGL((render_fast<SPP, ST, WI, SK>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);             \
-    else                                                                                                                             \
-        hipLaunchKernelGGL((render_fast_lobes<SPP, ST, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo)
-    if (layers) {  // (launch_fast's choice of the image; the host refuses layers with work counters)
-        const LayerDev ld = *layers;
-#define RTO_FAST_L(WI, SK) hipLaunchKernelGGL((render_fast_layers<SPP, WI, SK, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, ld)
-        if (tree.widew) {
-            if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
-                RTO_FAST_L(true, 1);
-            } else {
-                RTO_FAST_L(true, 0);
-            }
-        } else {
-            RTO_FAST_L(false, 0);
-        }
-#undef RTO_FAST_L
-    } else if (fo.stats) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
-        RTO_FAST(true, false, 0);
-    } else if (tree.widew) {
-        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {  // two pairs of levels below the grid at most
-            RTO_FAST(false, true, 1);
-        } else {
-            RTO_FAST(false, true, 0);
-        }
-    } else {
-        RTO_FAST(false, false, 0);
-    }
-#undef RTO_FAST
-}
-
-template <int SPP>
-static hipError_t launch_spp(int kernel, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
-                             const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows, const LayerDev* layers,
-                             const DepthOut* depth, hipStream_t stream) {
-    if (depth) {  // the depth-carrying layered kernels (depth_kernels.hip), over the context's layers or none
-        const LayerDev ld = layers ? *layers : LayerDev{nullptr, nullptr};
-        if (kernel != 2)
-            launch_generic_depth<SPP>(tree, cam, opt, rng, fo, ld, *depth, stream);
-        else if (tree.format == kFmtSG)
-            launch_fast_depth<SPP, kFmtSG>(tree, cam, opt, rng, jump, fo, strip_rows, ld, *depth, stream);
-        else if (tree.format == kFmtASG)
-            launch_fast_depth<SPP, kFmtASG>(tree, cam, opt, rng, jump, fo, strip_rows, ld, *depth, stream);
+    const auto offscreen = [&](auto stats, auto wide, auto stack) {
+        if constexpr (LOBES == 0)
+            hipLaunchKernelGGL((render_fast<SPP, stats, wide, stack>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
         else
-            launch_fast_depth<SPP, 0>(tree, cam, opt, rng, jump, fo, strip_rows, ld, *depth, stream);
-        return hipGetLastError();
-    }
-    if (kernel == 2) {
-        if (tree.format == kFmtSG)
-            launch_fast<SPP, kFmtSG>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
-        else if (tree.format == kFmtASG)
-            launch_fast<SPP, kFmtASG>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
-        else
-            launch_fast<SPP, 0>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream);
-    } else {
-        const int64_t size = (int64_t)cam.width * cam.height;
-        if (layers)
-            hipLaunchKernelGGL(render_generic_layers<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam, opt, rng,
-                               fo, *layers);
-        else
-        hipLaunchKernelGGL(render_generic<SPP>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, stream, tree, cam,
-                           opt, rng, fo);
-    }
-    return hipGetLastError();
-}
-
-template <int SPP, int LOBES>
-static void launch_rays_fast(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump, const RayBatch& rb,
-                             const DepthOut* depth, const dim3 grid, hipStream_t stream) {
-    const size_t lds = (size_t)(tree.max_depth + 1) * 256 * sizeof(uint32_t);
-    if (depth) {  // the depth-carrying kernel (depth_kernels.hip: the same choice of the image)
-        launch_rays_depth_fast<SPP, LOBES>(tree, opt, rng, jump, rb, *depth, grid, stream);
+            hipLaunchKernelGGL((render_fast_lobes<SPP, stats, wide, stack, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
+    };
+    if (fo.stats && !layers) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
+        offscreen(std::true_type{}, std::false_type{}, int_c<0>{});
         return;
     }
-#define RTO_RAYS(WI, SK) hipLaunchKernelGGL((render_rays<SPP, WI, SK, LOBES>), grid, dim3(256), lds, stream, tree, opt, rng, jump, rb)
-    if (tree.widew) {  // (launch_fast's choice)
-        if ((tree.max_depth - tree.top_levels + 1) / 2 <= 2) {
-            RTO_RAYS(true, 1);
-        } else {
-            RTO_RAYS(true, 0);
-        }
-    } else {
-        RTO_RAYS(false, 0);
-    }
-#undef RTO_RAYS
+    with_image(tree, [&](auto wide, auto stack) {
+        if (layers)  // (the host refuses layers with work counters)
+            hipLaunchKernelGGL((render_fast_layers<SPP, wide, stack, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, *layers);
+        else
+            offscreen(std::false_type{}, wide, stack);
+    });
 }
 
-template <int SPP>
-static hipError_t launch_rays_spp(int kernel, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                                  const RayBatch& rb_in, const DepthOut* depth, bool xcd_order, hipStream_t stream) {
+hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                       const RayBatch& rb_in, const DepthOut* depth, bool xcd_order, hipStream_t stream) {
+    if (rb_in.n == 0) return hipSuccess;
+    if ((uint64_t)rb_in.n * (uint64_t)spp >= (uint64_t(1) << 32)) return hipErrorInvalidValue;  // (the RNG offset of a ray is 32-bit)
     RayBatch rb = rb_in;
     const uint32_t blocks = (uint32_t)(((uint64_t)rb.n + 255) / 256);
     rb.per_xcd = xcd_order ? (blocks + 7) / 8 : 0u;
     const dim3 grid(xcd_order ? 8 * rb.per_xcd : blocks);
-    if (kernel == 2) {
-        if (tree.format == kFmtSG)
-            launch_rays_fast<SPP, kFmtSG>(tree, opt, rng, jump, rb, depth, grid, stream);
-        else if (tree.format == kFmtASG)
-            launch_rays_fast<SPP, kFmtASG>(tree, opt, rng, jump, rb, depth, grid, stream);
+    if (depth)  // the depth-carrying kernels (depth_kernels.hip)
+        return kernel == 2 ? launch_rays_depth_fast(spp, tree, opt, rng, jump, rb, *depth, grid, stream)
+                           : launch_rays_depth_generic(spp, tree, opt, rng, rb, *depth, grid, stream);
+    return with_spp(spp, [&](auto SPP) {
+        if (kernel == 2)
+            with_lobes(tree, [&](auto LOBES) {
+                with_image(tree, [&](auto wide, auto stack) {
+                    hipLaunchKernelGGL((render_rays<SPP, wide, stack, LOBES>), grid, dim3(256), fast_lds_bytes(tree), stream, tree, opt, rng, jump, rb);
+                });
+            });
         else
-            launch_rays_fast<SPP, 0>(tree, opt, rng, jump, rb, depth, grid, stream);
-    } else if (depth) {
-        launch_rays_depth_generic<SPP>(tree, opt, rng, rb, *depth, grid, stream);  // (depth_kernels.hip)
-    } else {
-        hipLaunchKernelGGL(render_rays_generic<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                       const RayBatch& rb, const DepthOut* depth, bool xcd_order, hipStream_t stream) {
-    if (rb.n == 0) return hipSuccess;
-    if ((uint64_t)rb.n * (uint64_t)spp >= (uint64_t(1) << 32)) return hipErrorInvalidValue;  // (the RNG offset of a ray is 32-bit)
-    switch (spp) {
-#ifndef RTO_DEV_SPP6_ONLY
-        case 1: return launch_rays_spp<1>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 2: return launch_rays_spp<2>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 3: return launch_rays_spp<3>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 4: return launch_rays_spp<4>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 8: return launch_rays_spp<8>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 16: return launch_rays_spp<16>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        case 32: return launch_rays_spp<32>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-#endif
-        case 6: return launch_rays_spp<6>(kernel, tree, opt, rng, jump, rb, depth, xcd_order, stream);
-        default: return hipErrorInvalidValue;
-    }
+            hipLaunchKernelGGL(render_rays_generic<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_t* mask, int mask_words, hipStream_t stream) {
@@ -954,83 +868,49 @@ hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_
 hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
                          const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows,
                          const LayerDev* layers, const DepthOut* depth, hipStream_t stream) {
-    switch (spp) {  // volrend.cu:266-278
-#ifndef RTO_DEV_SPP6_ONLY
-        case 1: return launch_spp<1>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 2: return launch_spp<2>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 3: return launch_spp<3>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 4: return launch_spp<4>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 8: return launch_spp<8>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 16: return launch_spp<16>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        case 32: return launch_spp<32>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-#endif
-        case 6: return launch_spp<6>(kernel, tree, cam, opt, rng, jump, fo, strip_rows, layers, depth, stream);
-        default: return hipErrorInvalidValue;
+    if (depth) {  // the depth-carrying layered kernels (depth_kernels.hip), over the context's layers or none
+        const LayerDev ld = layers ? *layers : LayerDev{nullptr, nullptr};
+        return kernel == 2 ? launch_fast_depth(spp, tree, cam, opt, rng, jump, fo, strip_rows, ld, *depth, stream)
+                           : launch_generic_depth(spp, tree, cam, opt, rng, fo, ld, *depth, stream);
     }
+    return with_spp(spp, [&](auto SPP) {
+        const dim3 ggrid((unsigned)(((int64_t)cam.width * cam.height + 255) / 256));
+        if (kernel == 2)
+            with_lobes(tree, [&](auto LOBES) { launch_fast<SPP, LOBES>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream); });
+        else if (layers)
+            hipLaunchKernelGGL(render_generic_layers<SPP>, ggrid, dim3(256), 0, stream, tree, cam, opt, rng, fo, *layers);
+        else
+            hipLaunchKernelGGL(render_generic<SPP>, ggrid, dim3(256), 0, stream, tree, cam, opt, rng, fo);
+        return hipGetLastError();
+    });
 }
 
 // (RTO_WPS_DEFAULT, the waves per SIMD the default instantiation is built for: rto_render_shared.h)
-// the shading kernel of an SG / ASG tree (LOBES = kFmtSG / kFmtASG): the SH modes of the same record layouts
-template <int SPP, int SP, int LOBES>
-static void launch_shade_lobes(const dim3 sgrid, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb, const uint32_t* hits,
-                               hipStream_t stream) {
-#define RTO_SHADE_L(M) hipLaunchKernelGGL((shade_kernel<SPP, SP, M, LOBES>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, hits)
-    if (tree.data_dim == 28)
-        RTO_SHADE_L(28);
-    else if (tree.data_dim == 49)
-        RTO_SHADE_L(49);
-    else if (tree.data_dim == 76)
-        RTO_SHADE_L(76);
-    else
-        RTO_SHADE_L(0);
-#undef RTO_SHADE_L
-}
-
-// shade_kernel_layers for an expanded tree of any format (LOBES = 0: SH / RGBA; quantised-direct trees take no layers)
-template <int SPP, int SP, int LOBES>
-static void launch_shade_layers(const dim3 sgrid, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb, const uint32_t* hits,
-                                const LayerDev& layers, hipStream_t stream) {
-    const bool rec = LOBES != 0 || tree.format == 1;  // (the record modes: launch_batch_impl's / launch_shade_lobes' choice)
-#define RTO_SHADE_L(M) hipLaunchKernelGGL((shade_kernel_layers<SPP, SP, M, LOBES>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, hits, layers)
-    if (rec && tree.data_dim == 28)
-        RTO_SHADE_L(28);
-    else if (rec && tree.data_dim == 49)
-        RTO_SHADE_L(49);
-    else if (rec && tree.data_dim == 76)
-        RTO_SHADE_L(76);
-    else
-        RTO_SHADE_L(0);
-#undef RTO_SHADE_L
-}
-
 // LAYERS: the launch may carry layers (`layers` != nullptr: rto_ctx_set_layers) -- a depth layer takes render_persist_layers, a
 // colour layer shade_kernel_layers; instantiated for the default tuning only
 // depth != nullptr (LAYERS only; rto_ctx_enable_depth(RTO_DEPTH_BATCHED)): the traversal is render_persist_depth, over the layers or
 // none, through the launcher of depth_kernels.hip; its planes are filled with (0, +inf) on the stream first.  Marks, queues,
 // thresholds and shading are what they are without
-template <int SPP, int REFILL, int WPS, bool WIDE, bool LAYERS = false>
+// WIDE, STACK: the traversal image (with_image, chosen by launch_batch_spp)
+template <int SPP, int REFILL, int WPS, bool WIDE, int STACK, bool LAYERS = false>
 static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                     const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
                                     int chunk_override, bool cull, OccupancyCache* occ, hipEvent_t* ev, hipStream_t stream,
                                     const LayerDev* layers = nullptr, const DepthOut* depth = nullptr) {
     // dynamic LDS: ancestor stack + thresholds per lane, then the frame table of THIS batch (96 B per frame: a batch of
     // one does not pay for 128)
-    // (two pairs of levels below the grid at most: the ancestor stack is two registers and its LDS rows only park a ray's two
-    //  hand-off offsets)
-    const bool regstack = WIDE && (tree.max_depth - tree.top_levels + 1) / 2 <= 2;
+    constexpr bool regstack = STACK == 1;  // (the LDS rows of the register-stack form only park a ray's two hand-off offsets)
     bool with_depth = false;  // (two more rows, the ray's hit distances; without the register stack four: rto_render_persist.inc)
     if constexpr (LAYERS) with_depth = depth != nullptr;
     const size_t lds = (size_t)((regstack ? 2 : tree.max_depth + 1 - tree.top_levels) + SPP + 1 + (with_depth ? (regstack ? 2 : 4) : 0)) * 256 * sizeof(uint32_t) + sizeof(float) * kCamFloats * (size_t)fb.n;
-    const auto kern = regstack ? &render_persist<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0> : &render_persist<SPP, REFILL, WPS, WIDE, 0>;
-    const void* fn = reinterpret_cast<const void*>(kern);
+    // the traversal kernel of this launch: the key of the occupancy cache, of the occupancy query and of the LDS request below
+    const void* fn = reinterpret_cast<const void*>(&render_persist<SPP, REFILL, WPS, WIDE, STACK>);
     bool depth_layer = false, color_layer = false;
     if constexpr (LAYERS) {
         depth_layer = layers && layers->depth;
         color_layer = layers && layers->color;
-        if (depth_layer)
-            fn = regstack ? reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>)
-                          : reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, 0>);
-        if (with_depth) fn = persist_depth_kernel<SPP, WIDE>(regstack);  // (the occupancy query and the LDS request below are this kernel's)
+        if (depth_layer) fn = reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, STACK>);
+        if (with_depth) fn = persist_depth_kernel(SPP, tree);
     }
     OccupancyCache local;
     if (!occ) occ = &local;
@@ -1098,19 +978,15 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     if (ev) (void)hipEventRecord(ev[1], stream);
     if constexpr (LAYERS) {
         if (with_depth) {
-            launch_persist_depth<SPP, WIDE>(regstack, grid, lds, stream, tree, opt, fb, queue, hits, chunk,
-                                            layers ? *layers : LayerDev{nullptr, nullptr}, *depth);
-        } else if (depth_layer) {
-            const LayerDev ld = *layers;
-            if (regstack)
-                hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, WIDE ? 1 : 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb,
-                                   queue, hits, chunk, ld);
-            else
-                hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, 0>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
-                                   hits, chunk, ld);
-        }
+            if (launch_persist_depth(SPP, tree, grid, lds, stream, opt, fb, queue, hits, chunk, layers ? *layers : LayerDev{nullptr, nullptr},
+                                     *depth) != hipSuccess)
+                return hipErrorLaunchFailure;
+        } else if (depth_layer)
+            hipLaunchKernelGGL((render_persist_layers<SPP, REFILL, WPS, WIDE, STACK>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue,
+                               hits, chunk, *layers);
     }
-    if (!depth_layer && !with_depth) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
+    if (!depth_layer && !with_depth)
+        hipLaunchKernelGGL((render_persist<SPP, REFILL, WPS, WIDE, STACK>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
     if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
     if (ev) (void)hipEventRecord(ev[2], stream);
 #ifndef RTO_SHADE_P
@@ -1124,38 +1000,27 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
 #else
     const dim3 sgrid(((pblocks + 7u) / 8u) * 8u * (unsigned)fb.n);  // see shade_kernel: (pixel block, frame) <- block id
 #endif
-#define RTO_SHADE(M) hipLaunchKernelGGL((shade_kernel<SPP, SP, M>), sgrid, dim3(64 * kShadeWaves), 0, stream, tree, opt, fb, (const uint32_t*)hits)
-    if (color_layer) {  // (never a quantised-direct tree: the host refuses it layers)
-        if constexpr (LAYERS) {
-            if (tree.format == kFmtSG)
-                launch_shade_layers<SPP, SP, kFmtSG>(sgrid, tree, opt, fb, hits, *layers, stream);
-            else if (tree.format == kFmtASG)
-                launch_shade_layers<SPP, SP, kFmtASG>(sgrid, tree, opt, fb, hits, *layers, stream);
-            else
-                launch_shade_layers<SPP, SP, 0>(sgrid, tree, opt, fb, hits, *layers, stream);
-        }
-    } else if (tree.qrec) {  // (the host admits SH4/9/16/25 only)
+    const dim3 sblock(64 * kShadeWaves);
+    if (tree.qrec && !color_layer) {  // (the host admits SH4/9/16/25 only, and refuses a quantised-direct tree layers)
+        const auto quant = [&](auto mode) { hipLaunchKernelGGL((shade_kernel<SPP, SP, mode>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits); };
         if (tree.basis_dim == 4)
-            RTO_SHADE(-4);
+            quant(int_c<-4>{});
         else if (tree.basis_dim == 9)
-            RTO_SHADE(-9);
+            quant(int_c<-9>{});
         else if (tree.basis_dim == 16)
-            RTO_SHADE(-16);
+            quant(int_c<-16>{});
         else
-            RTO_SHADE(-25);
-    } else if (tree.format == kFmtSG) {
-        launch_shade_lobes<SPP, SP, kFmtSG>(sgrid, tree, opt, fb, hits, stream);
-    } else if (tree.format == kFmtASG) {
-        launch_shade_lobes<SPP, SP, kFmtASG>(sgrid, tree, opt, fb, hits, stream);
-    } else if (tree.format == 1 && tree.data_dim == 28)
-        RTO_SHADE(28);
-    else if (tree.format == 1 && tree.data_dim == 49)
-        RTO_SHADE(49);
-    else if (tree.format == 1 && tree.data_dim == 76)
-        RTO_SHADE(76);
-    else
-        RTO_SHADE(0);
-#undef RTO_SHADE
+            quant(int_c<-25>{});
+    } else {  // an expanded tree: the record modes for SH, SG and ASG trees, over the colour layer or not
+        with_lobes(tree, [&](auto lobes) {
+            with_record_mode(tree, lobes != 0 || tree.format == kFmtSH, [&](auto mode) {
+                if (!color_layer)
+                    hipLaunchKernelGGL((shade_kernel<SPP, SP, mode, lobes>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits);
+                else if constexpr (LAYERS)
+                    hipLaunchKernelGGL((shade_kernel_layers<SPP, SP, mode, lobes>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits, *layers);
+            });
+        });
+    }
     if (ev) (void)hipEventRecord(ev[3], stream);
     return hipGetLastError();
 }
@@ -1169,10 +1034,14 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     refill %= 100000;
     const int chunk_override = (refill / 1000) * 64;
     refill %= 1000;
-    const bool wide = tree.widew != nullptr;
     if constexpr (SPP == 6) {  // tuning instantiations only for the benchmark configuration (and its usual two-level image)
-#define RTO_F(R, O) return launch_batch_impl<SPP, R, O, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream)
-        if (wide && !layers && !depth) switch (refill) {  // (a layered launch: the default instantiation whatever the key's A/B part says)  // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
+#define RTO_F(R, O)                                                                                                                     \
+    return with_wide_image(tree, [&](auto wide, auto stack) {                                                                           \
+        return launch_batch_impl<SPP, R, O, wide, stack>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream); \
+    })
+        // A/B set kept for tools/ab_tuning.py: 100 * waves/SIMD + refill threshold
+        // (a layered launch: the default instantiation whatever the key's A/B part says)
+        if (tree.widew && !layers && !depth) switch (refill) {
             case 808: RTO_F(8, 8);
             case 816: RTO_F(16, 8);
             case 824: RTO_F(24, 8);
@@ -1194,39 +1063,23 @@ static hipError_t launch_batch_spp(const TreeDev& tree, const OptDev& opt, const
     // measured with the real knob, tuning key blocks_per_cu: 1 / 2 / 3 / 4 / 5 / 6 workgroups per CU take 26.2 / 14.4 /
     // 10.6 / 8.8 / 7.8 / 7.35 ms per 100 frames -- round 2's "4 to 8 waves within 2 %" compared __launch_bounds__ hints,
     // which change the register budget, not the number of resident waves).
-    // The two-level traversal image when the tree has one (always, unless it would not fit its index space or the device's
-    // memory: host/tree_layout.cpp build_wide_image), else the one-level image: the same pixels either way.
     // (Round 5's reservoir kernel -- whole-tile set-up, rays parked in LDS, refill rounds at 8-24 idle lanes -- lost its same-box
     //  A/B, 4.27-4.32 against 4.11-4.20 ms per 100 C2 frames, and lives in tools/experiments/r5_lab_switches.patch.)
-    if (layers || depth) {  // (depth outputs: the default instantiation too, render_persist_depth has no other)
-        if (wide)
-            return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers, depth);
-        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream, layers, depth);
-    }
-    if (wide)
-        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
-    return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, false>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
+    return with_image(tree, [&](auto wide, auto stack) {
+        if (layers || depth)  // (depth outputs: the default instantiation too, render_persist_depth has no other)
+            return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, wide, stack, true>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ,
+                                                                                  ev, stream, layers, depth);
+        return launch_batch_impl<SPP, 32, RTO_WPS_DEFAULT, wide, stack>(tree, opt, fb, jump, queue, hits, num_cus, chunk_override, cull, occ, ev, stream);
+    });
 }
 
 hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, const FrameBatch& fb,
                                const PcgJumpEntry* jump, unsigned long long* queue, uint32_t* hits, int num_cus,
                                int refill, bool cull, OccupancyCache* occ, hipEvent_t* ev, const LayerDev* layers, const DepthOut* depth,
                                hipStream_t stream) {
-    switch (spp) {
-#ifndef RTO_DEV_SPP6_ONLY  // (development builds: compile the benchmark's instantiation only)
-        case 1: return launch_batch_spp<1>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-        case 2: return launch_batch_spp<2>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-        case 3: return launch_batch_spp<3>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-        case 4: return launch_batch_spp<4>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-#endif
-        case 6: return launch_batch_spp<6>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-#ifndef RTO_DEV_SPP6_ONLY
-        case 8: return launch_batch_spp<8>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-        case 16: return launch_batch_spp<16>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-        case 32: return launch_batch_spp<32>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
-#endif
-        default: return hipErrorInvalidValue;
-    }
+    return with_spp(spp, [&](auto SPP) {
+        return launch_batch_spp<SPP>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
+    });
 }
 
 #ifdef RTO_DBG_COUNTERS

@@ -1,5 +1,5 @@
 // rto_depth_launch.h -- host launchers of the depth-carrying kernels, shared by render_kernels.hip (caller) and depth_kernels.hip
-// (definitions and explicit instantiations).
+// (definitions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,32 +7,26 @@
 
 namespace rto {
 
-// Launchers of the depth-carrying instantiations (render_rays_depth, render_rays_generic_depth,
-// render_fast_layers_depth, render_generic_layers_depth), defined and explicitly instantiated in depth_kernels.hip for every supported SPP (and
-// LOBES = 0, kFmtSG, kFmtASG); render_kernels.hip's launch_render / launch_rays call them when depth outputs are asked for.
-// The fast forms choose the traversal image as launch_fast does.
-template <int SPP, int LOBES>
-void launch_fast_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                       const FrameOut& fo, int strip_rows, const LayerDev& layers, const DepthOut& depth, hipStream_t stream);
-template <int SPP>
-void launch_generic_depth(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const FrameOut& fo,
-                          const LayerDev& layers, const DepthOut& depth, hipStream_t stream);
-template <int SPP, int LOBES>
-void launch_rays_depth_fast(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump, const RayBatch& rb,
-                            const DepthOut& depth, dim3 grid, hipStream_t stream);
-template <int SPP>
-void launch_rays_depth_generic(const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb, const DepthOut& depth,
-                               dim3 grid, hipStream_t stream);
+// Launchers of the depth-carrying instantiations (render_rays_depth, render_rays_generic_depth, render_fast_layers_depth,
+// render_generic_layers_depth); render_kernels.hip's launch_render / launch_rays call them when depth outputs are asked for.
+// Plain functions: spp, the tree's lobe form and its traversal image become template arguments inside depth_kernels.hip, by the rules
+// of rto_dispatch.h.  An spp outside {1,2,3,4,6,8,16,32} is hipErrorInvalidValue (nothing launched), else hipGetLastError().
+hipError_t launch_fast_depth(int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                             const FrameOut& fo, int strip_rows, const LayerDev& layers, const DepthOut& depth, hipStream_t stream);
+hipError_t launch_generic_depth(int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const FrameOut& fo,
+                                const LayerDev& layers, const DepthOut& depth, hipStream_t stream);
+hipError_t launch_rays_depth_fast(int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
+                                  const RayBatch& rb, const DepthOut& depth, dim3 grid, hipStream_t stream);
+hipError_t launch_rays_depth_generic(int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const RayBatch& rb,
+                                     const DepthOut& depth, dim3 grid, hipStream_t stream);
 
 // render_persist_depth<SPP, 32, RTO_WPS_DEFAULT, WIDE, STACK> (the batched traversal with depth outputs, default tuning only), for
-// launch_batch_impl: the kernel a launch takes -- regstack: STACK = 1, the two-level image's register-stack form -- as the identity
-// its OccupancyCache, occupancy query and dynamic-LDS request go by, and its launch.  lds: launch_batch_impl's size, which counts
-// the kernel's two more rows.  layers: both pointers null = offscreen.  depth: plane f = batch frame f, both pointers set.
-template <int SPP, bool WIDE>
-const void* persist_depth_kernel(bool regstack);
-template <int SPP, bool WIDE>
-void launch_persist_depth(bool regstack, int grid, size_t lds, hipStream_t stream, const TreeDev& tree, const OptDev& opt,
-                          const FrameBatch& fb, unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers,
-                          const DepthOut& depth);
+// launch_batch_impl: the kernel a launch on `tree` takes, as the identity its OccupancyCache, occupancy query and dynamic-LDS
+// request go by (nullptr for an unsupported spp), and its launch.  lds: launch_batch_impl's size, which counts the kernel's two
+// more rows.  layers: both pointers null = offscreen.  depth: plane f = batch frame f, both pointers set.
+const void* persist_depth_kernel(int spp, const TreeDev& tree);
+hipError_t launch_persist_depth(int spp, const TreeDev& tree, int grid, size_t lds, hipStream_t stream, const OptDev& opt,
+                                const FrameBatch& fb, unsigned long long* queue, uint32_t* hits, uint32_t chunk, const LayerDev& layers,
+                                const DepthOut& depth);
 
 }  // namespace rto

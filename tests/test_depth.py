@@ -191,7 +191,7 @@ def _fast_vs_generic(dt, o, d, spp, tuning=()):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,basis", [("RGBA", -1), ("SH", 9), ("SH", 16), ("SG", 16)])
+@pytest.mark.parametrize("kind,basis", [("RGBA", -1), ("SH", 9), ("SH", 16), ("SG", 16), ("ASG", 9)])
 @pytest.mark.parametrize("spp", [1, 6, 32])
 def test_fast_and_generic_kernels_agree_bit_for_bit(kind, basis, spp):
     _, _, o, d = D.scene()

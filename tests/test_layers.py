@@ -167,7 +167,7 @@ def _check_frame(aux, image, rgba, what):
 
 
 def _single(dt, ht, cam, spp, kernel, depth, color, ndc=None, **optkw):
-    """one layered single-frame launch checked against render_rays and the CPU oracle (ht = None: an SG tree, whose lobes the
+    """one layered single-frame launch checked against render_rays and the CPU oracle (ht = None: an SG / ASG tree, whose lobes the
     C oracle does not evaluate -- render_rays on it is pinned in test_rays.py / test_sg_asg.py); -> its (r, g, b, alpha)"""
     ctx = R.RenderContext(cam.width, cam.height)
     ctx.rng_seed()
@@ -187,12 +187,12 @@ def _single(dt, ht, cam, spp, kernel, depth, color, ndc=None, **optkw):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,basis", [("SH", 9), ("SH", 16), ("RGBA", -1), ("SG", 16)])
+@pytest.mark.parametrize("kind,basis", [("SH", 9), ("SH", 16), ("RGBA", -1), ("SG", 16), ("ASG", 16)])
 @pytest.mark.parametrize("spp", [1, 6, 32])
 @pytest.mark.parametrize("kernel", [R.KERNEL_FAST, R.KERNEL_GENERIC])
 def test_single_frame_equals_rays_and_oracle(kind, basis, spp, kernel):
     t = _tree(kind, basis)
-    ht = None if kind == "SG" else _host(t)
+    ht = None if kind in ("SG", "ASG") else _host(t)
     dt = _dev(t)
     cam = _cams(2)[1]
     depth, color = make_layers(t, _cams(2))
@@ -267,7 +267,7 @@ def _views(ctx, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,basis,spp", [("SH", 9, 6), ("SH", 16, 1), ("RGBA", -1, 6), ("SG", 16, 6), ("SH", 9, 32)])
+@pytest.mark.parametrize("kind,basis,spp", [("SH", 9, 6), ("SH", 16, 1), ("RGBA", -1, 6), ("SG", 16, 6), ("ASG", 9, 6), ("SH", 9, 32)])
 def test_batched_launch(kind, basis, spp):
     t = _tree(kind, basis)
     dt = _dev(t)
@@ -308,6 +308,57 @@ def test_batched_launch(kind, basis, spp):
             assert (aux[f][3, ty * 8:ty * 8 + 8, tx * 8:tx * 8 + 8] == 0).all()
             culled_backdrops += int(tile.min() != tile.max())
     assert culled_backdrops > 10
+
+
+@pytest.mark.gpu
+def test_layered_kernels_on_the_one_level_image_and_on_a_deep_tree():
+    """the traversal images the default small tree does not take (it walks the two-level image with the register stack): the
+    one-level image (WIDE = false) and a tree deep enough to keep its ancestor stack in LDS rows (STACK == 0) -- the layered
+    single-frame fast kernel and the layered batch (render_persist_layers, shade_kernel_layers) give the layered generic kernel's
+    frames, bit for bit"""
+    from helpers import cameras
+    from test_render_parity import _chain_tree
+
+    def check(t, dt, cams, tuning=()):
+        n, w, h = len(cams), cams[0].width, cams[0].height
+        depth, color = make_layers(t, cams)
+        opt = R.RenderOptions(spp=6, denoise=False)
+        jumps = [4, 1]
+        for with_color in (True, False):
+            layers = _dev_layers(depth, color if with_color else None)
+            bctx = R.RenderContext(w, h, frames=n)
+            one = R.RenderContext(w, h, frames=n)
+            for ctx in (bctx, one):
+                for k, v in tuning:
+                    ctx.set_tuning(k, v)
+                ctx.set_layers(*layers)
+            bctx.rng_seed()
+            R.launch_renderer_batch(dt, cams, opt, bctx, rng_jumps=jumps)
+            assert (bctx.tile_marks() is not None) == (not with_color)  # (depth only: the marks of the batched kernels)
+            for f in range(n):
+                outs = []
+                for kernel in (R.KERNEL_GENERIC, R.KERNEL_FAST):
+                    one.select_frame(f)
+                    one.rng_seed()
+                    one.rng_advance(jumps[f] << 32)
+                    one.set_kernel(kernel)
+                    R.launch_renderer(dt, cams[f], opt, one)
+                    outs.append((one.download_aux(), one.download_image()))
+                bctx.select_frame(f)
+                outs.append((bctx.download_aux(), bctx.download_image()))
+                for (aux, image), what in zip(outs[1:], ("fast", "batched")):
+                    assert_bits_equal(aux, outs[0][0], "%s vs generic, colour %d, frame %d: aux" % (what, with_color, f))
+                    assert_bits_equal(image, outs[0][1], "%s vs generic, colour %d, frame %d: image" % (what, with_color, f))
+                assert (outs[0][0][3] > 0).sum() >= 50, f
+
+    # (slot-ordered records: a tree whose records follow the two-level image's entries has no one-level fallback; 2^6 entries:
+    #  nothing fits, the launches take the WIDE = false instantiations)
+    t = _tree("SH", 9)
+    check(t, _dev(t, compact_records=True), _cams(2, 60, 44), tuning=(("wide_bits", 6),))
+    deep = _chain_tree(13, seed=13)  # four pairs of levels below the grid
+    dt = _dev(deep)
+    assert (dt.max_depth - 6 + 1) // 2 > 2 and dt.wide_nodes > 0
+    check(deep, dt, [cameras(56, 40, synth.look_at_c2w(eye, target=(0.0, -0.1, 0.05)))[1] for eye in ((2.2, 1.7, 1.9), (2.0, 1.9, 1.7))])
 
 
 @pytest.mark.gpu

@@ -273,6 +273,35 @@ def test_camera_equivalence_options_and_ndc(kernel):
     _camera_equivalence(ndc, cam, 6, kernel)
 
 
+@pytest.mark.gpu
+def test_fast_and_generic_kernels_agree_on_the_one_level_image_and_on_a_deep_tree():
+    """the traversal images the default small tree does not take (it walks the two-level image with the register stack): the
+    one-level image (WIDE = false) and a tree deep enough to keep its ancestor stack in LDS rows (STACK == 0) -- render_rays
+    returns the generic kernel's bits on both"""
+    from helpers import cameras
+    from test_render_parity import _chain_tree
+
+    def both(dt, cam, tuning=()):
+        o, d = R.camera_rays(cam)
+        bg = np.random.default_rng(2).uniform(0, 1, o.shape).astype(f32)
+        out = []
+        for kernel in (R.KERNEL_FAST, R.KERNEL_GENERIC):
+            ctx = R.RenderContext(8, 8)
+            ctx.rng_seed()
+            ctx.set_kernel(kernel)
+            for k, v in tuning:
+                ctx.set_tuning(k, v)
+            out.append(R.render_rays(dt, o, d, R.RenderOptions(spp=6), ctx, background=bg, first_ray=77).cpu().numpy())
+        assert_bits_equal(out[0], out[1], "render_rays, fast vs generic")
+        assert (out[0][:, 3] > 0).sum() >= 100
+    # (slot-ordered records: a tree whose records follow the two-level image's entries has no one-level fallback; 2^6 entries:
+    #  nothing fits, the launch takes the WIDE = false instantiation)
+    both(_dev(_tree("SH", 9), compact_records=True), _cam(64, 48), tuning=(("wide_bits", 6),))
+    deep = _dev(_chain_tree(13, seed=13))  # four pairs of levels below the grid
+    assert (deep.max_depth - 6 + 1) // 2 > 2 and deep.wide_nodes > 0
+    both(deep, cameras(56, 40, synth.look_at_c2w((2.2, 1.7, 1.9), target=(0.0, -0.1, 0.05)))[1])
+
+
 def _world(t, p):
     """tree-space points -> world space (cen = offset + scale * world)"""
     return ((p - t.offset[None, :]) / t.scale[None, :]).astype(f32)
