@@ -379,6 +379,110 @@ void rto_grid_params_default(rto_grid_params* p, const rto_options* o);
 int rto_draw_grid_layers(const rto_tree* tree, const rto_camera* cams /* host [n] */, int n, const rto_grid_params* p,
                          float* depth, float* color, void* stream);
 
+/* ---- meshes: triangles, lines and points as depth and colour layers ----
+ * The reference's mesh pass (Mesh::draw and its shaders, mesh.cpp:100-161, 366-397; cuda_renderer.cpp:96-111) without a
+ * rasteriser: a pixel is a ray, and the answer is the nearest primitive along it.  DESIGN.md section 7g has the float32 rule
+ * operation by operation, tests/mesh_ref.py restates it bit for bit.  In short, for the ray o + t d (d unit; t is the world
+ * distance, the measure of rto_rays.t_max and of the depth layer, the reference's Depth = length(FragPos.xyz)):
+ *   triangle: Moeller-Trumbore, two-sided (the reference culls no faces); hit when det != 0, u >= 0, v >= 0, u + v <= 1, t > 0.
+ *     Colour: the vertex colours interpolated with (1 - u - v, u, v); a lit mesh multiplies by ambient + diffuse + diffuse2 +
+ *     specular of the fragment shader with the interpolated, NOT renormalised, normal and pow(x, 32) as five squarings.
+ *     DEVIATION: viewDir = -d.  The shader subtracts a view-space position from a world-space camera position
+ *     (normalize(camPos - vec3(FragPos)), FragPos = MV * pos); here the view direction is the one from the hit point to the eye.
+ *     No clamp: the reference's colour surface is RGBA32F.
+ *   segment, point (a segment with a == b): the closest approach of the ray's line to the segment, the segment's parameter s
+ *     clamped to [0, 1]; tc = the ray parameter of the point nearest to it, dist = their distance; hit when tc > 0 and
+ *     dist <= spread * tc.  Depth tc, colour (1 - s) c0 + s c1, always unlit.  For a camera pixel spread = 0.5 * line_px / fx
+ *     (point_px for points): lines are cones of line_px pixels, as the grid's are.
+ *   nearest wins: the smallest depth, among equal depths the lowest primitive index (GL_LESS in draw order: mesh order, then
+ *     face order).  No hit: depth +inf, colour (background x 3, 1).
+ * A mesh set holds world-space primitives only: the model transform (Mesh::draw: rotation(axis-angle) * scale, then translation;
+ * |rotation| < 1e-3 is the identity) is applied on the host at creation, in double precision rounded to float once, and normals
+ * are stored as normalize(mat3(M) n).  An invisible mesh is simply not passed in.  One threaded BVH (host-built, deterministic)
+ * covers all primitives. */
+typedef struct rto_mesh_desc {
+    const float* vert;       /* host [n_verts][9]: position, rgb, normal -- the reference's VERT_SZ layout */
+    int64_t n_verts;
+    const uint32_t* faces;   /* host [n_faces][face_size], or NULL: consecutive vertices form the n_verts / face_size faces */
+    int64_t n_faces;
+    int face_size;           /* 3 triangles, 2 lines, 1 points */
+    int unlit;
+    int estimate_normals;    /* triangles only: overwrite the normals as mesh.cpp estimate_normals does */
+    float rotation[3];       /* axis-angle; |r| < 1e-3 = identity (Mesh::draw) */
+    float translation[3];
+    float scale;
+} rto_mesh_desc;
+typedef struct rto_meshes rto_meshes; /* opaque */
+typedef struct rto_meshes_info {
+    int64_t triangles, segments, points;
+    int64_t nodes;           /* of the BVH */
+    int64_t device_bytes;
+    float lo[3], hi[3];      /* world bounds of the positions (zeros for an empty set) */
+    int device;
+} rto_meshes_info;
+/* device >= 0: the set is uploaded to that GPU.  device < 0: a host-only set, for rto_meshes_trace_rays_host and the queries --
+ * no device is touched.  n == 0 or zero primitives give a valid, empty set.
+ * RTO_E_INVALID (before any device use): null meshes with n > 0 or null out, n < 0, face_size outside 1..3, negative counts, a
+ * face index >= n_verts, a non-finite position, rotation, translation or scale (or a position that overflows in world space),
+ * more than 2^30 primitives. */
+int rto_meshes_create(const rto_mesh_desc* meshes, int n, int device, rto_meshes** out);
+/* A set from files: an .obj (Mesh::load_basic_obj: `v x y z [r g b]`, `vn`, `f` with a, a/b, a/b/c, a//c and negative indices;
+ * polygons that are no triangles are dropped; colours and normals are taken only when there is one per vertex, else (1, 0.5, 0.2)
+ * and estimated normals; nothing else is parsed) or a drawlist .npz (Mesh::open_drawlist, mesh.cpp:770-938: entries `<name>` =
+ * type string, `<name>__<field>`; types cube, sphere (rings, sectors), line (a, b), lines (points, segs), points, camerafrustum
+ * (focal_length, image_width, image_height, z, r, t, connect), mesh (points, faces, face_size); common fields color, vert_color,
+ * scale, translation, rotation, visible, unlit, with the reference's defaults; meshes in the order of their names, invisible ones
+ * left out), chosen by the extension.  rto_meshes_load_files concatenates the meshes of n files in order.
+ * RTO_E_IO: a file that cannot be opened.  RTO_E_FORMAT, with a message: another extension, malformed or truncated content, an
+ * index out of range, a non-finite value. */
+int rto_meshes_load(const char* path, int device, rto_meshes** out);
+int rto_meshes_load_files(const char* const* paths, int n, int device, rto_meshes** out);
+int rto_meshes_get_info(const rto_meshes* m, rto_meshes_info* info);
+/* What the set holds, for tests and tools: prims = host [triangles + segments + points][32] floats or NULL, nodes = host
+ * [nodes][8] floats or NULL -- the records (in leaf order; word 29 is the primitive's index in draw order) and the BVH nodes
+ * in the layouts of csrc/rto_mesh_trace.h. */
+int rto_meshes_download(const rto_meshes* m, float* prims, float* nodes);
+void rto_meshes_free(rto_meshes* m);
+
+#define RTO_MESH_MERGE 1
+typedef struct rto_mesh_params {
+    float line_px, point_px; /* widths in pixels, > 0 */
+    float background;        /* rgb of a pixel without a hit */
+    int flags;               /* 0 or RTO_MESH_MERGE */
+} rto_mesh_params;
+/* line_px = point_px = 1, background = o->background_brightness, flags = 0 (o == NULL: the default options) */
+void rto_mesh_params_default(rto_mesh_params* p, const rto_options* o);
+/* The set drawn for n cameras of one size into depth (device [n][H][W] float32 or NULL) and color (device [n][H][W][4] float32,
+ * 16-byte aligned, or NULL), the inputs of rto_ctx_set_layers; the pixel's ray is the one of rto_launch_renderer.
+ * RTO_MESH_MERGE has exactly RTO_GRID_MERGE's semantics: a hit replaces depth and colour only where the existing depth is
+ * greater than its own; a pixel whose existing depth is <= 0 or NaN is left alone and not traced; nothing else is written; it
+ * needs `depth`.  The reference's draw order is rto_draw_mesh_layers, then rto_draw_grid_layers(... RTO_GRID_MERGE).
+ * The cameras travel to the kernel BY VALUE, 32 per launch: no allocation, no host synchronisation and no host-to-device copy
+ * per call; asynchronous on `stream`; n == 0 launches nothing; n calls of one frame give the bytes of one call of n frames.
+ * RTO_E_INVALID (checked before any device use; the buffers are untouched): a null set / cams / params, a host-only set, both
+ * outputs NULL, n < 0, line_px or point_px not finite or <= 0, a non-finite background, an unknown flag, RTO_MESH_MERGE without
+ * depth, color not 16-byte aligned, cameras of differing size, a camera whose width or height is <= 0 or whose fx / fy is zero
+ * or not finite. */
+int rto_draw_mesh_layers(const rto_meshes* m, const rto_camera* cams /* host [n] */, int n, const rto_mesh_params* p,
+                         float* depth, float* color, void* stream);
+/* n arbitrary rays against the set.  The direction is normalised as rto_launch_rays does; a degenerate ray (a direction that
+ * cannot be normalised, a non-finite origin) is a miss: (+inf, background).  A pixel of rto_draw_mesh_layers equals the ray
+ * camera_rays(cam)[y W + x] with line_spread = 0.5f * line_px / fx (point_spread likewise), bit for bit; t_hit can be passed
+ * to rto_launch_rays as t_max and rgb as background.  Splitting a batch gives the same bytes. */
+typedef struct rto_mesh_rays {
+    const float* origins;    /* [n][3] */
+    const float* dirs;       /* [n][3], any length */
+    int64_t n;
+    float line_spread, point_spread; /* >= 0: a line is hit within line_spread * (distance along the ray) of it */
+    float background;
+} rto_mesh_rays;
+/* device pointers; t_hit [n] or NULL, rgb [n][3] or NULL.  Asynchronous on `stream`.  RTO_E_INVALID (before any device use):
+ * null set / rays, a host-only set, both outputs NULL, n < 0, null origins / dirs with n > 0, a spread that is negative or not
+ * finite, a non-finite background. */
+int rto_meshes_trace_rays(const rto_meshes* m, const rto_mesh_rays* rays, float* t_hit, float* rgb, void* stream);
+/* The same on the CPU, with HOST pointers: the same code as the kernels' (csrc/rto_mesh_trace.h) compiled for the host. */
+int rto_meshes_trace_rays_host(const rto_meshes* m, const rto_mesh_rays* rays, float* t_hit, float* rgb);
+
 /* ---- the operator ---- */
 /* launch_renderer(tree, cam, options, ctx, stream, offscreen) (volrend.cu:236-285); offscreen = false is a context with
  * layers (rto_ctx_set_layers).  Asynchronous on `stream`.  Writes ctx aux + (options->denoise ? noisy : image).

@@ -10,10 +10,12 @@ from .volrend import (  # noqa: F401
     SUPPORTED_SPP, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST, FILTER_EXACT, FILTER_FAST, DEPTH_BATCHED,
     GridParams, draw_grid_layers, GRID_MERGE,
 )
+from .meshes import Mesh, MeshSet, MeshParams, draw_mesh_layers, trace_mesh_rays, MESH_MERGE  # noqa: F401
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
     "RenderOptions", "Timer", "launch_renderer", "launch_renderer_batch", "filtering", "render_rays", "camera_rays", "SUPPORTED_SPP",
     "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_FAST", "FILTER_EXACT", "FILTER_FAST", "DEPTH_BATCHED",
     "GridParams", "draw_grid_layers", "GRID_MERGE",
+    "Mesh", "MeshSet", "MeshParams", "draw_mesh_layers", "trace_mesh_rays", "MESH_MERGE",
 ]

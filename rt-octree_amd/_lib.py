@@ -58,6 +58,30 @@ class CGridParams(C.Structure):
                 ("flags", C.c_int)]
 
 
+class CMeshDesc(C.Structure):
+    """rto_mesh_desc (include/rto.h): host pointers"""
+    _fields_ = [("vert", C.c_void_p), ("n_verts", C.c_int64), ("faces", C.c_void_p), ("n_faces", C.c_int64),
+                ("face_size", C.c_int), ("unlit", C.c_int), ("estimate_normals", C.c_int), ("rotation", C.c_float * 3),
+                ("translation", C.c_float * 3), ("scale", C.c_float)]
+
+
+class CMeshesInfo(C.Structure):
+    """rto_meshes_info (include/rto.h)"""
+    _fields_ = [("triangles", C.c_int64), ("segments", C.c_int64), ("points", C.c_int64), ("nodes", C.c_int64),
+                ("device_bytes", C.c_int64), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("device", C.c_int)]
+
+
+class CMeshParams(C.Structure):
+    """rto_mesh_params (include/rto.h)"""
+    _fields_ = [("line_px", C.c_float), ("point_px", C.c_float), ("background", C.c_float), ("flags", C.c_int)]
+
+
+class CMeshRays(C.Structure):
+    """rto_mesh_rays (include/rto.h): device pointers (host pointers for rto_meshes_trace_rays_host)"""
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("n", C.c_int64), ("line_spread", C.c_float),
+                ("point_spread", C.c_float), ("background", C.c_float)]
+
+
 class CGuidanceLayer(C.Structure):
     """rto_guidance_layer (include/rto.h): host pointers to one convolution's fp32 weights [cout][cin][3][3] and bias"""
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("cin", C.c_int), ("cout", C.c_int)]
@@ -102,6 +126,16 @@ SYMBOLS = {
     "rto_tree_query": (C.c_int, [_P, _P, C.c_int64, C.POINTER(CQueryOut), _P]),
     "rto_grid_params_default": (None, [C.POINTER(CGridParams), C.POINTER(COptions)]),
     "rto_draw_grid_layers": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(CGridParams), _P, _P, _P]),
+    "rto_meshes_create": (C.c_int, [C.POINTER(CMeshDesc), C.c_int, C.c_int, C.POINTER(_P)]),
+    "rto_meshes_load": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(_P)]),
+    "rto_meshes_load_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(_P)]),
+    "rto_meshes_get_info": (C.c_int, [_P, C.POINTER(CMeshesInfo)]),
+    "rto_meshes_download": (C.c_int, [_P, _P, _P]),
+    "rto_meshes_free": (None, [_P]),
+    "rto_mesh_params_default": (None, [C.POINTER(CMeshParams), C.POINTER(COptions)]),
+    "rto_draw_mesh_layers": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(CMeshParams), _P, _P, _P]),
+    "rto_meshes_trace_rays": (C.c_int, [_P, C.POINTER(CMeshRays), _P, _P, _P]),
+    "rto_meshes_trace_rays_host": (C.c_int, [_P, C.POINTER(CMeshRays), _P, _P]),
     "rto_tree_probe_npz": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     "rto_tree_free": (None, [_P]),
     "rto_ctx_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),

@@ -27,6 +27,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <sstream>
 #include <thread>
 #include <vector>
 
@@ -77,7 +78,10 @@ Args parse(int argc, char** argv) {
             } else {
                 v = "true";
             }
-            a.kv[k] = v;
+            if (k == "draw" && a.kv.count(k))
+                a.kv[k] += "\n" + v;  // --draw may be repeated: the files are kept in order
+            else
+                a.kv[k] = v;
         } else if (s.size() >= 2 && s[0] == '-' && !(s[1] >= '0' && s[1] <= '9') && s[1] != '.') {
             const std::string sk = s.substr(1, 1);
             auto it = kShort.find(sk);
@@ -114,6 +118,9 @@ void usage() {
         "  --grid N           show the octree grid cut off at depth N: sets show_grid and grid_max_depth (also over --options); every\n"
         "                     launch's cameras get the grid drawn into a depth and a colour layer (rto_draw_grid_layers) and are\n"
         "                     rendered over them (rto_ctx_set_layers)\n"
+        "  --draw FILE        draw the meshes of an .obj or a drawlist .npz (may be repeated: the sets are concatenated in order) into\n"
+        "                     the depth and colour layers every launch is rendered over (rto_draw_mesh_layers); with --grid the grid\n"
+        "                     is depth-tested over them, the reference's draw order\n"
         "  --dataset blender|tt|llff (blender)\n"
         "  --ts_module ts.ts  TorchScript GuidanceNet (needed when denoise = true)\n"
         "  -o,--write_images DIR   write r_<i>.png (or buf_<name>.bin with --write_buffer)\n"
@@ -448,13 +455,36 @@ int main(int argc, char** argv) {
     rto_grid_params grid_params;
     rto_grid_params_default(&grid_params, &options);
     const bool grid_on = args.has("grid");
-    if (grid_on) {
+    // --draw: the meshes go into the same layers first; the grid is then depth-tested over them (RTO_GRID_MERGE)
+    rto_meshes* meshes = nullptr;
+    rto_mesh_params mesh_params;
+    rto_mesh_params_default(&mesh_params, &options);
+    if (args.has("draw")) {
+        if (dataset == "llff") {
+            std::fprintf(stderr, "ERROR: --draw: meshes are in world space, an NDC tree's depth measure differs\n");
+            return 1;
+        }
+        std::vector<std::string> files;
+        std::stringstream list(args.get("draw", ""));
+        for (std::string f; std::getline(list, f);) files.push_back(f);
+        std::vector<const char*> cfiles;
+        for (const std::string& f : files) cfiles.push_back(f.c_str());
+        CHECK_RTO(rto_meshes_load_files(cfiles.data(), (int)cfiles.size(), device, &meshes));
+        rto_meshes_info mi;
+        CHECK_RTO(rto_meshes_get_info(meshes, &mi));
+        std::printf("INFO: --draw: %lld triangles, %lld segments, %lld points, %lld BVH nodes\n", (long long)mi.triangles,
+                    (long long)mi.segments, (long long)mi.points, (long long)mi.nodes);
+        if (grid_on) grid_params.flags |= RTO_GRID_MERGE;
+    }
+    if (grid_on || meshes) {
         grid_depth = std::make_unique<rto::DeviceFloats>((size_t)batch * width * height, device);
         grid_color = std::make_unique<rto::DeviceFloats>((size_t)batch * width * height * 4, device);
         CHECK_RTO(rto_ctx_set_layers(ctx, grid_depth->data(), grid_color->data()));
     }
     auto draw_grid = [&](const rto_camera* cams_, int n) -> int {
-        return grid_on ? rto_draw_grid_layers(tree, cams_, n, &grid_params, grid_depth->data(), grid_color->data(), stream) : RTO_OK;
+        int rc = meshes ? rto_draw_mesh_layers(meshes, cams_, n, &mesh_params, grid_depth->data(), grid_color->data(), stream) : RTO_OK;
+        if (rc == RTO_OK && grid_on) rc = rto_draw_grid_layers(tree, cams_, n, &grid_params, grid_depth->data(), grid_color->data(), stream);
+        return rc;
     };
 
     // Denoiser::denoise (denoiser.cpp:31-61) for the n frames in context slots 0..n-1 (the selected slot must be 0 for
@@ -605,6 +635,7 @@ int main(int argc, char** argv) {
         if (args.has("rank_report")) std::printf("RANK_REPORT %.10f %.10f %.10f %zu\n", ms[0], ms[1], ms[2], rendered);
         denoiser.reset();
         rto_ctx_free(ctx);
+        rto_meshes_free(meshes);
         rto_tree_free(tree);
         return 0;
     }
@@ -656,6 +687,7 @@ int main(int argc, char** argv) {
 
     denoiser.reset();
     rto_ctx_free(ctx);
+    rto_meshes_free(meshes);
     rto_tree_free(tree);
     return 0;
 }

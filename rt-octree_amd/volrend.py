@@ -384,26 +384,53 @@ class RenderContext:
         check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
-    def show_grid(self, tree, cams, options, params=None, stream=None):
+    def _own_layers(self):
+        """the depth and colour tensors show_meshes and show_grid draw into, allocated once per context"""
+        import torch
+        keep = getattr(self, "_grid_layers", None)
+        if keep is None:
+            device = torch.device("cuda", self.device)
+            keep = (torch.empty((self.frames, self.height, self.width), dtype=torch.float32, device=device),
+                    torch.empty((self.frames, self.height, self.width, 4), dtype=torch.float32, device=device))
+            self._grid_layers = keep
+        return keep
+
+    def show_meshes(self, meshset, cams, options, params=None, stream=None, tree=None):
+        """The reference's mesh pass for this context: draws `meshset` (meshes.draw_mesh_layers; `params`: a MeshParams instead of
+        the defaults taken from `options`) for `cams` -- one Camera per frame slot -- into the depth and colour tensors the
+        context keeps alive (the ones show_grid uses) and binds them with set_layers.  For meshes AND the grid call show_meshes
+        first, then show_grid(..., merge=True): the reference's draw order.  `tree`: the tree the frames will be rendered from;
+        meshes live in world space, so an NDC tree is refused with RTO_E_UNSUPPORTED, as the grid refuses it.  Returns (depth,
+        color)."""
+        from .meshes import MeshParams, draw_mesh_layers
+        if isinstance(cams, Camera):
+            cams = [cams]
+        if len(cams) != self.frames:
+            raise RtoError(-1, "show_meshes: %d cameras for a context of %d frame slots" % (len(cams), self.frames))
+        if tree is not None and tree.use_ndc:
+            raise RtoError(-3, "show_meshes: meshes are in world space: over an NDC tree the depth measure differs")
+        keep = self._own_layers()
+        if params is None:
+            params = MeshParams(options)
+        draw_mesh_layers(meshset, cams, params, depth=keep[0], color=keep[1], stream=stream)
+        self.set_layers(keep[0], keep[1])
+        return keep
+
+    def show_grid(self, tree, cams, options, params=None, stream=None, merge=False):
         """RenderOptions.show_grid for this context: draws the octree grid of `tree` cut off at options.grid_max_depth
         (draw_grid_layers; `params`: a GridParams instead of the defaults taken from `options`) for `cams` -- one Camera per frame
         slot, or a single Camera for a single-slot context -- into a depth and a colour tensor the context keeps alive, and binds
         them with set_layers: the launches that follow render over the grid.  Returns (depth [frames, H, W], color [frames, H, W,
-        4]).  set_layers() with no arguments restores the offscreen behaviour."""
-        import torch
+        4]).  set_layers() with no arguments restores the offscreen behaviour.  merge=True (after show_meshes): the lines are depth-tested
+        against what the layers hold (RTO_GRID_MERGE) instead of replacing them."""
         if isinstance(cams, Camera):
             cams = [cams]
         if len(cams) != self.frames:
             raise RtoError(-1, "show_grid: %d cameras for a context of %d frame slots" % (len(cams), self.frames))
-        device = torch.device("cuda", self.device)
-        keep = getattr(self, "_grid_layers", None)
-        if keep is None:
-            keep = (torch.empty((self.frames, self.height, self.width), dtype=torch.float32, device=device),
-                    torch.empty((self.frames, self.height, self.width, 4), dtype=torch.float32, device=device))
-            self._grid_layers = keep
+        keep = self._own_layers()
         if params is None:
             params = GridParams(options)
-        draw_grid_layers(tree, cams, params, depth=keep[0], color=keep[1], stream=stream)
+        draw_grid_layers(tree, cams, params, depth=keep[0], color=keep[1], merge=merge, stream=stream)
         self.set_layers(keep[0], keep[1])
         return keep
 
