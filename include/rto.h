@@ -769,6 +769,50 @@ int rto_denoise(rto_guidance_net* net, rto_ctx* ctx, int n, int mode, void* stre
 int rto_denoise_launch_strips(int n, int H, int W, int* filter_strip, int* net_strip);
 void rto_guidance_net_free(rto_guidance_net* net);
 
+/* ---- image metrics (denoiser/metrics.py:7-9, 61-79; denoiser/runner.py:126-160) ----
+ * Per frame, of a predicted against a true image, [n][H][W][4] each, r, g, b only:
+ *   mse   = mean of (p - t)^2 over the 3 H W values;  psnr = -10 log10(mse), +inf when mse is 0
+ *   smape = mean of |p - t| / (|p| + |t| + 1e-5)
+ *   ssim  = pytorch_msssim.ssim(X, Y, data_range = 1): 11-tap Gaussian window (sigma 1.5, normalised), separable, no padding --
+ *           the map is (H - 10) x (W - 10); per channel mu = G(x), var = G(x^2) - mu^2, cov = G(xy) - mu_x mu_y, C1 = 1e-4,
+ *           C2 = 9e-4, map = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) * (2 cov + C2) / (var_x + var_y + C2); the mean of the
+ *           map over positions and channels.  NaN when H < 11 or W < 11 (the other three are still computed).
+ * All arithmetic after the input conversion is float64 on the device, compiled without FMA contraction: identical inputs give
+ * ssim == 1.0, mse == 0 and smape == 0 exactly.  Sums are taken in a fixed order without atomics: a frame's result depends on
+ * neither n, its position in the batch nor the run.  A non-finite r, g or b makes that frame's four values NaN and leaves
+ * the other frames untouched.
+ * Formats, each side on its own: RTO_IMAGE_RGBA32F (the context's image layout; 16-byte aligned) or RTO_IMAGE_RGBA8 (value / 255.0f
+ * in float32; 4-byte aligned).  RTO_METRICS_TRUTH_OVER_BACKGROUND: the true image's rgb becomes rgb * a + background * (1 - a),
+ * in float32 with separate multiplies and adds (denoiser/dataset.py:82-84, where the background is 1), before the promotion
+ * to double.
+ * RTO_E_INVALID, decided before anything is enqueued: a null argument; n, H or W < 1; an unknown format or unknown flag bits; a
+ * non-finite background with the flag set; pred, truth or device_out misaligned or not memory of the handle's device; n H W >
+ * 2^31 - 1.  The handle owns the partial-sum scratch ([frame][workgroup][4] doubles) and, for rto_metrics_compute, the device
+ * results; both grow on demand, and growing synchronises the device once (as rto_guidance_net_reserve's scratch does): call once
+ * at the largest extent before a timed or captured region.  One handle serves one stream at a time. */
+#define RTO_IMAGE_RGBA32F 0
+#define RTO_IMAGE_RGBA8 1
+#define RTO_METRICS_TRUTH_OVER_BACKGROUND 1
+typedef struct {
+    double mse, psnr, smape, ssim;
+} rto_frame_metrics;
+typedef struct rto_metrics rto_metrics;
+int rto_metrics_create(int device, rto_metrics** out);
+void rto_metrics_free(rto_metrics* m);
+/* asynchronous on `stream`; device_out: device memory [n][4] doubles = mse, psnr, smape, ssim */
+int rto_metrics_compute_async(rto_metrics* m, void* stream, const void* pred, int pred_format, const void* truth, int truth_format,
+                              int n, int H, int W, int flags, float background, double* device_out);
+/* the same, results copied to host_out[n]; synchronises `stream` before it returns */
+int rto_metrics_compute(rto_metrics* m, void* stream, const void* pred, int pred_format, const void* truth, int truth_format, int n,
+                        int H, int W, int flags, float background, rto_frame_metrics* host_out);
+/* Host only, no device: an 8-bit RGB or RGBA, non-interlaced PNG -> RGBA8 [height][width][4] (alpha 255 for RGB).  rgba == NULL
+ * or cap < width * height * 4: sizes only (signature and IHDR are validated), returns RTO_OK with *width / *height set.
+ * The signature, every chunk's length against the file size and every chunk's CRC are checked.  RTO_E_INVALID: a null path /
+ * width / height.  RTO_E_IO, with a message that names the file: a file that cannot be opened, and everything this reader does
+ * not take -- 16-bit, palette, grey or interlaced images, a truncated file, inflated data shorter or longer than the image, a
+ * bad CRC, a filter type above 4. */
+int rto_image_read_png(const char* path, int* width, int* height, uint8_t* rgba, size_t cap);
+
 /* ---- profiling aid ---- */
 /* Counter calibration (MI355X_MICROARCH.md "HBM"): launches `repeats` kernels in which every lane
  * loads one dword from its own never-repeated 128-byte line of a zero-filled n_lines*128-byte buffer

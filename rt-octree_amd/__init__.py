@@ -11,6 +11,7 @@ from .volrend import (  # noqa: F401
     GridParams, draw_grid_layers, GRID_MERGE,
 )
 from .meshes import Mesh, MeshSet, MeshParams, draw_mesh_layers, trace_mesh_rays, MESH_MERGE  # noqa: F401
+from .metrics import FrameMetrics, ImageMetrics, read_png  # noqa: F401
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
@@ -18,4 +19,5 @@ __all__ = [
     "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_FAST", "FILTER_EXACT", "FILTER_FAST", "DEPTH_BATCHED",
     "GridParams", "draw_grid_layers", "GRID_MERGE",
     "Mesh", "MeshSet", "MeshParams", "draw_mesh_layers", "trace_mesh_rays", "MESH_MERGE",
+    "FrameMetrics", "ImageMetrics", "read_png",
 ]

@@ -202,6 +202,11 @@ SYMBOLS = {
     "rto_ctx_selected_frame": (C.c_int, [_P]),
     "rto_guidance_net_reserve": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "rto_guidance_net_free": (None, [_P]),
+    "rto_metrics_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_metrics_free": (None, [_P]),
+    "rto_metrics_compute_async": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "rto_metrics_compute": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "rto_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
     "rto_probe_gather": (C.c_int, [C.c_uint64, C.c_int]),
     "rto_probe_gather_sweep": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_double)]),

@@ -176,5 +176,14 @@ DeviceFloats::DeviceFloats(size_t n, int device) : impl_(new Impl) {
 }
 DeviceFloats::~DeviceFloats() = default;
 float* DeviceFloats::data() const { return impl_->t.data_ptr<float>(); }
+// (copied as int32 words: bit patterns, whatever they spell as floats)
+void DeviceFloats::upload(const void* host, size_t bytes, size_t offset_bytes) {
+    const torch::Tensor src = torch::from_blob(const_cast<void*>(host), {(int64_t)(bytes / 4)}, torch::TensorOptions().dtype(torch::kInt32));
+    impl_->t.view(torch::kInt32).narrow(0, (int64_t)(offset_bytes / 4), (int64_t)(bytes / 4)).copy_(src);
+}
+void DeviceFloats::download(void* host, size_t bytes, size_t offset_bytes) const {
+    torch::Tensor dst = torch::from_blob(host, {(int64_t)(bytes / 4)}, torch::TensorOptions().dtype(torch::kInt32));
+    dst.copy_(impl_->t.view(torch::kInt32).narrow(0, (int64_t)(offset_bytes / 4), (int64_t)(bytes / 4)));
+}
 
 }  // namespace rto

@@ -44,6 +44,11 @@ public:
     DeviceFloats(size_t n, int device);
     ~DeviceFloats();
     float* data() const;
+    // raw bytes in and out (a multiple of 4, starting `offset_bytes` into the buffer), in order behind the work already issued on
+    // libtorch's current stream; both return when the copy is done.  --gt_dir: the ground-truth RGBA8 images go up through the
+    // first, the metric results ([n][4] doubles) come down through the second
+    void upload(const void* host, size_t bytes, size_t offset_bytes = 0);
+    void download(void* host, size_t bytes, size_t offset_bytes = 0) const;
 
 private:
     struct Impl;

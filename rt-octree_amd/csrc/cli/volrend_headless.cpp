@@ -12,7 +12,9 @@
 //     denoises them as one batch; images are identical to B = 1 (one launch per frame, the reference's loop), the report is still per frame;
 //   * extra flags `--shard i/N` (render poses i, i+N, ...: frame sharding across GPUs, one process
 //     per GPU), `--gpus N` (this process touches no GPU: it starts N copies of itself, `--shard i/N` on GPU i each,
-//     and prints the report of their union) and `--warmup K` (default 100 like the reference).
+//     and prints the report of their union) and `--warmup K` (default 100 like the reference);
+//   * `--gt_dir DIR` scores every rendered pose against its ground-truth PNG as the reference's test loop does
+//     (denoiser/runner.py:126-160): psnr / ssim / smape after the timing lines, per pose in <-o DIR>/metrics.json.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -34,6 +36,7 @@
 #include "denoiser_torch.h"
 #include "imwrite.h"
 #include "poses.h"
+#include "rank_metrics.h"
 #include "rto.h"
 
 namespace fs = std::filesystem;
@@ -142,6 +145,11 @@ void usage() {
         "                     dense SH9 / SH16 tree, same pixels, slower shading)\n"
         "  --no_denoise_cull  with --fast_filter and a batch: run GuidanceNet and the filter on every tile, also those that see\n"
         "                     only background (default: such tiles are filled with the kernels' background output; same pixels)\n"
+        "  --gt_dir DIR       score every rendered pose against its ground-truth PNG (8-bit RGB / RGBA, the frame's size): blender\n"
+        "                     DIR/<basename of the frame's file_path>.png, tt / llff the i-th *.png of DIR in byte-wise sorted order.\n"
+        "                     The true image is composited over the background brightness and compared with the float image -o\n"
+        "                     would write (rto_metrics_compute_async); after the timing lines the report gains psnr:, ssim: and\n"
+        "                     smape:, each the mean over frames; with -o DIR also DIR/metrics.json with the per-pose values\n"
         "  --print_poses      parse the poses, print them (column-major 4x3) and exit\n");
 }
 
@@ -149,7 +157,7 @@ void usage() {
 // processes render poses i, i + N, ... each on its own GPU.  This parent never touches a GPU: it starts the
 // children (posix_spawn of this very executable: nothing is exec'ed from a process that initialised HIP), relays their
 // output and merges their timing reports.  A child that fails makes the whole run fail.
-int run_multi_gpu(int argc, char** argv, int gpus) {
+int run_multi_gpu(int argc, char** argv, int gpus, const std::string& out_dir) {
     char self[4096];
     const ssize_t sl = readlink("/proc/self/exe", self, sizeof(self) - 1);
     if (sl <= 0) {
@@ -237,6 +245,8 @@ int run_multi_gpu(int argc, char** argv, int gpus) {
     bool ok = true;
     double sum_ms[3] = {0, 0, 0}, sum_fps = 0;
     long frames = 0;
+    rto::MetricSums metric_sums;  // --gt_dir: the ranks' RANK_METRICS sums, their RANK_FRAME_METRICS rows
+    std::vector<rto::FrameRow> metric_rows;
     for (int r = 0; r < gpus; ++r) {
         const Child& k = kids[(size_t)r];
         if (!WIFEXITED(k.status) || WEXITSTATUS(k.status) != 0) {
@@ -257,6 +267,10 @@ int run_multi_gpu(int argc, char** argv, int gpus) {
                 sum_ms[2] += c * n;
                 frames += n;
                 if (a + b + c > 0) sum_fps += 1000.0 / (a + b + c);
+            } else if (rto::MetricSums ms; rto::parse_rank_metrics(line, &ms)) {
+                metric_sums.merge(ms);
+            } else if (rto::FrameRow row; rto::parse_frame_metrics(line, &row)) {
+                metric_rows.push_back(row);
             } else if (!line.empty()) {
                 std::printf("[rank %d] %s\n", r, line.c_str());
             }
@@ -271,6 +285,13 @@ int run_multi_gpu(int argc, char** argv, int gpus) {
         std::printf("all:    %.10f ms per frame\n", m0 + m1 + m2);
         std::printf("FPS:    %.10f\n", sum_fps);
         std::printf("INFO: %ld frames on %d GPUs; FPS = the sum of the ranks' 1000 / (render + torch + filter)\n", frames, gpus);
+    }
+    if (metric_sums.frames > 0) {
+        std::fputs(rto::format_metric_means(metric_sums).c_str(), stdout);
+        if (!out_dir.empty() && !rto::write_metrics_json(out_dir + "/metrics.json", metric_rows)) {
+            std::fprintf(stderr, "ERROR: cannot write %s/metrics.json\n", out_dir.c_str());
+            return 1;
+        }
     }
     return 0;
 }
@@ -309,7 +330,7 @@ int main(int argc, char** argv) {
                 std::fputs("ERROR: --gpus N starts the shards itself; give one of --gpus and --shard\n", stderr);
                 return 1;
             }
-            return run_multi_gpu(argc, argv, gpus);  // before anything that could touch a GPU
+            return run_multi_gpu(argc, argv, gpus, args.get("write_images", ""));  // before anything that could touch a GPU
         }
     }
     const std::string tree_path = args.positional[0], poses_path = args.positional[1];
@@ -416,6 +437,48 @@ int main(int argc, char** argv) {
         options.grid_max_depth = std::atoi(args.get("grid", "4").c_str());
     }
 
+    // --gt_dir: every ground truth of this process's poses is read and checked against the frame size here, before any launch
+    const std::string gt_dir = args.get("gt_dir", "");
+    std::vector<size_t> gt_pose;                 // the poses this process renders, in order
+    std::vector<std::vector<uint8_t>> gt_rgba8;  // their ground truths, [H][W][4]
+    if (!gt_dir.empty()) {
+        std::vector<std::string> sorted_pngs;  // tt / llff: the i-th *.png of the directory, byte-wise sorted
+        if (dataset != "blender") {
+            std::error_code ec;
+            for (fs::directory_iterator it(gt_dir, ec), end; !ec && it != end; it.increment(ec))
+                if (it->path().extension() == ".png") sorted_pngs.push_back(it->path().filename().string());
+            if (ec) {
+                std::fprintf(stderr, "ERROR: --gt_dir: cannot list %s: %s\n", gt_dir.c_str(), ec.message().c_str());
+                return 1;
+            }
+            std::sort(sorted_pngs.begin(), sorted_pngs.end());
+        }
+        for (size_t i = 0; i < ps.trans.size(); ++i) {
+            if ((int)(i % shard_n) != shard_i) continue;
+            if (dataset != "blender" && i >= sorted_pngs.size()) {
+                std::fprintf(stderr, "ERROR: --gt_dir: %s holds %zu *.png files, pose %zu has none\n", gt_dir.c_str(), sorted_pngs.size(), i);
+                return 1;
+            }
+            const std::string file = gt_dir + "/" + (dataset == "blender" ? ps.basenames[i] + ".png" : sorted_pngs[i]);
+            int gw = 0, gh = 0;
+            if (rto_image_read_png(file.c_str(), &gw, &gh, nullptr, 0) != RTO_OK) {
+                std::fprintf(stderr, "ERROR: --gt_dir: %s\n", rto_last_error());
+                return 1;
+            }
+            if (gw != width || gh != height) {
+                std::fprintf(stderr, "ERROR: --gt_dir: %s is %d x %d, the frames are %d x %d\n", file.c_str(), gw, gh, width, height);
+                return 1;
+            }
+            std::vector<uint8_t> px((size_t)width * height * 4);
+            if (rto_image_read_png(file.c_str(), &gw, &gh, px.data(), px.size()) != RTO_OK) {
+                std::fprintf(stderr, "ERROR: --gt_dir: %s\n", rto_last_error());
+                return 1;
+            }
+            gt_pose.push_back(i);
+            gt_rgba8.push_back(std::move(px));
+        }
+    }
+
     int batch = std::max(1, std::min(128, std::atoi(args.get("batch", "100").c_str())));
     const int filter_mode = args.has("fast_filter") ? RTO_FILTER_FACTORISED : RTO_FILTER_EXACT;
     {  // no more frame slots than this process has poses to render
@@ -431,6 +494,16 @@ int main(int argc, char** argv) {
     // (depth outputs: batches through the persistent kernels; the per-frame loop's launches are the same in either mode)
     if (write_depth) CHECK_RTO(rto_ctx_enable_depth(ctx, RTO_DEPTH_BATCHED));
     std::printf("INFO: %d poses per launch\n", batch);
+    // --gt_dir: the ground truths of one launch's frames as RGBA8 on the device (one float of the buffer per pixel), the results of
+    // all frames ([frames][4] doubles, downloaded once at the end); the metric kernels run outside the three timer buckets
+    rto_metrics* metrics = nullptr;
+    std::unique_ptr<rto::DeviceFloats> gt_dev, metric_dev;
+    size_t scored = 0;
+    if (!gt_pose.empty()) {
+        CHECK_RTO(rto_metrics_create(device, &metrics));
+        gt_dev = std::make_unique<rto::DeviceFloats>((size_t)batch * width * height, device);
+        metric_dev = std::make_unique<rto::DeviceFloats>(gt_pose.size() * 8, device);
+    }
 
     std::unique_ptr<rto::TorchDenoiser> denoiser;
     if (options.denoise) {
@@ -524,6 +597,46 @@ int main(int argc, char** argv) {
     };
     auto denoise = [&]() -> int { return denoise_n(1, true); };
 
+    // --gt_dir: scores the n frames in slots 0..n-1 -- the float image -o would write -- against the ground truths of the next n
+    // poses, composited over the run's background (runner.py:140-145, dataset.py:82-84).  Asynchronous but for the upload.
+    auto score_n = [&](int n) -> int {
+        if (!metrics) return RTO_OK;
+        const size_t frame_bytes = (size_t)width * height * 4;
+        for (int f = 0; f < n; ++f) gt_dev->upload(gt_rgba8[scored + (size_t)f].data(), frame_bytes, (size_t)f * frame_bytes);
+        rto_ctx_select_frame(ctx, 0);
+        const int rc = rto_metrics_compute_async(metrics, stream, rto_ctx_image(ctx), RTO_IMAGE_RGBA32F, gt_dev->data(), RTO_IMAGE_RGBA8, n, height,
+                                                 width, RTO_METRICS_TRUTH_OVER_BACKGROUND, options.background_brightness,
+                                                 reinterpret_cast<double*>(metric_dev->data()) + scored * 4);
+        scored += (size_t)n;
+        return rc;
+    };
+    // after the timing lines: the means over frames (Metric.result, metrics.py:50-58); -o DIR: DIR/metrics.json.  A rank of
+    // --gpus N hands its sums and rows to the parent instead, which prints the means and writes the file for the union
+    auto report_metrics = [&]() -> int {
+        if (!metrics) return 0;
+        std::vector<double> v(scored * 4);
+        if (scored) metric_dev->download(v.data(), v.size() * sizeof(double));
+        rto::MetricSums sums;
+        std::vector<rto::FrameRow> rows(scored);
+        for (size_t k = 0; k < scored; ++k) {
+            rows[k].pose = (long)gt_pose[k];
+            rows[k].name = ps.basenames[gt_pose[k]];
+            rows[k].mse = v[4 * k], rows[k].psnr = v[4 * k + 1], rows[k].smape = v[4 * k + 2], rows[k].ssim = v[4 * k + 3];
+            sums.add(rows[k].psnr, rows[k].ssim, rows[k].smape);
+        }
+        std::fputs(rto::format_metric_means(sums).c_str(), stdout);
+        if (args.has("rank_report")) {
+            std::printf("%s\n", rto::format_rank_metrics(sums).c_str());
+            for (const rto::FrameRow& r : rows) std::printf("%s\n", rto::format_frame_metrics(r).c_str());
+        } else if (!out_dir.empty() && !rto::write_metrics_json(out_dir + "/metrics.json", rows)) {
+            std::fprintf(stderr, "ERROR: cannot write %s/metrics.json\n", out_dir.c_str());
+            return 1;
+        }
+        rto_metrics_free(metrics);
+        metrics = nullptr;
+        return 0;
+    };
+
     // Warm up (main_headless.cpp:469-479): pose 0, every iteration advances the RNG
     rto_timer_reset(ctx, stream);
     const int warmup = std::atoi(args.get("warmup", "100").c_str());
@@ -593,6 +706,7 @@ int main(int argc, char** argv) {
             rto_timer_stop(ctx, RTO_T_RENDER);
             if (options.denoise) CHECK_RTO(denoise_n(n, true, true));
             CHECK_RTO(rto_timer_record(ctx, options.denoise));
+            CHECK_RTO(score_n(n));
             rendered += (size_t)n;
             if (out_dir.empty()) continue;
             for (int f = 0; f < n; ++f) {
@@ -633,6 +747,7 @@ int main(int argc, char** argv) {
         std::printf("all:    %.10f ms per frame\n", all);
         std::printf("FPS:    %.10f\n", all > 0 ? 1000.f / all : 0.f);
         if (args.has("rank_report")) std::printf("RANK_REPORT %.10f %.10f %.10f %zu\n", ms[0], ms[1], ms[2], rendered);
+        if (report_metrics() != 0) return 1;
         denoiser.reset();
         rto_ctx_free(ctx);
         rto_meshes_free(meshes);
@@ -649,6 +764,7 @@ int main(int argc, char** argv) {
             rto_timer_stop(ctx, RTO_T_RENDER);
             if (options.denoise) CHECK_RTO(denoise());
             CHECK_RTO(rto_timer_record(ctx, options.denoise));
+            CHECK_RTO(score_n(1));
         }
         rto_ctx_rng_advance(ctx, 1LL << 32);  // skipped poses advance too: images do not depend on N
         if ((int)(i % shard_n) != shard_i || out_dir.empty()) continue;
@@ -684,6 +800,7 @@ int main(int argc, char** argv) {
     std::printf("all:    %.10f ms per frame\n", ms[0] + ms[1] + ms[2]);
     std::printf("FPS:    %.10f\n", fps);
     if (args.has("rank_report")) std::printf("RANK_REPORT %.10f %.10f %.10f %d\n", ms[0], ms[1], ms[2], frames);
+    if (report_metrics() != 0) return 1;
 
     denoiser.reset();
     rto_ctx_free(ctx);

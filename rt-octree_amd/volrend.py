@@ -552,7 +552,23 @@ class RenderContext:
         check(lib().rto_ctx_download_rgba8(self._h, _stream_ptr(stream), int(noisy), C.c_void_p(out.ctypes.data)))
         return out
 
+    def metrics(self, truth, n=1, noisy=False, over_background=None, stream=None):
+        """MSE, PSNR, SMAPE and SSIM (metrics.ImageMetrics) of the image -- or the noisy image -- of the n frame slots from the
+        selected one against `truth`, a device tensor [n,H,W,4] (or [H,W,4]), float32 or uint8, read in place.  Returns a list
+        of n FrameMetrics; synchronises `stream`."""
+        from .metrics import ImageMetrics
+        sel = lib().rto_ctx_selected_frame(self._h)
+        if n < 1 or sel + n > self.frames:
+            raise RtoError(-1, "metrics: %d frames from slot %d of a context of %d" % (n, sel, self.frames))
+        if getattr(self, "_metrics", None) is None:
+            self._metrics = ImageMetrics(self.device)
+        pred = _DevArray(self.noisy_ptr if noisy else self.image_ptr, (n, self.height, self.width, 4), self)
+        return self._metrics.compute(pred, truth, over_background=over_background, stream=stream)
+
     def freeResource(self):
+        if getattr(self, "_metrics", None) is not None:
+            self._metrics.free()
+            self._metrics = None
         if getattr(self, "_h", None):
             lib().rto_ctx_free(self._h)
             self._h = C.c_void_p(0)

@@ -106,18 +106,21 @@ def main():
     # per-pixel gradients of a mean over 2 M values underflow in the fp16 backward (runner.py:79 scales too)
     scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 16)
 
+    image_metrics = R.ImageMetrics(0)  # SSIM (pytorch_msssim's definition) on the device, float64
+
     def evaluate(tag):
         model.eval()
         with torch.no_grad():
-            raw, den = [], []
+            raw, den, ssim = [], [], []
             for i in test_idx:
                 aux, noisy, tgt = data[i]
                 out = denoiser.filtering(model, aux[:1], noisy[:1])
                 raw.append(psnr(noisy[0, ..., :3], tgt[..., :3]))
                 den.append(psnr(out[0, ..., :3], tgt[..., :3]))
+                ssim.append([image_metrics.compute(x[:1].float().contiguous(), tgt[None].contiguous())[0].ssim for x in (noisy, out)])
         model.train()
-        print("%s: held-out PSNR raw %.2f dB -> denoised %.2f dB  (pose 0: %.2f -> %.2f)"
-              % (tag, np.mean(raw), np.mean(den), raw[0], den[0]), flush=True)
+        print("%s: held-out PSNR raw %.2f dB -> denoised %.2f dB  (pose 0: %.2f -> %.2f)  SSIM raw %.4f -> denoised %.4f"
+              % (tag, np.mean(raw), np.mean(den), raw[0], den[0], np.mean([s[0] for s in ssim]), np.mean([s[1] for s in ssim])), flush=True)
         return np.mean(den)
 
     evaluate("before training")
