@@ -282,3 +282,16 @@ def check(rc):
     if rc != RTO_OK:
         raise RtoError(rc, lib().rto_last_error().decode("utf-8", "replace"))
     return rc
+
+
+class LayerParams:
+    """GridParams / MeshParams: C struct CSTRUCT as DEFAULT(options) sets it, then keywords; a subclass has _load(c), to_c(merge)"""
+    def __init__(self, options=None, **kw):
+        c = self.CSTRUCT()
+        co = options.to_c() if options is not None else None
+        getattr(lib(), self.DEFAULT)(C.byref(c), C.byref(co) if co is not None else None)
+        self._load(c)
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError("%s has no field '%s'" % (self.CSTRUCT.__name__[1:], k))
+            setattr(self, k, v)

@@ -51,18 +51,12 @@ RTO_DEV float grid_edge_test(const float* p, float tau, int a, float cs, const f
     return best;
 }
 
-// blockIdx.z = frame of this launch (cams.c[z], plane z of gd.depth / gd.color); a workgroup = 16x16 pixels, wave w its 8x8 tile
-// (w & 1, w >> 1), lane l pixel (l & 7, l >> 3) of the tile
-__global__ void __launch_bounds__(256) grid_layers_kernel(const TreeDev tree, const int walk, const GridDraw gd, const GridCams cams) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= gd.width || y >= gd.height) return;
-    const int64_t idx = ((int64_t)blockIdx.z * gd.height + y) * gd.width + x;
-    float old = 0.f;
-    if (gd.merge) {  // the GL depth test against what the buffers hold; a depth <= 0 or NaN (not traced) is left alone
-        old = gd.depth[idx];
-        if (!(old > 0.f)) return;
-    }
+// a layer pass (rto_layer_pass.h): the pixel frame around the walk of this pixel's ray
+__global__ void __launch_bounds__(256) grid_layers_kernel(const TreeDev tree, const int walk, const GridDraw gd, const LayerCams cams) {
+    int x, y;
+    int64_t idx;
+    float old;
+    if (!layer_pixel_begin(gd.target, x, y, idx, old)) return;
     const CamDev& cam = cams.c[blockIdx.z];
     float dir[3], dw[3], cen[3];
     ray_setup(x, y, cam, tree, dir, dw, cen);  // (no NDC tree gets here: dw = dir = the unit world direction)
@@ -135,23 +129,14 @@ __global__ void __launch_bounds__(256) grid_layers_kernel(const TreeDev tree, co
         axp = axo;
     }
     const bool line = best < __builtin_inff();
-    if (gd.merge) {
-        if (!(line && old > best)) return;
-    }
-    if (gd.depth) gd.depth[idx] = best;
-    if (gd.color) {
-        const float bg = gd.background;
-        gd.color[idx] = line ? make_float4(gd.color_rgb[0], gd.color_rgb[1], gd.color_rgb[2], 1.f) : make_float4(bg, bg, bg, 1.f);
-    }
+    const float bg = gd.background;
+    layer_pixel_end(gd.target, idx, old, best, line ? gd.color_rgb[0] : bg, line ? gd.color_rgb[1] : bg, line ? gd.color_rgb[2] : bg);
 }
 
-hipError_t launch_grid_layers(const TreeDev& tree, int walk, const GridDraw& gd, const GridCams& cams, int frames, hipStream_t stream) {
-    if (frames <= 0 || gd.width <= 0 || gd.height <= 0) return hipSuccess;
-    if (frames > kGridCamChunk) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((gd.width + 15) / 16), (unsigned)((gd.height + 15) / 16), (unsigned)frames);
-    if (grid.y > 65535u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(grid_layers_kernel, grid, dim3(256), 0, stream, tree, walk, gd, cams);
-    return hipGetLastError();
+hipError_t launch_grid_layers(const TreeDev& tree, int walk, const GridDraw& gd, const LayerCams& cams, int frames, hipStream_t stream) {
+    return launch_layer_pass(gd.target, frames, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(grid_layers_kernel, grid, block, 0, stream, tree, walk, gd, cams);
+    });
 }
 
 }  // namespace rto

@@ -16,20 +16,22 @@
 
 namespace rto {
 
-// blockIdx.z = frame of this launch (cams.c[z], plane z of md.depth / md.color); a workgroup = 16x16 pixels, wave w its 8x8 tile
-// (w & 1, w >> 1), lane l pixel (l & 7, l >> 3) of the tile
-__global__ void __launch_bounds__(256) mesh_layers_kernel(const MeshSetDev ms, const MeshDraw md, const MeshCams cams) {
+// A layer pass (rto_layer_pass.h: launch shape, LayerTarget, LayerCams) that keeps the text of the pixel frame and of ray_setup's
+// pixel ray (volrend.cu:23-34) written out: built from layer_pixel_begin / layer_pixel_end, and from a ray helper shared with the
+// render kernels, it ran 1.3 % (sphere, batched) to 2.6 % (frusta, lone frame) slower, each half about half of that
+// (profiles/layer_pass_ab.txt).  wave w = the 8x8 tile (w & 1, w >> 1) of the 16x16 workgroup, lane l its pixel (l & 7, l >> 3)
+__global__ void __launch_bounds__(256) mesh_layers_kernel(const MeshSetDev ms, const MeshDraw md, const LayerCams cams) {
+    const LayerTarget& lt = md.target;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (x >= md.width || y >= md.height) return;
-    const int64_t idx = ((int64_t)blockIdx.z * md.height + y) * md.width + x;
+    if (x >= lt.width || y >= lt.height) return;
+    const int64_t idx = ((int64_t)blockIdx.z * lt.height + y) * lt.width + x;
     float old = 0.f;
-    if (md.merge) {  // the GL depth test against what the buffers hold; a depth <= 0 or NaN (not traced) is left alone
-        old = md.depth[idx];
+    if (lt.merge) {  // the GL depth test against what the buffers hold; a depth <= 0 or NaN (not traced) is left alone
+        old = lt.depth[idx];
         if (!(old > 0.f)) return;
     }
     const CamDev& cam = cams.c[blockIdx.z];
-    // ray_setup of the render kernels (volrend.cu:23-34): o = the camera centre, d = normalize3(M xyz)
     const float xyz[3] = {(x - 0.5f * cam.width) / cam.fx, -(y - 0.5f * cam.height) / cam.fy, -1.0f};
     const float* m = cam.transform;
     float d[3];
@@ -43,11 +45,11 @@ __global__ void __launch_bounds__(256) mesh_layers_kernel(const MeshSetDev ms, c
     const float o[3] = {m[9], m[10], m[11]};
     float rgb[3];
     const float t = mesh_trace_shade(ms, o, d, (0.5f * md.line_px) / cam.fx, (0.5f * md.point_px) / cam.fx, md.background, rgb);
-    if (md.merge) {
+    if (lt.merge) {
         if (!(old > t)) return;  // (a miss is +inf: never nearer)
     }
-    if (md.depth) md.depth[idx] = t;
-    if (md.color) md.color[idx] = make_float4(rgb[0], rgb[1], rgb[2], 1.f);
+    if (lt.depth) lt.depth[idx] = t;
+    if (lt.color) lt.color[idx] = make_float4(rgb[0], rgb[1], rgb[2], 1.f);
 }
 
 // one thread per ray
@@ -71,13 +73,10 @@ __global__ void __launch_bounds__(256) mesh_rays_kernel(const MeshSetDev ms, con
     }
 }
 
-hipError_t launch_mesh_layers(const MeshSetDev& ms, const MeshDraw& md, const MeshCams& cams, int frames, hipStream_t stream) {
-    if (frames <= 0 || md.width <= 0 || md.height <= 0) return hipSuccess;
-    if (frames > kMeshCamChunk) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((md.width + 15) / 16), (unsigned)((md.height + 15) / 16), (unsigned)frames);
-    if (grid.y > 65535u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mesh_layers_kernel, grid, dim3(256), 0, stream, ms, md, cams);
-    return hipGetLastError();
+hipError_t launch_mesh_layers(const MeshSetDev& ms, const MeshDraw& md, const LayerCams& cams, int frames, hipStream_t stream) {
+    return launch_layer_pass(md.target, frames, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(mesh_layers_kernel, grid, block, 0, stream, ms, md, cams);
+    });
 }
 
 hipError_t launch_mesh_rays(const MeshSetDev& ms, const MeshRays& mr, hipStream_t stream) {

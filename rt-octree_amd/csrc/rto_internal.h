@@ -3,7 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -181,6 +184,61 @@ inline rto::PcgJumpEntry pcg_jump(uint64_t inc, uint64_t delta) {
 }
 
 rto::OptDev make_opt_dev(const rto_options* o);  // (rto_abi.cpp) RenderOptions -> the fields the kernels read
+
+inline rto::CamDev cam_dev(const rto_camera& cam) {
+    rto::CamDev cd;
+    cd.width = cam.width;
+    cd.height = cam.height;
+    cd.fx = cam.fx;
+    cd.fy = cam.fy;
+    std::memcpy(cd.transform, cam.transform, sizeof(cd.transform));
+    return cd;
+}
+
+// ---- the host half of a layer pass (rto_layer_pass.h): rto_draw_grid_layers, rto_draw_mesh_layers ----
+// The argument checks of every pass, in one order; none reads `handle`, whose own checks follow in the caller (then n == 0).
+// fn: the message prefix; merge_name: the pass's merge flag (bit 0 of p->flags, the only one); own() -> nullptr or a message.
+template <class Params, class Own>
+int check_layer_call(const char* fn, const char* handle_noun, const char* merge_name, const void* handle, const rto_camera* cams, int n,
+                     const Params* p, const float* depth, const float* color, Own own) {
+    const std::string at = std::string(fn) + ": ";
+    if (!handle || !cams || !p) return set_err(RTO_E_INVALID, at + "null " + handle_noun + ", cams or params");
+    if (!depth && !color) return set_err(RTO_E_INVALID, at + "depth and color are both null");
+    if (n < 0) return set_err(RTO_E_INVALID, at + "n must be >= 0");
+    if (const char* msg = own()) return set_err(RTO_E_INVALID, at + msg);
+    if (p->flags & ~1) return set_err(RTO_E_INVALID, at + "unknown flag");
+    if ((p->flags & 1) && !depth) return set_err(RTO_E_INVALID, at + merge_name + " tests against the depth buffer, which is null");
+    if ((uintptr_t)color % 16 != 0) return set_err(RTO_E_INVALID, at + "color must be 16-byte aligned");
+    for (int f = 0; f < n; ++f) {
+        const rto_camera& c = cams[f];
+        if (c.width != cams[0].width || c.height != cams[0].height)
+            return set_err(RTO_E_INVALID, at + "the cameras of one call share width and height");
+        if (c.width <= 0 || c.height <= 0 || c.height > 65535 * 16 || !std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.f || c.fy == 0.f)
+            return set_err(RTO_E_INVALID, at + "a camera's width, height (<= 1048560), fx or fy is out of range");
+    }
+    return RTO_OK;
+}
+
+// The launches of a checked call (n > 0): launch(target, cams, k) -> hipError_t for each chunk of k <= kLayerCamChunk cameras
+// (the unused slots hold the chunk's first) and the planes of its first frame.  what: "grid" / "mesh", for the error message.
+template <class Launch>
+int launch_layer_chunks(const char* what, const rto_camera* cams, int n, int flags, float* depth, float* color, Launch launch) {
+    rto::LayerTarget lt;
+    lt.width = cams[0].width;
+    lt.height = cams[0].height;
+    lt.merge = flags & 1;
+    const size_t px = (size_t)lt.width * lt.height;
+    for (int f0 = 0; f0 < n; f0 += rto::kLayerCamChunk) {
+        const int k = std::min(rto::kLayerCamChunk, n - f0);
+        rto::LayerCams lc;
+        for (int f = 0; f < rto::kLayerCamChunk; ++f) lc.c[f] = cam_dev(cams[f0 + (f < k ? f : 0)]);
+        lt.depth = depth ? depth + (size_t)f0 * px : nullptr;
+        lt.color = color ? reinterpret_cast<float4*>(color) + (size_t)f0 * px : nullptr;
+        const hipError_t e = launch(lt, lc, k);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string(what) + " launch failed: " + hipGetErrorString(e));
+    }
+    return RTO_OK;
+}
 
 // ---- rto_tree.cpp ----
 // How the fast / batched kernels render `tree` at this SPP: 0 = not at all (generic kernel), 1 = with tree->dev as it is,

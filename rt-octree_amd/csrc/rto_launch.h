@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rto_kernel_types.h"
+#include "rto_layer_pass.h"
 
 namespace rto {
 
@@ -121,25 +122,16 @@ struct ProbeDraw {
 };
 hipError_t launch_probe_overlay(const TreeDev& tree, const OptDev& opt, ProbeDraw pd, int frames, const float* coeffs, hipStream_t stream);
 
-// ---- grid_kernels.hip: rto_draw_grid_layers ----
-// The cameras of one launch travel BY VALUE in the kernel arguments (64 B each; a kernarg segment holds 4 KB): no table in
-// device memory, so no copy and nothing for the tree handle to own.  A call of more frames is split into launches of kGridCamChunk.
-constexpr int kGridCamChunk = 32;
-struct GridCams {
-    CamDev c[kGridCamChunk];
-};
+// ---- grid_kernels.hip: rto_draw_grid_layers, a layer pass (rto_layer_pass.h) ----
 struct GridDraw {
-    int width, height;   // of every camera of the launch
-    int max_depth;       // cells: the leaves cut off at level max_depth + 1 (<= 22)
-    int merge;           // RTO_GRID_MERGE: depth-test against what depth holds (depth != nullptr then)
+    LayerTarget target;
+    int max_depth;  // cells: the leaves cut off at level max_depth + 1 (<= 22)
     float line_px;
     float color_rgb[3];
     float background;
-    float* depth;        // [frames][H][W] or nullptr, offset to the launch's first frame
-    float4* color;       // [frames][H][W] or nullptr
 };
-// frames <= kGridCamChunk; walk: as launch_query's (kWalkChild needs tree.child)
-hipError_t launch_grid_layers(const TreeDev& tree, int walk, const GridDraw& gd, const GridCams& cams, int frames, hipStream_t stream);
+// frames <= kLayerCamChunk; walk: as launch_query's (kWalkChild needs tree.child)
+hipError_t launch_grid_layers(const TreeDev& tree, int walk, const GridDraw& gd, const LayerCams& cams, int frames, hipStream_t stream);
 
 #ifdef RTO_DBG_COUNTERS
 hipError_t debug_shade_phases(unsigned long long* out16, bool reset);  // tools/dbg_shade_phases.py

@@ -180,54 +180,27 @@ void rto_mesh_params_default(rto_mesh_params* p, const rto_options* o) {
 
 int rto_draw_mesh_layers(const rto_meshes* m, const rto_camera* cams, int n, const rto_mesh_params* p, float* depth, float* color,
                          void* stream_) {
-    if (!m || !cams || !p) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: null set, cams or params");
-    if (!depth && !color) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: depth and color are both null");
-    if (n < 0) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: n must be >= 0");
-    if (!(std::isfinite(p->line_px) && p->line_px > 0.f && std::isfinite(p->point_px) && p->point_px > 0.f))
-        return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: line_px and point_px must be finite and > 0");
-    if (!std::isfinite(p->background)) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: the background must be finite");
-    if (p->flags & ~RTO_MESH_MERGE) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: unknown flag");
-    if ((p->flags & RTO_MESH_MERGE) && !depth)
-        return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: RTO_MESH_MERGE tests against the depth buffer, which is null");
-    if ((uintptr_t)color % 16 != 0) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: color must be 16-byte aligned");
-    for (int f = 0; f < n; ++f) {
-        const rto_camera& c = cams[f];
-        if (c.width != cams[0].width || c.height != cams[0].height)
-            return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: the cameras of one call share width and height");
-        if (c.width <= 0 || c.height <= 0 || c.height > 65535 * 16 || !std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.f || c.fy == 0.f)
-            return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: a camera's width, height (<= 1048560), fx or fy is out of range");
-    }
+    static_assert(RTO_MESH_MERGE == 1, "check_layer_call takes bit 0 of the flags for the merge flag");
+    const int rc = check_layer_call("rto_draw_mesh_layers", "set", "RTO_MESH_MERGE", m, cams, n, p, depth, color, [&]() -> const char* {
+        if (!(std::isfinite(p->line_px) && p->line_px > 0.f && std::isfinite(p->point_px) && p->point_px > 0.f))
+            return "line_px and point_px must be finite and > 0";
+        if (!std::isfinite(p->background)) return "the background must be finite";
+        return nullptr;
+    });
+    if (rc != RTO_OK) return rc;
     if (m->device < 0) return set_err(RTO_E_INVALID, "rto_draw_mesh_layers: a host-only set (device < 0) cannot be drawn on a GPU");
     if (n == 0) return RTO_OK;
     DeviceGuard guard(m->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     const rto::MeshSetDev ms = dev_view(m);
     rto::MeshDraw md;
-    md.width = cams[0].width;
-    md.height = cams[0].height;
-    md.merge = (p->flags & RTO_MESH_MERGE) ? 1 : 0;
     md.line_px = p->line_px;
     md.point_px = p->point_px;
     md.background = p->background;
-    const size_t px = (size_t)md.width * md.height;
-    for (int f0 = 0; f0 < n; f0 += rto::kMeshCamChunk) {
-        const int k = std::min(rto::kMeshCamChunk, n - f0);
-        rto::MeshCams mc;
-        for (int f = 0; f < k; ++f) {
-            const rto_camera& c = cams[f0 + f];
-            mc.c[f].width = c.width;
-            mc.c[f].height = c.height;
-            mc.c[f].fx = c.fx;
-            mc.c[f].fy = c.fy;
-            std::memcpy(mc.c[f].transform, c.transform, sizeof(c.transform));
-        }
-        for (int f = k; f < rto::kMeshCamChunk; ++f) mc.c[f] = mc.c[0];
-        md.depth = depth ? depth + (size_t)f0 * px : nullptr;
-        md.color = color ? reinterpret_cast<float4*>(color) + (size_t)f0 * px : nullptr;
-        const hipError_t e = rto::launch_mesh_layers(ms, md, mc, k, (hipStream_t)stream_);
-        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("mesh launch failed: ") + hipGetErrorString(e));
-    }
-    return RTO_OK;
+    return launch_layer_chunks("mesh", cams, n, p->flags, depth, color, [&](const rto::LayerTarget& lt, const rto::LayerCams& lc, int k) {
+        md.target = lt;
+        return rto::launch_mesh_layers(ms, md, lc, k, (hipStream_t)stream_);
+    });
 }
 
 static int check_rays(const char* fn, const rto_meshes* m, const rto_mesh_rays* r, const float* t_hit, const float* rgb) {

@@ -2,26 +2,19 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "rto_kernel_types.h"
+#include "rto_layer_pass.h"
 #include "rto_mesh_trace.h"
 
 namespace rto {
 
-// As the grid's: the cameras of one launch travel BY VALUE in the kernel arguments, 32 per launch.
-constexpr int kMeshCamChunk = 32;
-struct MeshCams {
-    CamDev c[kMeshCamChunk];
-};
+// rto_draw_mesh_layers, a layer pass (rto_layer_pass.h)
 struct MeshDraw {
-    int width, height;  // of every camera of the launch
-    int merge;          // RTO_MESH_MERGE: depth-test against what depth holds (depth != nullptr then)
+    LayerTarget target;
     float line_px, point_px;
     float background;
-    float* depth;   // [frames][H][W] or nullptr, offset to the launch's first frame
-    float4* color;  // [frames][H][W] or nullptr
 };
-// frames <= kMeshCamChunk
-hipError_t launch_mesh_layers(const MeshSetDev& ms, const MeshDraw& md, const MeshCams& cams, int frames, hipStream_t stream);
+// frames <= kLayerCamChunk
+hipError_t launch_mesh_layers(const MeshSetDev& ms, const MeshDraw& md, const LayerCams& cams, int frames, hipStream_t stream);
 
 struct MeshRays {
     const float* origins;  // [n][3]

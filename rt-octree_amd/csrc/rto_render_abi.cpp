@@ -127,16 +127,6 @@ int choose_kernel(const rto_tree* tree, const rto_options* o, const rto_ctx* ctx
     return RTO_OK;
 }
 
-rto::CamDev cam_dev(const rto_camera& cam) {
-    rto::CamDev cd;
-    cd.width = cam.width;
-    cd.height = cam.height;
-    cd.fx = cam.fx;
-    cd.fy = cam.fy;
-    std::memcpy(cd.transform, cam.transform, sizeof(cd.transform));
-    return cd;
-}
-
 // ctx.rng advanced by delta draws: frame f of a batch starts at (its jump count) << 32, as after that many ctx.rng.advance()
 // of the reference's frame loop (main_headless.cpp:494-506); a ray at (its index) * spp
 rto::Pcg32 rng_after(const rto_ctx* ctx, uint64_t delta) {

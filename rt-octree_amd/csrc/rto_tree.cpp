@@ -671,24 +671,15 @@ void rto_grid_params_default(rto_grid_params* p, const rto_options* o) {
 
 int rto_draw_grid_layers(const rto_tree* tree, const rto_camera* cams, int n, const rto_grid_params* p, float* depth, float* color,
                          void* stream_) {
-    if (!tree || !cams || !p) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: null tree, cams or params");
-    if (!depth && !color) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: depth and color are both null");
-    if (n < 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: n must be >= 0");
-    if (!(std::isfinite(p->line_px) && p->line_px > 0.f)) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: line_px must be finite and > 0");
-    if (p->max_depth < 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: max_depth must be >= 0");
-    if (!(std::isfinite(p->color[0]) && std::isfinite(p->color[1]) && std::isfinite(p->color[2]) && std::isfinite(p->background)))
-        return set_err(RTO_E_INVALID, "rto_draw_grid_layers: the line colour and the background must be finite");
-    if (p->flags & ~RTO_GRID_MERGE) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: unknown flag");
-    if ((p->flags & RTO_GRID_MERGE) && !depth)
-        return set_err(RTO_E_INVALID, "rto_draw_grid_layers: RTO_GRID_MERGE tests against the depth buffer, which is null");
-    if ((uintptr_t)color % 16 != 0) return set_err(RTO_E_INVALID, "rto_draw_grid_layers: color must be 16-byte aligned");
-    for (int f = 0; f < n; ++f) {
-        const rto_camera& c = cams[f];
-        if (c.width != cams[0].width || c.height != cams[0].height)
-            return set_err(RTO_E_INVALID, "rto_draw_grid_layers: the cameras of one call share width and height");
-        if (c.width <= 0 || c.height <= 0 || c.height > 65535 * 16 || !std::isfinite(c.fx) || !std::isfinite(c.fy) || c.fx == 0.f || c.fy == 0.f)
-            return set_err(RTO_E_INVALID, "rto_draw_grid_layers: a camera's width, height (<= 1048560), fx or fy is out of range");
-    }
+    static_assert(RTO_GRID_MERGE == 1, "check_layer_call takes bit 0 of the flags for the merge flag");
+    const int rc = check_layer_call("rto_draw_grid_layers", "tree", "RTO_GRID_MERGE", tree, cams, n, p, depth, color, [&]() -> const char* {
+        if (!(std::isfinite(p->line_px) && p->line_px > 0.f)) return "line_px must be finite and > 0";
+        if (p->max_depth < 0) return "max_depth must be >= 0";
+        if (!(std::isfinite(p->color[0]) && std::isfinite(p->color[1]) && std::isfinite(p->color[2]) && std::isfinite(p->background)))
+            return "the line colour and the background must be finite";
+        return nullptr;
+    });
+    if (rc != RTO_OK) return rc;
     if (tree->dev.ndc_width > 0)
         return set_err(RTO_E_UNSUPPORTED, "rto_draw_grid_layers: the line width is defined in unwarped space: NDC trees are not drawn");
     if (tree->dev.N != 2) return set_err(RTO_E_UNSUPPORTED, "rto_draw_grid_layers: N != 2");
@@ -701,32 +692,14 @@ int rto_draw_grid_layers(const rto_tree* tree, const rto_camera* cams, int n, co
     DeviceGuard guard(tree->device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     rto::GridDraw gd;
-    gd.width = cams[0].width;
-    gd.height = cams[0].height;
     gd.max_depth = std::min(p->max_depth, 22);
-    gd.merge = (p->flags & RTO_GRID_MERGE) ? 1 : 0;
     gd.line_px = p->line_px;
     for (int i = 0; i < 3; ++i) gd.color_rgb[i] = p->color[i];
     gd.background = p->background;
-    const size_t px = (size_t)gd.width * gd.height;
-    for (int f0 = 0; f0 < n; f0 += rto::kGridCamChunk) {
-        const int m = std::min(rto::kGridCamChunk, n - f0);
-        rto::GridCams gc;
-        for (int f = 0; f < m; ++f) {
-            const rto_camera& c = cams[f0 + f];
-            gc.c[f].width = c.width;
-            gc.c[f].height = c.height;
-            gc.c[f].fx = c.fx;
-            gc.c[f].fy = c.fy;
-            std::memcpy(gc.c[f].transform, c.transform, sizeof(c.transform));
-        }
-        for (int f = m; f < rto::kGridCamChunk; ++f) gc.c[f] = gc.c[0];
-        gd.depth = depth ? depth + (size_t)f0 * px : nullptr;
-        gd.color = color ? reinterpret_cast<float4*>(color) + (size_t)f0 * px : nullptr;
-        const hipError_t e = rto::launch_grid_layers(tree->dev, walk, gd, gc, m, (hipStream_t)stream_);
-        if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("grid launch failed: ") + hipGetErrorString(e));
-    }
-    return RTO_OK;
+    return launch_layer_chunks("grid", cams, n, p->flags, depth, color, [&](const rto::LayerTarget& lt, const rto::LayerCams& lc, int k) {
+        gd.target = lt;
+        return rto::launch_grid_layers(tree->dev, walk, gd, lc, k, (hipStream_t)stream_);
+    });
 }
 
 // Host-only check of the two-level traversal image (no device needed): builds it for child[] (breadth-first node order) and

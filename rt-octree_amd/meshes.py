@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CCamera, CMeshDesc, CMeshesInfo, CMeshParams, CMeshRays, RtoError, check, lib
+from ._lib import CMeshDesc, CMeshesInfo, CMeshParams, CMeshRays, LayerParams, RtoError, check, lib
 
 MESH_MERGE = 1  # RTO_MESH_MERGE (draw_mesh_layers(merge=True))
 DEFAULT_COLOR = (1.0, 0.5, 0.2)
@@ -333,18 +333,12 @@ class MeshSet:
             pass
 
 
-class MeshParams:
+class MeshParams(LayerParams):
     """rto_mesh_params: line_px, point_px, background.  MeshParams(options) takes background = options.background_brightness."""
+    CSTRUCT, DEFAULT = CMeshParams, "rto_mesh_params_default"
 
-    def __init__(self, options=None, **kw):
-        c = CMeshParams()
-        co = options.to_c() if options is not None else None
-        lib().rto_mesh_params_default(C.byref(c), C.byref(co) if co is not None else None)
+    def _load(self, c):
         self.line_px, self.point_px, self.background = c.line_px, c.point_px, c.background
-        for k, v in kw.items():
-            if not hasattr(self, k):
-                raise AttributeError("MeshParams has no field '%s'" % k)
-            setattr(self, k, v)
 
     def to_c(self, merge=False):
         c = CMeshParams()
@@ -358,39 +352,9 @@ def draw_mesh_layers(meshset, cams, params=None, depth=None, color=None, merge=F
     contiguous float32 torch tensors on the set's device -- allocated here when not given; depth=False / color=False for an output
     that is not wanted.  merge=True (RTO_MESH_MERGE): depth-test against what the given tensors hold.  Returns (depth, color),
     the inputs of RenderContext.set_layers.  Asynchronous on `stream` (default: torch's current stream); no sync."""
-    import torch
-    from .volrend import Camera, _stream_ptr
-    device = torch.device("cuda", meshset.device)
-    if isinstance(cams, Camera):
-        cams = [cams]
-    n = len(cams)
-    if params is None:
-        params = MeshParams()
-    H, W = (cams[0].height, cams[0].width) if n else (0, 0)
-    if merge and (depth is None or depth is False):
-        raise RtoError(-1, "draw_mesh_layers: merge=True tests against a depth tensor of the caller's")
-
-    def plane(t, shape, name):
-        if t is False:
-            return None
-        if t is None:
-            return torch.empty(shape, dtype=torch.float32, device=device)
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape)
-                or t.device != device):
-            raise RtoError(-1, "%s must be a contiguous float32 tensor of shape %s on %s" % (name, list(shape), device))
-        return t
-
-    d = plane(depth, (n, H, W), "depth")
-    c = plane(color, (n, H, W, 4), "color")
-    if n == 0:
-        return d, c
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
-    arr = (CCamera * n)(*[cam.to_c() for cam in cams])
-    cp = params.to_c(merge)
-    check(lib().rto_draw_mesh_layers(meshset._h, arr, n, C.byref(cp), C.c_void_p(d.data_ptr()) if d is not None else None,
-                                     C.c_void_p(c.data_ptr()) if c is not None else None, _stream_ptr(stream)))
-    return d, c
+    from .volrend import _draw_layers
+    return _draw_layers("draw_mesh_layers", lib().rto_draw_mesh_layers, meshset, cams, MeshParams() if params is None else params,
+                        depth, color, merge, stream)
 
 
 def trace_mesh_rays(meshset, origins, dirs, line_spread=0.0, point_spread=0.0, background=1.0, t_hit=None, rgb=None, stream=None):

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CCamera, CGridParams, COptions, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoError, check, lib
+from ._lib import CCamera, CGridParams, COptions, LayerParams, CQueryOut, CRays, CRaysOut, CTreeInfo, RtoError, check, lib
 
 SUPPORTED_SPP = (1, 2, 3, 4, 6, 8, 16, 32)  # volrend.cu:266-278
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_FAST = 0, 1, 2
@@ -384,15 +384,24 @@ class RenderContext:
         check(lib().rto_ctx_layers(self._h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
-    def _own_layers(self):
-        """the depth and colour tensors show_meshes and show_grid draw into, allocated once per context"""
+    def _show_layers(self, name, draw, target, cams, params, refusal=None, **kw):
+        """show_meshes / show_grid: draw(...) for one camera per frame slot into the depth and colour tensors the context keeps
+        alive (allocated once), then bound with set_layers.  refusal: an error to raise after the camera check"""
         import torch
+        if isinstance(cams, Camera):
+            cams = [cams]
+        if len(cams) != self.frames:
+            raise RtoError(-1, "%s: %d cameras for a context of %d frame slots" % (name, len(cams), self.frames))
+        if refusal is not None:
+            raise refusal
         keep = getattr(self, "_grid_layers", None)
         if keep is None:
             device = torch.device("cuda", self.device)
             keep = (torch.empty((self.frames, self.height, self.width), dtype=torch.float32, device=device),
                     torch.empty((self.frames, self.height, self.width, 4), dtype=torch.float32, device=device))
             self._grid_layers = keep
+        draw(target, cams, params, depth=keep[0], color=keep[1], **kw)
+        self.set_layers(keep[0], keep[1])
         return keep
 
     def show_meshes(self, meshset, cams, options, params=None, stream=None, tree=None):
@@ -403,18 +412,10 @@ class RenderContext:
         meshes live in world space, so an NDC tree is refused with RTO_E_UNSUPPORTED, as the grid refuses it.  Returns (depth,
         color)."""
         from .meshes import MeshParams, draw_mesh_layers
-        if isinstance(cams, Camera):
-            cams = [cams]
-        if len(cams) != self.frames:
-            raise RtoError(-1, "show_meshes: %d cameras for a context of %d frame slots" % (len(cams), self.frames))
-        if tree is not None and tree.use_ndc:
-            raise RtoError(-3, "show_meshes: meshes are in world space: over an NDC tree the depth measure differs")
-        keep = self._own_layers()
-        if params is None:
-            params = MeshParams(options)
-        draw_mesh_layers(meshset, cams, params, depth=keep[0], color=keep[1], stream=stream)
-        self.set_layers(keep[0], keep[1])
-        return keep
+        ndc = tree is not None and tree.use_ndc
+        return self._show_layers("show_meshes", draw_mesh_layers, meshset, cams, MeshParams(options) if params is None else params,
+                                 RtoError(-3, "show_meshes: meshes are in world space: over an NDC tree the depth measure differs") if ndc else None,
+                                 stream=stream)
 
     def show_grid(self, tree, cams, options, params=None, stream=None, merge=False):
         """RenderOptions.show_grid for this context: draws the octree grid of `tree` cut off at options.grid_max_depth
@@ -423,16 +424,8 @@ class RenderContext:
         them with set_layers: the launches that follow render over the grid.  Returns (depth [frames, H, W], color [frames, H, W,
         4]).  set_layers() with no arguments restores the offscreen behaviour.  merge=True (after show_meshes): the lines are depth-tested
         against what the layers hold (RTO_GRID_MERGE) instead of replacing them."""
-        if isinstance(cams, Camera):
-            cams = [cams]
-        if len(cams) != self.frames:
-            raise RtoError(-1, "show_grid: %d cameras for a context of %d frame slots" % (len(cams), self.frames))
-        keep = self._own_layers()
-        if params is None:
-            params = GridParams(options)
-        draw_grid_layers(tree, cams, params, depth=keep[0], color=keep[1], merge=merge, stream=stream)
-        self.set_layers(keep[0], keep[1])
-        return keep
+        return self._show_layers("show_grid", draw_grid_layers, tree, cams, GridParams(options) if params is None else params,
+                                 merge=merge, stream=stream)
 
     def enable_depth(self, on=True, batched=False):
         """rto_ctx_enable_depth: launch_renderer / launch_renderer_batch also write depth and t_near [frames, H, W] (include/rto.h
@@ -607,21 +600,13 @@ def launch_renderer_batch(tree, cams, options, ctx, stream=None, rng_jumps=None)
     check(lib().rto_launch_renderer_batch(tree._h, arr, jumps, n, C.byref(co), ctx._h, _stream_ptr(stream)))
 
 
-class GridParams:
+class GridParams(LayerParams):
     """rto_grid_params: max_depth, line_px, color (the lines' rgb), background.  GridParams(options) takes max_depth =
     options.grid_max_depth and background = options.background_brightness (rto_grid_params_default)."""
+    CSTRUCT, DEFAULT = CGridParams, "rto_grid_params_default"
 
-    def __init__(self, options=None, **kw):
-        c = CGridParams()
-        co = options.to_c() if options is not None else None
-        lib().rto_grid_params_default(C.byref(c), C.byref(co) if co is not None else None)
-        self.max_depth, self.line_px = c.max_depth, c.line_px
-        self.color = list(c.color)
-        self.background = c.background
-        for k, v in kw.items():
-            if not hasattr(self, k):
-                raise AttributeError("GridParams has no field '%s'" % k)
-            setattr(self, k, v)
+    def _load(self, c):
+        self.max_depth, self.line_px, self.color, self.background = c.max_depth, c.line_px, list(c.color), c.background
 
     def to_c(self, merge=False):
         c = CGridParams()
@@ -639,16 +624,20 @@ def draw_grid_layers(tree, cams, params=None, depth=None, color=None, merge=Fals
     default options).  merge=True (RTO_GRID_MERGE): depth-test the lines against what the given tensors hold instead of
     overwriting them.  Returns (depth, color) (None for an output not asked for), the inputs of RenderContext.set_layers.
     Asynchronous on `stream` (default: torch's current stream); no sync."""
+    return _draw_layers("draw_grid_layers", lib().rto_draw_grid_layers, tree, cams, GridParams() if params is None else params,
+                        depth, color, merge, stream)
+
+
+def _draw_layers(name, entry, target, cams, params, depth, color, merge, stream):
+    """a layer pass (draw_grid_layers, meshes.draw_mesh_layers) over its C entry point: target = the N3Tree / MeshSet"""
     import torch
-    device = torch.device("cuda", tree.device)
+    device = torch.device("cuda", target.device)
     if isinstance(cams, Camera):
         cams = [cams]
     n = len(cams)
-    if params is None:
-        params = GridParams()
     H, W = (cams[0].height, cams[0].width) if n else (0, 0)
     if merge and (depth is None or depth is False):
-        raise RtoError(-1, "draw_grid_layers: merge=True tests against a depth tensor of the caller's")
+        raise RtoError(-1, "%s: merge=True tests against a depth tensor of the caller's" % name)
 
     def plane(t, shape, name):
         if t is False:
@@ -668,8 +657,8 @@ def draw_grid_layers(tree, cams, params=None, depth=None, color=None, merge=Fals
         stream = torch.cuda.current_stream(device)
     arr = (CCamera * n)(*[cam.to_c() for cam in cams])
     cp = params.to_c(merge)
-    check(lib().rto_draw_grid_layers(tree._h, arr, n, C.byref(cp), C.c_void_p(d.data_ptr()) if d is not None else None,
-                                     C.c_void_p(c.data_ptr()) if c is not None else None, _stream_ptr(stream)))
+    check(entry(target._h, arr, n, C.byref(cp), C.c_void_p(d.data_ptr()) if d is not None else None,
+                C.c_void_p(c.data_ptr()) if c is not None else None, _stream_ptr(stream)))
     return d, c
 
 

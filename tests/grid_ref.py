@@ -8,6 +8,7 @@ import functools
 
 import numpy as np
 
+import layer_ref as L
 from rt_octree_amd import synth
 
 f32 = np.float32
@@ -72,16 +73,7 @@ def _edge_test(p, tau, a, cs, dw, sc, ds, kk):
     return best
 
 
-def camera_dirs(W, H, fx, fy, m):
-    """ray_setup's unit world directions [H * W, 3] (float32, left to right) for the 12-float column-major transform m"""
-    x = np.broadcast_to(np.arange(W, dtype=np.int64).astype(f32)[None, :], (H, W)).reshape(-1)
-    y = np.broadcast_to(np.arange(H, dtype=np.int64).astype(f32)[:, None], (H, W)).reshape(-1)
-    xyz0 = (x - f32(0.5) * f32(W)) / f32(fx)
-    xyz1 = -(y - f32(0.5) * f32(H)) / f32(fy)
-    xyz2 = f32(-1.0)
-    dw = np.stack([(m[c] * xyz0 + m[3 + c] * xyz1) + m[6 + c] * xyz2 for c in range(3)], 1).astype(f32)
-    inv = f32(1) / np.sqrt((dw[:, 0] * dw[:, 0] + dw[:, 1] * dw[:, 1]) + dw[:, 2] * dw[:, 2])
-    return dw * inv[:, None]
+camera_dirs = L.unit_dirs  # ray_setup's unit world directions [H * W, 3]
 
 
 def grid_depth(tree, cam, max_depth, line_px):
@@ -158,21 +150,13 @@ def grid_layers(tree, cams, max_depth, line_px, color=(0.0, 0.0, 0.0), backgroun
     return depth, col
 
 
-def merge_layers(depth, col, old_depth, old_col):
-    """RTO_GRID_MERGE: the GL depth test of (depth, col) against what the buffers hold.  A line pixel replaces both where the
-    existing depth is greater than its own; a NaN or <= 0 existing depth never is (the line's depth is > 0)."""
-    with np.errstate(invalid="ignore"):
-        take = np.isfinite(depth) & (old_depth > depth)
-    return np.where(take, depth, old_depth), np.where(take[..., None], col, old_col)
+merge_layers = L.merge_layers  # RTO_GRID_MERGE
 
 
 # ------------------------------------------------------------------ the cases of the issue
-class Cam:
+class Cam(L.Cam):
     def __init__(self, W, H, pose, fx=None):
-        self.width, self.height = W, H
-        self.fx = self.fy = float(synth.blender_focal(W) if fx is None else fx)
-        self.c2w = np.asarray(pose, np.float64)[:3, :4]
-        self.transform = np.ascontiguousarray(np.asarray(pose, f32)[:3, :4].T).reshape(-1)
+        super().__init__(W, H, pose, synth.blender_focal(W) if fx is None else fx)
 
 
 @functools.lru_cache(maxsize=None)

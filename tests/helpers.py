@@ -66,12 +66,47 @@ def make_pair(tree, device=0):
     return ht, dt
 
 
-def cameras(W, H, pose, fx=None):
+def rcam(W, H, pose, fx=None):
+    """the package's Camera for a pose (fx: synth.blender_focal(W) unless given)"""
     fx = synth.blender_focal(W) if fx is None else fx
     cam = R.Camera(W, H, fx, fx)
     cam.set_c2w(pose)
-    ocam = orc.camera(W, H, fx, fx, cam.transform.reshape(-1))
+    return cam
+
+
+def cameras(W, H, pose, fx=None):
+    cam = rcam(W, H, pose, fx)
+    ocam = orc.camera(W, H, cam.fx, cam.fx, cam.transform.reshape(-1))
     return ocam, cam
+
+
+def rcam_of(model_cam):
+    """the package's Camera for a camera of the numpy models (layer_ref.Cam): the same 12 floats"""
+    cam = R.Camera(model_cam.width, model_cam.height, model_cam.fx, model_cam.fy)
+    cam.transform = [float(v) for v in model_cam.transform]
+    return cam
+
+
+def gpu_torch():
+    import torch
+    return torch
+
+
+def check_33_cameras_in_one_call(draw, cams, model):
+    """33 cameras, one more than a launch takes: draw(cams, **kw) -> (depth, color) against 33 calls and model(f) -> (depth, color)"""
+    torch = gpu_torch()
+    d33, c33 = draw(cams)
+    for f in range(33):
+        d1, c1 = draw([cams[f]])
+        assert torch.equal(d1[0].view(torch.int32), d33[f].view(torch.int32)) and torch.equal(c1[0].view(torch.int32), c33[f].view(torch.int32)), f
+    for f in (0, 31, 32):
+        wd, wc = model(f)
+        assert_bits_equal(d33[f].cpu().numpy(), wd, "frame %d depth" % f)
+        assert_bits_equal(c33[f].cpu().numpy(), wc, "frame %d colour" % f)
+    d_only, none = draw(cams, color=False)
+    assert none is None and torch.equal(d_only.view(torch.int32), d33.view(torch.int32))
+    none, c_only = draw(cams, depth=False)
+    assert none is None and torch.equal(c_only.view(torch.int32), c33.view(torch.int32))
 
 
 def oracle_frame(ht, ocam, spp, frame=0, **optkw):

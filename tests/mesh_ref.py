@@ -11,6 +11,7 @@ import functools
 import numpy as np
 
 import grid_ref as G
+import layer_ref as L
 from rt_octree_amd import Mesh, synth
 
 f32 = np.float32
@@ -208,12 +209,7 @@ def camera_rays(cam):
     """(origins, dirs) [H * W, 3] float32 of a camera's pixels: ray_setup's M xyz before normalising (volrend.camera_rays)"""
     W, H = int(cam.width), int(cam.height)
     m = np.asarray(cam.transform, f32).reshape(-1)
-    x = np.broadcast_to(np.arange(W, dtype=np.int64).astype(f32)[None, :], (H, W)).reshape(-1)
-    y = np.broadcast_to(np.arange(H, dtype=np.int64).astype(f32)[:, None], (H, W)).reshape(-1)
-    xyz0 = (x - f32(0.5) * f32(W)) / f32(cam.fx)
-    xyz1 = -(y - f32(0.5) * f32(H)) / f32(cam.fy)
-    dirs = np.stack([(m[c] * xyz0 + m[3 + c] * xyz1) + m[6 + c] * f32(-1.0) for c in range(3)], 1).astype(f32)
-    return np.broadcast_to(m[9:12], (H * W, 3)).copy(), dirs
+    return np.broadcast_to(m[9:12], (H * W, 3)).copy(), L.pixel_dirs(W, H, cam.fx, cam.fy, m)
 
 
 def spread(px, fx):
@@ -231,11 +227,7 @@ def layers(prims, cam, line_px=1.0, point_px=1.0, background=1.0, want_index=Fal
     return out + (res[2].reshape(H, W),) if want_index else out
 
 
-def merge_layers(depth, col, old_depth, old_col):
-    """RTO_MESH_MERGE: a hit replaces both where the existing depth is greater than its own"""
-    with np.errstate(invalid="ignore"):
-        take = np.isfinite(depth) & (old_depth > depth)
-    return np.where(take, depth, old_depth), np.where(take[..., None], col, old_col)
+merge_layers = L.merge_layers  # RTO_MESH_MERGE
 
 
 # ------------------------------------------------------------------ the scenes of the issue

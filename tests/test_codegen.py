@@ -43,8 +43,9 @@ def device_asm(src, extra=()):
     return _ASM[key]
 
 
-def kernel_resources(src, extra=()):
-    """{mangled kernel name: {"vgprs", "scratch", "occupancy"}} of one device source (the compiler's own remarks)"""
+def kernel_resources(src, extra=(), min_kernels=21):
+    """{mangled kernel name: {"vgprs", "scratch", "occupancy"}} of one device source (the compiler's own remarks); min_kernels: how
+    many the source is known to hold at least"""
     device_asm(src, extra)
     extra = tuple(f for f in makefile_flags(src) if f not in extra) + tuple(extra)
     t = _REMARKS[(src, tuple(extra))]
@@ -52,7 +53,7 @@ def kernel_resources(src, extra=()):
     vg = [int(v) for v in re.findall(r" VGPRs: (\d+)", t)]
     sc = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", t)]
     oc = [int(v) for v in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", t)]
-    assert len(names) == len(vg) == len(sc) == len(oc) and len(names) > 20
+    assert len(names) == len(vg) == len(sc) == len(oc) and len(names) >= min_kernels
     return {n: {"vgprs": v, "scratch": s, "occupancy": o} for n, v, s, o in zip(names, vg, sc, oc)}
 
 
@@ -110,6 +111,24 @@ def test_the_traversal_kernels_private_segments_are_what_is_recorded_here():
     # the single-frame kernel on the two-level image: ancestor stack in LDS rows (0) / the register-stack restart (1)
     fast = [v for n, v in res.items() if n.startswith("_ZN3rto11render_fastILi6ELb0ELb1ELi")]
     assert len(fast) == 2 and all(f["occupancy"] == 5 and f["scratch"] == 0 for f in fast), fast
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
+def test_the_layer_pass_kernels_keep_their_registers_and_no_private_segment():
+    """the shared pixel frame of rto_layer_pass.h costs grid_layers_kernel, built from it, nothing (as a lambda filling an rgb[3] it cost
+    grid_layers_kernel 24 bytes of scratch per lane).  Bounds: the VGPRs before the frame was shared (51 / 72 / 86 at 7 / 7 / 5
+    waves per SIMD), re-derived from that commit with (the Makefile adds no per-source flag for either)
+        hipcc --offload-arch=gfx950 -std=c++17 -O3 -ffp-contract=off -fno-fast-math -Iinclude -Irt-octree_amd/csrc -S
+              --cuda-device-only -Rpass-analysis=kernel-resource-usage rt-octree_amd/csrc/{grid,mesh}_kernels.hip"""
+    for src, kernels in (("grid_kernels.hip", {"grid_layers_kernel": (51, 7)}),
+                         ("mesh_kernels.hip", {"mesh_layers_kernel": (72, 7), "mesh_rays_kernel": (86, 5)})):
+        res = kernel_resources(src, min_kernels=len(kernels))
+        for name, (vgprs, waves) in kernels.items():
+            found = [v for n, v in res.items() if n.startswith("_ZN3rto%d%s" % (len(name), name))]  # (the argument types are not pinned)
+            assert len(found) == 1, (name, sorted(res))
+            k = found[0]
+            assert k["scratch"] == 0, "%s: %d bytes of scratch per lane" % (name, k["scratch"])
+            assert k["vgprs"] <= vgprs and k["occupancy"] >= waves, (name, k)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")

@@ -15,21 +15,15 @@ import numpy as np
 import pytest
 
 import grid_ref as G
+import layer_ref
 import rt_octree_amd as R
+from helpers import assert_bits_equal, check_33_cameras_in_one_call, gpu_torch as _torch, rcam as _rcam
 from rt_octree_amd import _lib, synth
 
 E_INVALID, E_UNSUPPORTED = -1, -3
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "rt-octree_amd", "bin", "volrend_headless")
 f32 = np.float32
-
-
-def _bits_equal(a, b, what):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.flatnonzero(a.view(np.uint32).reshape(-1) != b.view(np.uint32).reshape(-1))
-    assert bad.size == 0, "%s: %d of %d words differ; first at %d: %r vs %r" % (
-        what, bad.size, a.size, bad[0], a.reshape(-1)[bad[0]], b.reshape(-1)[bad[0]])
 
 
 # ------------------------------------------------------------------ CPU
@@ -64,35 +58,14 @@ def _raw(tree_h, cams, n, p, depth, color):
 def _invalid_calls(tree_h, cam, depth, color):
     """every RTO_E_INVALID of include/rto.h as (what, thunk -> rc); depth / color: valid device pointers or fake ones"""
     def params(**kw):
-        p = R.GridParams(**kw).to_c()
-        return p
+        return R.GridParams(**kw).to_c()
 
-    other = R.Camera(cam.width + 8, cam.height, cam.fx, cam.fy)
-    zero_f = R.Camera(cam.width, cam.height, cam.fx, cam.fy)
-    zero_f.fx = 0.0
-    bad_flag = params()
-    bad_flag.flags = 2
-    merge = params()
-    merge.flags = 1
-    ok = params()
-    return [
-        ("null tree", lambda: _raw(None, [cam], 1, ok, depth, color)),
-        ("null cams", lambda: _raw(tree_h, None, 1, ok, depth, color)),
-        ("null params", lambda: _raw(tree_h, [cam], 1, None, depth, color)),
-        ("both outputs null", lambda: _raw(tree_h, [cam], 1, ok, None, None)),
-        ("n < 0", lambda: _raw(tree_h, [cam], -1, ok, depth, color)),
-        ("line_px 0", lambda: _raw(tree_h, [cam], 1, params(line_px=0.0), depth, color)),
+    return layer_ref.invalid_layer_calls(_raw, params, tree_h, cam, depth, color) + [
         ("line_px < 0", lambda: _raw(tree_h, [cam], 1, params(line_px=-1.0), depth, color)),
-        ("line_px nan", lambda: _raw(tree_h, [cam], 1, params(line_px=float("nan")), depth, color)),
         ("line_px inf", lambda: _raw(tree_h, [cam], 1, params(line_px=float("inf")), depth, color)),
         ("max_depth < 0", lambda: _raw(tree_h, [cam], 1, params(max_depth=-1), depth, color)),
         ("colour nan", lambda: _raw(tree_h, [cam], 1, params(color=[0.0, float("nan"), 0.0]), depth, color)),
         ("colour inf", lambda: _raw(tree_h, [cam], 1, params(color=[float("inf"), 0.0, 0.0]), depth, color)),
-        ("unknown flag", lambda: _raw(tree_h, [cam], 1, bad_flag, depth, color)),
-        ("merge without depth", lambda: _raw(tree_h, [cam], 1, merge, None, color)),
-        ("colour misaligned", lambda: _raw(tree_h, [cam], 1, ok, depth, C.c_void_p(C.cast(color, C.c_void_p).value + 8))),
-        ("cameras of differing size", lambda: _raw(tree_h, [cam, other], 2, ok, depth, color)),
-        ("fx 0", lambda: _raw(tree_h, [zero_f], 1, ok, depth, color)),
     ]
 
 
@@ -130,11 +103,6 @@ def test_model_draws_the_wires_only_the_wires_and_the_front_ones(name, pose, lin
 
 
 # ------------------------------------------------------------------ GPU
-def _torch():
-    import torch
-    return torch
-
-
 def _upload(tree, walk="wide", **kw):
     """the walks a tree can be loaded with (as tests/test_query.py selects them): the two-level image, or with RTO_NO_WIDE=1 the
     one-level image"""
@@ -146,13 +114,6 @@ def _upload(tree, walk="wide", **kw):
         os.environ.pop("RTO_NO_WIDE", None)
     assert (dt.wide_nodes > 0) == (walk == "wide")
     return dt
-
-
-def _rcam(W, H, pose, fx=None):
-    fx = synth.blender_focal(W) if fx is None else fx
-    cam = R.Camera(W, H, fx, fx)
-    cam.set_c2w(pose)
-    return cam
 
 
 def _world(tree, xyz):
@@ -192,8 +153,8 @@ def test_layers_equal_the_model_bit_for_bit(name, line_px, walk):
     want_c[..., :3] = np.where(line[..., None], np.array([0.9, 0.2, 0.1], f32), f32(0.75))
     want_c[..., 3] = 1.0
     got_d, got_c = _draw(dt, cams, params)
-    _bits_equal(got_d, want_d, "depth")
-    _bits_equal(got_c, want_c, "colour")
+    assert_bits_equal(got_d, want_d, "depth")
+    assert_bits_equal(got_c, want_c, "colour")
 
 
 @pytest.mark.gpu
@@ -209,8 +170,8 @@ def test_partial_tiles_every_cut_off_and_a_reframed_tree(walk):
         want_d, want_c = G.grid_layers(tree, cams, D, lp, color=(0.0, 0.0, 0.0), background=1.0)
         assert np.isfinite(want_d).sum() > 500
         got_d, got_c = _draw(dt, cams, R.GridParams(max_depth=D, line_px=lp))
-        _bits_equal(got_d, want_d, "depth, max_depth %d" % D)
-        _bits_equal(got_c, want_c, "colour, max_depth %d" % D)
+        assert_bits_equal(got_d, want_d, "depth, max_depth %d" % D)
+        assert_bits_equal(got_c, want_c, "colour, max_depth %d" % D)
 
 
 @pytest.mark.gpu
@@ -245,6 +206,23 @@ def test_one_call_equals_three_and_a_null_output_leaves_the_other_unchanged():
 
 
 @pytest.mark.gpu
+def test_33_cameras_in_one_call_equal_33_calls_and_the_model_across_the_chunk_boundary():
+    """one more camera than travels in one launch's arguments: frames 0, 31 (the last of the first launch) and 32 (the first of
+    the second) against the model, every frame against a call of its own; 67 x 45: partial tiles"""
+    tree, D, _, _ = G.shape("B")
+    dt = _upload(tree)
+    cams = [_rcam(67, 45, p) for p in synth.orbit_poses(33)]
+    params = R.GridParams(max_depth=D, line_px=1.5, color=[0.1, 0.2, 0.3], background=0.5)
+
+    def model(f):
+        wd, wc = G.grid_layers(tree, [cams[f]], D, 1.5, color=(0.1, 0.2, 0.3), background=0.5)
+        assert np.isfinite(wd).sum() > 500
+        return wd[0], wc[0]
+
+    check_33_cameras_in_one_call(lambda c, **kw: R.draw_grid_layers(dt, c, params, **kw), cams, model)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("walk", ["wide", "nodew"])
 def test_merge_is_the_depth_test_against_what_the_buffers_hold(walk):
     from layers_ref import make_layers
@@ -266,13 +244,13 @@ def test_merge_is_the_depth_test_against_what_the_buffers_hold(walk):
     d, c = torch.from_numpy(old_d).cuda(), torch.from_numpy(old_c).cuda()
     R.draw_grid_layers(dt, cams, params, depth=d, color=c, merge=True)
     torch.cuda.synchronize()
-    _bits_equal(d.cpu().numpy(), want_d, "merged depth (untouched pixels keep their bytes)")
-    _bits_equal(c.cpu().numpy(), want_c, "merged colour")
+    assert_bits_equal(d.cpu().numpy(), want_d, "merged depth (untouched pixels keep their bytes)")
+    assert_bits_equal(c.cpu().numpy(), want_c, "merged colour")
     # depth alone
     d = torch.from_numpy(old_d).cuda()
     R.draw_grid_layers(dt, cams, params, depth=d, color=False, merge=True)
     torch.cuda.synchronize()
-    _bits_equal(d.cpu().numpy(), want_d, "merged depth without a colour buffer")
+    assert_bits_equal(d.cpu().numpy(), want_d, "merged depth without a colour buffer")
 
 
 def _e2e_scene():
@@ -303,10 +281,10 @@ def test_render_over_the_drawn_layers_single_frame(spp, kernel):
     R.launch_renderer(dt, cams[0], opt, ctx, offscreen=False)
     aux = ctx.download_aux()
     want_d, want_c = G.grid_layers(tree, cams[:1], 2, 1.0, background=0.8)
-    _bits_equal(d.cpu().numpy(), want_d, "the layers show_grid drew: depth")
-    _bits_equal(c.cpu().numpy(), want_c, "the layers show_grid drew: colour")
+    assert_bits_equal(d.cpu().numpy(), want_d, "the layers show_grid drew: depth")
+    assert_bits_equal(c.cpu().numpy(), want_c, "the layers show_grid drew: colour")
     want = expected_rgba(ht, cams[0], spp, want_d[0], want_c[0], rng_base=orc.rng(frame=1), bg=0.8)
-    _bits_equal(_frame_planes(aux), want, "frame over the grid vs the per-ray oracle")
+    assert_bits_equal(_frame_planes(aux), want, "frame over the grid vs the per-ray oracle")
     assert (want[np.isfinite(want_d[0]).reshape(-1), 3] < 1).any()  # the grid shows through the volume somewhere
 
 
@@ -329,7 +307,7 @@ def test_render_over_the_drawn_layers_batched():
     want_d, want_c = G.grid_layers(tree, cams, 2, 1.0)
     for f, jump in enumerate((3, 1)):
         want = expected_rgba(ht, cams[f], 6, want_d[f], want_c[f], rng_base=orc.rng(frame=jump))
-        _bits_equal(_frame_planes(aux[f]), want, "batched frame %d over the grid vs the per-ray oracle" % f)
+        assert_bits_equal(_frame_planes(aux[f]), want, "batched frame %d over the grid vs the per-ray oracle" % f)
 
 
 @pytest.mark.gpu
@@ -403,5 +381,5 @@ def test_refusals_leave_the_buffers_untouched(tmp_path):
     a, b = R.draw_grid_layers(qd, [cam], R.GridParams(max_depth=D)), R.draw_grid_layers(ex, [cam], R.GridParams(max_depth=D))
     want_d, want_c = G.grid_layers(tree, [cam], D, 1.0)
     for got in (a, b):
-        _bits_equal(got[0].cpu().numpy(), want_d, "quantised tree: depth")
-        _bits_equal(got[1].cpu().numpy(), want_c, "quantised tree: colour")
+        assert_bits_equal(got[0].cpu().numpy(), want_d, "quantised tree: depth")
+        assert_bits_equal(got[1].cpu().numpy(), want_c, "quantised tree: colour")

@@ -15,8 +15,10 @@ import numpy as np
 import pytest
 
 import grid_ref as G
+import layer_ref
 import mesh_ref as M
 import rt_octree_amd as R
+from helpers import assert_bits_equal, check_33_cameras_in_one_call, gpu_torch as _torch, rcam_of as _rcam
 from rt_octree_amd import _lib, synth
 
 E_INVALID, E_UNSUPPORTED = -1, -3
@@ -25,14 +27,6 @@ f32 = np.float32
 # the worst relative depth error of the model against the float64 geometry over the sure pixels of all cases, as measured (see
 # the docstring); the test asserts 4x that
 WORST_DEPTH_ERR = 1.586e-6
-
-
-def _bits_equal(a, b, what):
-    a, b = np.ascontiguousarray(a, f32), np.ascontiguousarray(b, f32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.flatnonzero(a.view(np.uint32).reshape(-1) != b.view(np.uint32).reshape(-1))
-    assert bad.size == 0, "%s: %d of %d words differ; first at %d: %r vs %r" % (
-        what, bad.size, a.size, bad[0], a.reshape(-1)[bad[0]], b.reshape(-1)[bad[0]])
 
 
 def _host_set(name):
@@ -70,28 +64,10 @@ def _invalid_draws(h, cam, depth, color):
     def params(**kw):
         return R.MeshParams(**kw).to_c()
 
-    other = R.Camera(cam.width + 8, cam.height, cam.fx, cam.fy)
-    zero_f = R.Camera(cam.width, cam.height, cam.fx, cam.fy)
-    zero_f.fx = 0.0
-    bad_flag, merge, ok = params(), params(), params()
-    bad_flag.flags, merge.flags = 2, 1
-    nan, inf = float("nan"), float("inf")
-    return [
-        ("null set", lambda: _raw_draw(None, [cam], 1, ok, depth, color)),
-        ("null cams", lambda: _raw_draw(h, None, 1, ok, depth, color)),
-        ("null params", lambda: _raw_draw(h, [cam], 1, None, depth, color)),
-        ("both outputs null", lambda: _raw_draw(h, [cam], 1, ok, None, None)),
-        ("n < 0", lambda: _raw_draw(h, [cam], -1, ok, depth, color)),
-        ("line_px 0", lambda: _raw_draw(h, [cam], 1, params(line_px=0.0), depth, color)),
-        ("line_px nan", lambda: _raw_draw(h, [cam], 1, params(line_px=nan), depth, color)),
+    return layer_ref.invalid_layer_calls(_raw_draw, params, h, cam, depth, color) + [
         ("point_px < 0", lambda: _raw_draw(h, [cam], 1, params(point_px=-1.0), depth, color)),
-        ("point_px inf", lambda: _raw_draw(h, [cam], 1, params(point_px=inf), depth, color)),
-        ("background nan", lambda: _raw_draw(h, [cam], 1, params(background=nan), depth, color)),
-        ("unknown flag", lambda: _raw_draw(h, [cam], 1, bad_flag, depth, color)),
-        ("merge without depth", lambda: _raw_draw(h, [cam], 1, merge, None, color)),
-        ("colour misaligned", lambda: _raw_draw(h, [cam], 1, ok, depth, C.c_void_p(C.cast(color, C.c_void_p).value + 8))),
-        ("cameras of differing size", lambda: _raw_draw(h, [cam, other], 2, ok, depth, color)),
-        ("fx 0", lambda: _raw_draw(h, [zero_f], 1, ok, depth, color)),
+        ("point_px inf", lambda: _raw_draw(h, [cam], 1, params(point_px=float("inf")), depth, color)),
+        ("background nan", lambda: _raw_draw(h, [cam], 1, params(background=float("nan")), depth, color)),
     ]
 
 
@@ -192,7 +168,7 @@ def test_bake_and_bvh_layout(name):
     want = M.scene_prims(name)
     ids = prims.view(np.uint32)[:, M.ID].astype(np.int64)
     assert sorted(ids) == list(range(len(want)))
-    _bits_equal(prims[np.argsort(ids)], want, "baked records")
+    assert_bits_equal(prims[np.argsort(ids)], want, "baked records")
     kinds = want.view(np.uint32)[:, M.KIND]
     assert (ms.triangles, ms.segments, ms.points) == tuple(int((kinds == k).sum()) for k in (3, 2, 1))
     pos = want[:, :9].reshape(-1, 3, 3)
@@ -230,7 +206,7 @@ def test_bake_and_bvh_layout(name):
 
     assert check(0)[0] == n and seen == list(range(len(want)))
     p2, n2 = _host_set(name).download()
-    _bits_equal(p2, prims, "a second build: records")
+    assert_bits_equal(p2, prims, "a second build: records")
     assert np.array_equal(n2.view(np.uint32), words)
     if name == "S2":
         assert ms.triangles == 840 and n >= 2 * 210 - 1  # several levels, leaves of at most 4
@@ -243,7 +219,7 @@ def test_estimate_normals_and_identity_transform():
     ms = R.MeshSet([sp], device=None)
     prims, _ = ms.download()
     prims = prims[np.argsort(prims.view(np.uint32)[:, M.ID])]
-    _bits_equal(prims, M.bake([sp]), "estimated normals")
+    assert_bits_equal(prims, M.bake([sp]), "estimated normals")
     assert np.array_equal(prims[:, 0:3], sp.vert[sp.faces[:, 0], :3]), "identity: positions untouched (-0 + 0 = +0 aside)"
     n = prims[:, 18:27].reshape(-1, 3)
     ln = np.linalg.norm(n.astype(np.float64), axis=1)
@@ -262,8 +238,8 @@ def test_bvh_walk_on_the_cpu_equals_the_brute_force_model(name, pose, line_px):
     o, g = M.camera_rays(cam)
     sp = M.spread(line_px, cam.fx)
     t, rgb = _host_set(name).trace_rays_host(o, g, sp, sp, 0.75)
-    _bits_equal(t, want_d.reshape(-1), "depth")
-    _bits_equal(rgb, want_c[..., :3].reshape(-1, 3), "colour")
+    assert_bits_equal(t, want_d.reshape(-1), "depth")
+    assert_bits_equal(rgb, want_c[..., :3].reshape(-1, 3), "colour")
 
 
 def test_bvh_walk_on_random_and_degenerate_rays():
@@ -281,8 +257,8 @@ def test_bvh_walk_on_random_and_degenerate_rays():
         t, rgb = ms.trace_rays_host(o, g, ls, ps, 0.5)
         want_t, want_c = M.trace(M.scene_prims(name), o, g, ls, ps, 0.5)
         assert np.isfinite(want_t).mean() > 0.1, name
-        _bits_equal(t, want_t, name + ": depth of random rays")
-        _bits_equal(rgb, want_c, name + ": colour of random rays")
+        assert_bits_equal(t, want_t, name + ": depth of random rays")
+        assert_bits_equal(rgb, want_c, name + ": colour of random rays")
     ms = _host_set("S2")
     c = (0.5 * (ms.bounds[0] + ms.bounds[1])).astype(f32)
     o = np.tile(c - np.array([3.0, 0.0, 0.0], f32), (7, 1))
@@ -297,8 +273,8 @@ def test_bvh_walk_on_random_and_degenerate_rays():
     assert np.isfinite(t[0]) and (rgb[0] != 0.125).any()
     assert np.isposinf(t[1:]).all() and (rgb[1:] == 0.125).all()
     want_t, want_c = M.trace(M.scene_prims("S2"), o, g, 0.0, 0.0, 0.125)
-    _bits_equal(t, want_t, "degenerate rays: depth")
-    _bits_equal(rgb, want_c, "degenerate rays: colour")
+    assert_bits_equal(t, want_t, "degenerate rays: depth")
+    assert_bits_equal(rgb, want_c, "degenerate rays: colour")
 
 
 def _sure_pixels(name, pose):
@@ -358,7 +334,7 @@ def test_model_lines_and_points_against_float64(pose, line_px):
     tri = prims[prims.view(np.uint32)[:, M.KIND] == 3]
     dt, _ = M.layers(tri, cam, line_px, line_px, 1.0)
     full = M.scene_layers("S1", pose, line_px, 0.75)[0]
-    _bits_equal(full, np.minimum(dt, d), "S1: the nearer of triangles and lines")
+    assert_bits_equal(full, np.minimum(dt, d), "S1: the nearer of triangles and lines")
 
 
 def test_tie_rule_lowest_index_wins():
@@ -372,30 +348,19 @@ def test_tie_rule_lowest_index_wins():
         ms = R.MeshSet(order, device=None)
         t, rgb = ms.trace_rays_host(o, g, sp, sp, 1.0)
         mt, mrgb, who = M.trace(M.bake(order), o, g, sp, sp, 1.0, want_index=True)
-        _bits_equal(t, mt, key + ": depth")
-        _bits_equal(rgb, mrgb, key + ": colour")
+        assert_bits_equal(t, mt, key + ": depth")
+        assert_bits_equal(rgb, mrgb, key + ": colour")
         out[key] = (t, rgb, who)
     tri = out["ab"][2] == 0
     assert tri.sum() > 50 and not (out["ab"][2] == 1).any() and np.array_equal(out["ba"][2] == 0, tri)
     # (the interpolation weights sum to 1 only up to rounding: the winner's channel is 1 - a few ulp, the loser's exactly 0)
     ab, ba = out["ab"][1][tri], out["ba"][1][tri]
     assert (np.abs(ab[:, 0] - 1) < 1e-6).all() and (ab[:, 1:] == 0).all() and (np.abs(ba[:, 2] - 1) < 1e-6).all() and (ba[:, :2] == 0).all()
-    _bits_equal(out["ab"][0], out["ba"][0], "the depth does not depend on the order")
+    assert_bits_equal(out["ab"][0], out["ba"][0], "the depth does not depend on the order")
     assert (out["ab"][2] == 2).any()  # the segment in their plane wins somewhere (outside the triangles, or nearer by rounding)
 
 
 # ------------------------------------------------------------------ GPU
-def _torch():
-    import torch
-    return torch
-
-
-def _rcam(gcam):
-    cam = R.Camera(gcam.width, gcam.height, gcam.fx, gcam.fy)
-    cam.transform = [float(v) for v in gcam.transform]
-    return cam
-
-
 def _dev_set(name):
     return R.MeshSet(list(M.scene(name)[0]), device=0)
 
@@ -420,8 +385,8 @@ def test_layers_equal_the_model_bit_for_bit(name, line_px):
     want_d, want_c = _want(name, M.POSES, line_px, 0.75)
     d, c = R.draw_mesh_layers(ms, cams, R.MeshParams(line_px=line_px, point_px=line_px, background=0.75))
     _torch().cuda.synchronize()
-    _bits_equal(_np(d), want_d, "depth")
-    _bits_equal(_np(c), want_c, "colour")
+    assert_bits_equal(_np(d), want_d, "depth")
+    assert_bits_equal(_np(c), want_c, "colour")
     info = _lib.CMeshesInfo()
     assert R.lib().rto_meshes_get_info(ms._h, C.byref(info)) == 0
     assert info.device == 0 and info.device_bytes == 32 * info.nodes + 128 * (info.triangles + info.segments + info.points)
@@ -435,19 +400,9 @@ def test_33_cameras_in_one_call_equal_33_calls_and_n_0_writes_nothing():
     poses = synth.orbit_poses(33)
     cams = [_rcam(G.Cam(W, H, poses[i])) for i in range(33)]
     params = R.MeshParams(line_px=1.5, point_px=3.0, background=0.5)
-    d33, c33 = R.draw_mesh_layers(ms, cams, params)
-    for f in range(33):
-        d1, c1 = R.draw_mesh_layers(ms, [cams[f]], params)
-        assert torch.equal(d1[0].view(torch.int32), d33[f].view(torch.int32)) and torch.equal(c1[0].view(torch.int32), c33[f].view(torch.int32)), f
     prims = M.scene_prims("S1")
-    for f in (0, 31, 32):
-        wd, wc = M.layers(prims, G.Cam(W, H, poses[f]), 1.5, 3.0, 0.5)
-        _bits_equal(_np(d33[f]), wd, "frame %d depth" % f)
-        _bits_equal(_np(c33[f]), wc, "frame %d colour" % f)
-    d_only, none = R.draw_mesh_layers(ms, cams, params, color=False)
-    assert none is None and torch.equal(d_only.view(torch.int32), d33.view(torch.int32))
-    none, c_only = R.draw_mesh_layers(ms, cams, params, depth=False)
-    assert none is None and torch.equal(c_only.view(torch.int32), c33.view(torch.int32))
+    check_33_cameras_in_one_call(lambda c, **kw: R.draw_mesh_layers(ms, c, params, **kw), cams,
+                                 lambda f: M.layers(prims, G.Cam(W, H, poses[f]), 1.5, 3.0, 0.5))
     buf = torch.full((16,), 7.0, device="cuda")
     assert _raw_draw(ms._h, [cams[0]], 0, params.to_c(), C.c_void_p(buf.data_ptr()), None) == 0
     torch.cuda.synchronize()
@@ -468,14 +423,14 @@ def test_rays_equal_the_layers_and_split_batches_give_the_same_bytes(name):
     t, rgb = R.trace_mesh_rays(ms, o, g, sp, sp, 0.75)
     d, c = R.draw_mesh_layers(ms, [cam], R.MeshParams(line_px=lp, point_px=lp, background=0.75))
     torch.cuda.synchronize()
-    _bits_equal(_np(t), _np(d).reshape(-1), "rays vs layers: depth")
-    _bits_equal(_np(rgb), _np(c)[0, ..., :3].reshape(-1, 3), "rays vs layers: colour")
-    _bits_equal(_np(t), want_d.reshape(-1), "rays vs the model")
+    assert_bits_equal(_np(t), _np(d).reshape(-1), "rays vs layers: depth")
+    assert_bits_equal(_np(rgb), _np(c)[0, ..., :3].reshape(-1, 3), "rays vs layers: colour")
+    assert_bits_equal(_np(t), want_d.reshape(-1), "rays vs the model")
     k = len(o) // 3 + 5
     t1, c1 = R.trace_mesh_rays(ms, o[:k], g[:k], sp, sp, 0.75)
     t2, c2 = R.trace_mesh_rays(ms, o[k:], g[k:], sp, sp, 0.75)
-    _bits_equal(np.concatenate([_np(t1), _np(t2)]), _np(t), "a split batch: depth")
-    _bits_equal(np.concatenate([_np(c1), _np(c2)]), _np(rgb), "a split batch: colour")
+    assert_bits_equal(np.concatenate([_np(t1), _np(t2)]), _np(t), "a split batch: depth")
+    assert_bits_equal(np.concatenate([_np(c1), _np(c2)]), _np(rgb), "a split batch: colour")
     # degenerate rays
     bad = np.tile(g[len(g) // 2], (6, 1)).astype(f32)
     ob = np.tile(o[0], (6, 1)).astype(f32)
@@ -488,8 +443,8 @@ def test_rays_equal_the_layers_and_split_batches_give_the_same_bytes(name):
     torch.cuda.synchronize()
     assert np.isposinf(_np(tb)[1:]).all() and (_np(cb)[1:] == 0.125).all()
     wt, wc = M.trace(M.scene_prims(name), ob, bad, sp, sp, 0.125)
-    _bits_equal(_np(tb), wt, "degenerate rays: depth")
-    _bits_equal(_np(cb), wc, "degenerate rays: colour")
+    assert_bits_equal(_np(tb), wt, "degenerate rays: depth")
+    assert_bits_equal(_np(cb), wc, "degenerate rays: colour")
 
 
 def _prefill(want_d, seed):
@@ -522,12 +477,12 @@ def test_merge_is_the_depth_test_against_what_the_buffers_hold():
     d, c = torch.from_numpy(old_d).cuda(), torch.from_numpy(old_c).cuda()
     R.draw_mesh_layers(ms, cams, params, depth=d, color=c, merge=True)
     torch.cuda.synchronize()
-    _bits_equal(_np(d), want_d, "merged depth (untouched pixels keep their bytes)")
-    _bits_equal(_np(c), want_c, "merged colour")
+    assert_bits_equal(_np(d), want_d, "merged depth (untouched pixels keep their bytes)")
+    assert_bits_equal(_np(c), want_c, "merged colour")
     d = torch.from_numpy(old_d).cuda()
     R.draw_mesh_layers(ms, cams, params, depth=d, color=False, merge=True)
     torch.cuda.synchronize()
-    _bits_equal(_np(d), want_d, "merged depth without a colour buffer")
+    assert_bits_equal(_np(d), want_d, "merged depth without a colour buffer")
 
 
 def _upload(tree):
@@ -549,9 +504,9 @@ def test_meshes_then_the_grid_merged_equal_the_nearer_of_the_two_models():
     gd, gc = G.grid_layers(tree, gcams, 2, 1.0, color=(0.0, 0.0, 0.0), background=0.6)
     want_d, want_c = G.merge_layers(gd, gc, md, mc)
     assert (np.isfinite(gd) & (gd < md)).sum() > 200 and (np.isfinite(md) & (md < gd)).sum() > 200
-    _bits_equal(_np(d), want_d, "meshes, then the grid merged: depth")
-    _bits_equal(_np(c), want_c, "meshes, then the grid merged: colour")
-    _bits_equal(_np(d), np.minimum(md, gd), "the per-pixel nearer of the two")
+    assert_bits_equal(_np(d), want_d, "meshes, then the grid merged: depth")
+    assert_bits_equal(_np(c), want_c, "meshes, then the grid merged: colour")
+    assert_bits_equal(_np(d), np.minimum(md, gd), "the per-pixel nearer of the two")
 
 
 def _frame_rgba(aux):
@@ -588,8 +543,8 @@ def test_frames_over_the_mesh_layers_equal_rays_limited_by_the_mesh_trace(spp):
     R.launch_renderer(dt, cams[0], opt, ctx, offscreen=False)
     aux = ctx.download_aux()
     want, t = rays_of(cams[0], ctx)
-    _bits_equal(_np(d)[0].reshape(-1), t, "the layer show_meshes drew vs the ray trace")
-    _bits_equal(_frame_rgba(aux), want, "single frame over the meshes vs rto_launch_rays")
+    assert_bits_equal(_np(d)[0].reshape(-1), t, "the layer show_meshes drew vs the ray trace")
+    assert_bits_equal(_frame_rgba(aux), want, "single frame over the meshes vs rto_launch_rays")
     assert np.isfinite(t).sum() > 300 and (want[np.isfinite(t), 3] < 1).any()
 
     jumps = [3, 1, 4, 2]
@@ -603,7 +558,7 @@ def test_frames_over_the_mesh_layers_equal_rays_limited_by_the_mesh_trace(spp):
     for f in range(4):
         one.rng_seed()
         one.rng_advance(jumps[f] << 32)
-        _bits_equal(_frame_rgba(baux[f]), rays_of(cams[f], one)[0], "batched frame %d over the meshes vs rto_launch_rays" % f)
+        assert_bits_equal(_frame_rgba(baux[f]), rays_of(cams[f], one)[0], "batched frame %d over the meshes vs rto_launch_rays" % f)
 
     torch.manual_seed(3)
     net = denoiser.FusedGuidanceNet(denoiser.GuidanceNetCompact.from_full(denoiser.GuidanceNet(8, 32, 5, 2, 4)).eval())
