@@ -812,6 +812,56 @@ int rto_metrics_compute(rto_metrics* m, void* stream, const void* pred, int pred
  * not take -- 16-bit, palette, grey or interlaced images, a truncated file, inflated data shorter or longer than the image, a
  * bad CRC, a filter type above 4. */
 int rto_image_read_png(const char* path, int* width, int* height, uint8_t* rgba, size_t cap);
+/* Host only: RGBA8 [height][width][4] -> an 8-bit RGBA PNG, the writer of the headless renderer (renderer/src/imwrite.cpp:14-86:
+ * filter 0, stored deflate blocks).  RTO_E_INVALID: a null argument or a non-positive extent; RTO_E_IO: the file cannot be written. */
+int rto_image_write_png(const char* path, const uint8_t* rgba, int width, int height);
+
+/* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
+ * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
+ * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that
+ * kernel.  The caller sums the branches (differentiably) and passes each layer's EFFECTIVE kernel and bias, float32 in device
+ * memory -- they change every step, so there is no packing step.  The domain is the fused inference network's: 8 -> c1 [-> c1]
+ * -> 2 * levels, c1 in 1..64, levels in 1..6, two or three layers.  All arithmetic is float32 with float32 accumulation.
+ *   forward (network.py:86-118):  z_l = conv3x3(x_{l-1}, W_l, zero padding "same") + b_l,  x_l = min(max(z_l, 0), 6);
+ *       weight_map = softmax over channels 0..levels-1 of the last x, guidance_map = its channels levels..2 levels - 1, both
+ *       [n][levels][H][W] as rto_filtering_train_forward takes them.  Every x_l is stored in `acts`: float32 planes
+ *       [n][cout_l][H][W], layer after layer (rto_guidance_train_acts_bytes gives the size).  That layout is part of the ABI.
+ *   backward:  softmax dx_k = w_k (g_k - sum_j g_j w_j); ReLU6 passes the gradient where 0 < x_l < 6 and nothing where x_l is
+ *       exactly 0 or 6 (torch's hardtanh_backward), read from `acts`; layers[l].grad_weight [cout][cin][3][3] and .grad_bias
+ *       [cout] are OVERWRITTEN for every layer.  There is no gradient for aux.
+ * No floating-point atomics: workgroups write partial sums to the handle's scratch and a finishing kernel adds them in a fixed
+ * order, so the same inputs give the same bits.  The calls keep no state between forward and backward other than the caller's
+ * `acts`: forwards and backwards of different inputs may interleave in any order on one stream.  The handle owns the backward's
+ * and the loss's scratch, which grows on demand; growing synchronises the device once.  One handle serves one stream at a time.
+ * Refused before any device use -- RTO_E_INVALID: a null pointer; n, H or W < 1; num_layers outside 2..3; layers[0].cin != 8,
+ * layers[l].cin != layers[l-1].cout or the last cout != 2 * levels; n H W > 2^31 - 1.  RTO_E_UNSUPPORTED: c1 outside 1..64, levels
+ * outside 1..6, a middle layer that is not c1 -> c1. */
+typedef struct rto_guidance_train rto_guidance_train;
+typedef struct rto_guidance_train_layer {
+    const float* weight; /* device, [cout][cin][3][3] */
+    const float* bias;   /* device, [cout] */
+    float* grad_weight;  /* device, backward only (forward and the size query ignore them) */
+    float* grad_bias;
+    int cin, cout;
+} rto_guidance_train_layer;
+int rto_guidance_train_create(int device, rto_guidance_train** out);
+void rto_guidance_train_free(rto_guidance_train* t);
+int rto_guidance_train_acts_bytes(const rto_guidance_train_layer* layers, int num_layers, int levels, int n, int H, int W, size_t* bytes);
+int rto_guidance_train_forward(rto_guidance_train* t, void* stream, const float* aux, const rto_guidance_train_layer* layers, int num_layers,
+                               int levels, int n, int H, int W, float* acts, float* weight_map, float* guidance_map);
+int rto_guidance_train_backward(rto_guidance_train* t, void* stream, const float* grad_weight_map, const float* grad_guidance_map,
+                                const float* aux, const float* acts, const rto_guidance_train_layer* layers, int num_layers, int levels, int n,
+                                int H, int W);
+/* The training loss and its gradient in one call (runner.py:78; metrics.py:7-9, 21-33): the mean over the r, g, b of pred against
+ * truth, [n][H][W][4] float32 each (16-byte aligned), of |p - t| / (|p| + |t| + 1e-5) (RTO_LOSS_SMAPE) or (p - t)^2 (RTO_LOSS_MSE).
+ * Terms in float64 from the float32 inputs, reduced by fixed-order partial sums (the convention of the image metrics); *device_loss
+ * is one double in device memory.  grad_pred [n][H][W][4] = d loss / d pred, alpha component 0: for SMAPE
+ * (sign(p - t) / D - |p - t| sign(p) / D^2) / (3 n H W) with D = |p| + |t| + 1e-5 and sign(0) = 0, so p == t gives exactly 0 as
+ * torch's abs does.  Non-finite inputs propagate.  RTO_E_INVALID: a null or misaligned pointer, n, H or W < 1, an unknown kind. */
+#define RTO_LOSS_SMAPE 0
+#define RTO_LOSS_MSE 1
+int rto_loss_forward_backward(rto_guidance_train* t, void* stream, const float* pred, const float* truth, int n, int H, int W, int kind,
+                              double* device_loss, float* grad_pred);
 
 /* ---- profiling aid ---- */
 /* Counter calibration (MI355X_MICROARCH.md "HBM"): launches `repeats` kernels in which every lane

@@ -87,6 +87,12 @@ class CGuidanceLayer(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("cin", C.c_int), ("cout", C.c_int)]
 
 
+class CGuidanceTrainLayer(C.Structure):
+    """rto_guidance_train_layer (include/rto.h): device pointers to one layer's effective kernel, bias and their gradients"""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p),
+                ("cin", C.c_int), ("cout", C.c_int)]
+
+
 class CGuidanceNetInfo(C.Structure):
     _fields_ = [("c1", C.c_int), ("levels", C.c_int), ("num_layers", C.c_int), ("halo", C.c_int), ("packed_route", C.c_int)]
 
@@ -207,6 +213,13 @@ SYMBOLS = {
     "rto_metrics_compute_async": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "rto_metrics_compute": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "rto_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
+    "rto_image_write_png": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
+    "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_guidance_train_free": (None, [_P]),
+    "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "rto_guidance_train_forward": (C.c_int, [_P, _P, _P, C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rto_guidance_train_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rto_loss_forward_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rto_probe_gather": (C.c_int, [C.c_uint64, C.c_int]),
     "rto_probe_gather_sweep": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_double)]),

@@ -360,10 +360,170 @@ def filtering_autograd(weight_map, guidance_map, imgs_in, requires_grad=False):
     return _Filtering.apply(weight_map, guidance_map, imgs_in, requires_grad)
 
 
-def filtering(model, aux_buffer, img_in, requires_grad=False):
-    """denoiser/network.py:77-84: model(aux) -> (weight_map, guidance_map) -> filtering_autograd."""
-    weight_map, guidance_map = model(aux_buffer)
+def filtering(model, aux_buffer, img_in, requires_grad=False, fused=False):
+    """denoiser/network.py:77-84: model(aux) -> (weight_map, guidance_map) -> filtering_autograd.
+    fused=True (a GuidanceNet under training): the network runs as the float32 HIP training kernels on its effective layers
+    (effective_layers + guidance_autograd) instead of through PyTorch under autocast."""
+    if fused:
+        weight_map, guidance_map = guidance_autograd(aux_buffer, effective_layers(model), model.kernel_levels)
+    else:
+        weight_map, guidance_map = model(aux_buffer)
     return filtering_autograd(weight_map, guidance_map, img_in, requires_grad=requires_grad)
+
+
+def effective_layers(model):
+    """[(W_eff [cout,cin,3,3], b_eff [cout])] of a GuidanceNet, differentiable: a RepVGGBlock (network.py:49-75) is linear before
+    its ReLU6, so its branches add up to one 3x3 kernel.  Summed in the order of RepVGGBlockCompact.from_full (network.py:135-151):
+    the conv3 branches in index order, the zero-padded conv1 branches, +1 at [o, o % cin, 1, 1] when cin == cout.  Autograd through
+    these sums hands the one kernel's gradient to every branch."""
+    out = []
+    for blk in model.layers:
+        w, b = blk.conv3[0].weight, blk.conv3[0].bias
+        for i in range(1, blk.num_branches):
+            w, b = w + blk.conv3[i].weight, b + blk.conv3[i].bias
+        for i in range(blk.num_branches):
+            w, b = w + F.pad(blk.conv1[i].weight, (1, 1, 1, 1)), b + blk.conv1[i].bias
+        if blk.in_channels == blk.out_channels:
+            ident = torch.zeros_like(w)
+            o = torch.arange(blk.out_channels, device=w.device)
+            ident[o, o % blk.in_channels, 1, 1] = 1
+            w = w + ident
+        out.append((w, b))
+    return out
+
+
+class _TrainHandle:
+    """rto_guidance_train: the scratch of the training backward and of the loss; one per device, used on torch's current stream"""
+    _by_device = {}
+
+    def __init__(self, device):
+        import ctypes as C
+        from ._lib import check, lib
+        self._h = C.c_void_p(0)
+        h = C.c_void_p(0)
+        check(lib().rto_guidance_train_create(int(device), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def get(cls, device):
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in cls._by_device:
+            cls._by_device[idx] = cls(idx)
+        return cls._by_device[idx]._h
+
+    def __del__(self):
+        try:
+            from ._lib import lib
+            if getattr(self, "_h", None):
+                lib().rto_guidance_train_free(self._h)
+        except Exception:
+            pass
+
+
+def _train_layers(tensors, grads=None):
+    from ._lib import CGuidanceTrainLayer
+    n = len(tensors) // 2
+    layers = (CGuidanceTrainLayer * n)()
+    for l in range(n):
+        w, b = tensors[2 * l], tensors[2 * l + 1]
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or tuple(b.shape) != (w.shape[0],):
+            raise RuntimeError("guidance_autograd: layer %d is not a 3x3 kernel [cout,cin,3,3] with a bias [cout]" % l)
+        layers[l].weight, layers[l].bias, layers[l].cin, layers[l].cout = w.data_ptr(), b.data_ptr(), int(w.shape[1]), int(w.shape[0])
+        if grads is not None:
+            layers[l].grad_weight, layers[l].grad_bias = grads[2 * l].data_ptr(), grads[2 * l + 1].data_ptr()
+    return layers, n
+
+
+class _GuidanceTrain(torch.autograd.Function):
+    """The network under training (network.py:86-118) on its effective layers: rto_guidance_train_forward / _backward
+    (csrc/guidance_train_kernels.hip), float32, deterministic; no state between the two but the saved activations."""
+
+    @staticmethod
+    def forward(ctx, aux, levels, *flat):
+        import ctypes as C
+        from ._lib import check, lib
+        if not aux.is_cuda:
+            raise RuntimeError("guidance_autograd needs CUDA(HIP) tensors: the training kernels have no CPU path")
+        x = aux.detach().float().contiguous()
+        ts = [t.detach().float().contiguous() for t in flat]
+        layers, nl = _train_layers(ts)
+        n, _c, H, W = (int(v) for v in x.shape)
+        nbytes = C.c_size_t(0)
+        check(lib().rto_guidance_train_acts_bytes(layers, nl, int(levels), n, H, W, C.byref(nbytes)))
+        acts = torch.empty(nbytes.value // 4, device=x.device, dtype=torch.float32)
+        wm = torch.empty((n, int(levels), H, W), device=x.device, dtype=torch.float32)
+        gm = torch.empty_like(wm)
+        s = torch.cuda.current_stream(x.device).cuda_stream
+        with torch.cuda.device(x.device):
+            check(lib().rto_guidance_train_forward(_TrainHandle.get(x.device), s, x.data_ptr(), layers, nl, int(levels), n, H, W,
+                                                   acts.data_ptr(), wm.data_ptr(), gm.data_ptr()))
+        ctx.save_for_backward(x, acts, *ts)
+        ctx.levels = int(levels)
+        return wm, gm
+
+    @staticmethod
+    def backward(ctx, grad_wm, grad_gm):
+        from ._lib import check, lib
+        x, acts, *ts = ctx.saved_tensors
+        gw, gg = grad_wm.float().contiguous(), grad_gm.float().contiguous()
+        grads = [torch.empty_like(t) for t in ts]
+        layers, nl = _train_layers(ts, grads)
+        n, _c, H, W = (int(v) for v in x.shape)
+        s = torch.cuda.current_stream(x.device).cuda_stream
+        with torch.cuda.device(x.device):
+            check(lib().rto_guidance_train_backward(_TrainHandle.get(x.device), s, gw.data_ptr(), gg.data_ptr(), x.data_ptr(),
+                                                    acts.data_ptr(), layers, nl, ctx.levels, n, H, W))
+        return (None, None) + tuple(grads)  # (no gradient for the aux planes)
+
+
+def guidance_autograd(aux, layers, levels):
+    """aux [n,8,H,W], layers = [(W_l [cout,cin,3,3], b_l [cout])] (effective_layers), levels -> (weight_map, guidance_map)
+    [n,levels,H,W] float32, differentiable with respect to every W_l and b_l."""
+    flat = [t for wb in layers for t in wb]
+    return _GuidanceTrain.apply(aux, levels, *flat)
+
+
+LOSS_KINDS = {"smape": 0, "mse": 1}  # RTO_LOSS_*
+
+
+class _ImageLoss(torch.autograd.Function):
+    """rto_loss_forward_backward: the loss (one float64) and d loss / d pred in one launch pair"""
+
+    @staticmethod
+    def forward(ctx, pred, truth, kind):
+        from ._lib import check, lib
+        if not (pred.is_cuda and truth.is_cuda):
+            raise RuntimeError("image_loss needs CUDA(HIP) tensors")
+        p, t = pred.detach().float().contiguous(), truth.detach().float().contiguous()
+        if p.shape != t.shape or p.dim() not in (3, 4) or p.shape[-1] != 4:
+            raise RuntimeError("image_loss: pred and truth [n,H,W,4] (or [H,W,4]) expected")
+        n, H, W = (1,) + tuple(p.shape[:2]) if p.dim() == 3 else tuple(p.shape[:3])
+        loss = torch.empty((), device=p.device, dtype=torch.float64)
+        grad = torch.empty_like(p)
+        s = torch.cuda.current_stream(p.device).cuda_stream
+        with torch.cuda.device(p.device):
+            check(lib().rto_loss_forward_backward(_TrainHandle.get(p.device), s, p.data_ptr(), t.data_ptr(), int(n), int(H), int(W),
+                                                  int(kind), loss.data_ptr(), grad.data_ptr()))
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (grad,) = ctx.saved_tensors
+        return grad * grad_loss.to(torch.float32), None, None
+
+
+def image_loss(pred, truth, kind="smape"):
+    """The training loss of denoiser/metrics.py:21-33 over the r, g, b of pred against truth [n,H,W,4]: "smape" and "mse" on the
+    device in float64 (a float64 scalar tensor, differentiable with respect to pred); "huber" stays in torch; the two LPIPS
+    losses need network weights that are not here and are refused."""
+    if kind in LOSS_KINDS:
+        return _ImageLoss.apply(pred, truth, LOSS_KINDS[kind])
+    if kind == "huber":
+        return F.huber_loss(pred[..., :3], truth[..., :3])
+    if kind in ("lpips_alex", "lpips_vgg"):
+        raise NotImplementedError("loss '%s' needs the LPIPS network weights, which this package does not ship" % kind)
+    raise NotImplementedError("Invalid loss function: %s" % kind)
 
 
 class Denoiser:

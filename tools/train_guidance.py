@@ -7,7 +7,7 @@ HIP forward-with-saves and gather-form backward of the guided filter.
 The result is a state_dict of the reference's module layout (layers.N.conv3/conv1.M.weight/bias), small
 enough to commit: bench.py loads rt-octree_amd/weights/guidance_synth_lego.pt when it exists, so its PSNR
 block reports a trained denoiser instead of random weights.  Held out of training: every pose with
-index % 4 == 0 (pose 0 is the one bench.py scores).
+index % 4 == 0 (pose 0 is the one bench.py scores).  --fused trains through the float32 HIP training kernels instead.
 
 usage: python tools/train_guidance.py [--iters 1500] [--out gpurun_out/guidance_synth_lego.pt]"""
 import argparse
@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--mid-channels", type=int, default=32, help="1..64 (the reference trainer's mid_channels); every such net runs as the fused HIP kernel")
     ap.add_argument("--layers", type=int, default=2, choices=[2, 3], help="the reference trainer's num_layers")
     ap.add_argument("--levels", type=int, default=4, choices=[1, 2, 3, 4, 5, 6], help="the reference trainer's kernel_levels")
+    ap.add_argument("--fused", action="store_true", help="train through the float32 HIP training kernels and the device loss "
+                    "(denoiser.filtering(..., fused=True) + denoiser.image_loss): no autocast, no loss scaler")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "guidance_synth_lego.pt"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -132,11 +134,16 @@ def main():
         noisy = torch.stack([data[i][1][r] for i, r in zip(pick, rz)])
         tgt = torch.stack([data[i][2] for i in pick])
         opt.zero_grad(set_to_none=True)
-        out = denoiser.filtering(model, aux, noisy, requires_grad=True)
-        loss = smape(out[..., :3], tgt[..., :3]) if args.loss == "smape" else ((out[..., :3] - tgt[..., :3]) ** 2).mean()
-        scaler.scale(loss).backward()
-        scaler.step(opt)
-        scaler.update()
+        if args.fused:
+            loss = denoiser.image_loss(denoiser.filtering(model, aux, noisy, requires_grad=True, fused=True), tgt, args.loss)
+            loss.backward()
+            opt.step()
+        else:
+            out = denoiser.filtering(model, aux, noisy, requires_grad=True)
+            loss = smape(out[..., :3], tgt[..., :3]) if args.loss == "smape" else ((out[..., :3] - tgt[..., :3]) ** 2).mean()
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
         sched.step()
         if it % 100 == 0 or it == args.iters - 1:
             print("it %4d loss %.5f  (%.1f it/s)" % (it, float(loss.detach()), (it + 1) / (time.time() - t0)), flush=True)
