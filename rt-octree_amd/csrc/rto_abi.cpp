@@ -1,7 +1,7 @@
 // rto_abi.cpp -- the C ABI declared in include/rto.h: version, errors, options, the rto_ctx_* surface, the filtering entry
-// points, downloads and timers.  Trees: rto_tree.cpp; the launch entries: rto_render_abi.cpp.
-// Host logic only; every computation on frame data happens in the gfx950 kernels
-// (render_kernels.hip, filter_kernels.hip).  There is no CPU fallback.
+// points, downloads and timers.  Trees: rto_tree.cpp; the launch entries: rto_render_abi.cpp.  Owns the error string that
+// set_err (rto_abi_common.h) records for every unit of the library.  Host logic only; every computation on frame data
+// happens in the gfx950 kernels (render_kernels.hip, filter_kernels.hip).  There is no CPU fallback.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -23,17 +23,6 @@ int set_err(int code, const std::string& msg) {
 }
 
 namespace {
-
-// The raw filtering entry points take device pointers only: launch on the device that owns the output
-// buffer (a process that drives several GPUs may have another one current).
-int device_of(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return a.device;
-}
 
 void pcg_seed(rto::Pcg32& r, uint64_t initstate, uint64_t initseq) {  // pcg32.h:53-59
     auto next = [&]() { r.state = r.state * rto::kPcgMult + r.inc; };
@@ -98,8 +87,26 @@ rto::OptDev make_opt_dev(const rto_options* o) {
     return od;
 }
 
-// error hook for the other translation units of the library (not part of the public ABI)
-extern "C" int rto_set_error_(int code, const char* msg) { return set_err(code, msg ? msg : ""); }
+// The four plain filter entries take device pointers only, and differ in one line: the launch.  Their checks, in one order:
+// `ptrs` are non-null and the sizes positive (who: the prefix of the entry's own messages), the window is one the reference has
+// (filtering.cu:362-366), `in` and `out` differ (both null: the entry has no such pair); then launch() -> hipError_t runs on the
+// device that owns dev_ptr, the entry's output (a process that drives several GPUs may have another one current).
+template <class Launch>
+static int filter_call(const char* who, std::initializer_list<const void*> ptrs, int L, int H, int W, int n, const void* in,
+                       const void* out, const void* dev_ptr, const char* launch_name, Launch launch) {
+    bool null = false;
+    for (const void* p : ptrs) null = null || !p;
+    if (null || H <= 0 || W <= 0 || n < 1) return set_err(RTO_E_INVALID, std::string(who) + ": null pointer or bad size");
+    if (L < 1 || L > 6) return set_err(RTO_E_INVALID, "Kernel size == " + std::to_string(L * 2 + 1) + " not supported.");
+    if (in && in == out) return set_err(RTO_E_INVALID, std::string(who) + ": img_in and img_out must differ");
+    const int dev = pointer_device(dev_ptr);
+    if (dev < 0) return set_err(RTO_E_INVALID, "filtering: the output pointer is not device memory");
+    DeviceGuard guard(dev);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    const hipError_t e = launch();
+    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string(launch_name) + " launch failed: " + hipGetErrorString(e));
+    return RTO_OK;
+}
 
 extern "C" {
 
@@ -249,10 +256,7 @@ int rto_ctx_create_batch(int width, int height, int frames, int device, rto_ctx*
         return set_err(RTO_E_INVALID, "rto_ctx_create_batch: frames must be in 1.." + std::to_string(rto::kMaxBatch));
     if ((int64_t)width * height * 32 > 0x7fffffffLL)
         return set_err(RTO_E_INVALID, "rto_ctx_create: width*height*32 exceeds the int range of idx*SPP (volrend.cu:157)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return set_err(RTO_E_HIP, "no HIP device available (librto has no CPU fallback)");
-    if (device < 0 || device >= ndev) return set_err(RTO_E_INVALID, "device index out of range");
+    if (const int rc = check_device_index(device, kNoDeviceMsg)) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
     auto c = new rto_ctx();
@@ -364,7 +368,7 @@ int rto_ctx_set_layers(rto_ctx* c, const float* depth, const float* color) {
                          {"color", (uintptr_t)color, (uintptr_t)color + px * 4 * sizeof(float)}};
     for (const Range& l : in) {
         if (!l.lo) continue;
-        if (device_of((const void*)l.lo) != c->device)
+        if (pointer_device((const void*)l.lo) != c->device)
             return set_err(RTO_E_INVALID, std::string("rto_ctx_set_layers: ") + l.what + " is not memory of the context's device");
         // (in-place use, the reference's surf_obj, is not offered: the batched path stores a pixel from another kernel than the
         //  one that would have to read it)
@@ -613,71 +617,38 @@ int rto_ctx_get_stats(rto_ctx* c, void* stream, uint64_t out[6], int reset) {
 
 int rto_filtering_batch(void* stream, const float* weight_map, const float* guidance_map, int L, int H, int W, int n,
                         const float* img_in, float* img_out) {
-    if (!weight_map || !guidance_map || !img_in || !img_out || H <= 0 || W <= 0 || n < 1)
-        return set_err(RTO_E_INVALID, "rto_filtering: null pointer or bad size");
-    if (L < 1 || L > 6)  // filtering.cu:362-366
-        return set_err(RTO_E_INVALID, "Kernel size == " + std::to_string(L * 2 + 1) + " not supported.");
-    if (img_in == img_out) return set_err(RTO_E_INVALID, "rto_filtering: img_in and img_out must differ");
-    const int pdev_ = device_of(img_out);
-    if (pdev_ < 0) return set_err(RTO_E_INVALID, "filtering: the output pointer is not device memory");
-    DeviceGuard guard(pdev_);
-    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
-    hipError_t e = rto::launch_filter(weight_map, guidance_map, L, H, W, n, img_in, img_out, (hipStream_t)stream);
-    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("filter launch failed: ") + hipGetErrorString(e));
-    return RTO_OK;
+    return rto_filtering_batch_mode(stream, weight_map, guidance_map, L, H, W, n, img_in, img_out, RTO_FILTER_EXACT);
 }
 
 int rto_filtering_batch_mode(void* stream, const float* weight_map, const float* guidance_map, int L, int H, int W, int n,
                              const float* img_in, float* img_out, int mode) {
-    if (mode == RTO_FILTER_EXACT) return rto_filtering_batch(stream, weight_map, guidance_map, L, H, W, n, img_in, img_out);
-    if (mode != RTO_FILTER_FACTORISED) return set_err(RTO_E_INVALID, "rto_filtering_batch_mode: unknown mode");
-    if (!weight_map || !guidance_map || !img_in || !img_out || H <= 0 || W <= 0 || n < 1)
-        return set_err(RTO_E_INVALID, "rto_filtering: null pointer or bad size");
-    if (L < 1 || L > 6) return set_err(RTO_E_INVALID, "Kernel size == " + std::to_string(L * 2 + 1) + " not supported.");
-    if (img_in == img_out) return set_err(RTO_E_INVALID, "rto_filtering: img_in and img_out must differ");
-    const int pdev_ = device_of(img_out);
-    if (pdev_ < 0) return set_err(RTO_E_INVALID, "filtering: the output pointer is not device memory");
-    DeviceGuard guard(pdev_);
-    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
-    hipError_t e = rto::launch_filter_fast(weight_map, guidance_map, L, H, W, n, img_in, img_out, (hipStream_t)stream);
-    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("filter launch failed: ") + hipGetErrorString(e));
-    return RTO_OK;
+    if (mode != RTO_FILTER_EXACT && mode != RTO_FILTER_FACTORISED) return set_err(RTO_E_INVALID, "rto_filtering_batch_mode: unknown mode");
+    return filter_call("rto_filtering", {weight_map, guidance_map, img_in, img_out}, L, H, W, n, img_in, img_out, img_out, "filter", [&] {
+        return (mode == RTO_FILTER_EXACT ? rto::launch_filter : rto::launch_filter_fast)(weight_map, guidance_map, L, H, W, n, img_in, img_out,
+                                                                                       (hipStream_t)stream);
+    });
 }
 
 int rto_filtering_train_forward(void* stream, const float* weight_map, const float* guidance_map, int L, int H, int W,
                                 int n, const float* img_in, float* img_out, float* rgb_filtered, float* max_map,
                                 float* inv_kernel_sum) {
-    if (!weight_map || !guidance_map || !img_in || !img_out || !rgb_filtered || !max_map || !inv_kernel_sum || H <= 0 ||
-        W <= 0 || n < 1)
-        return set_err(RTO_E_INVALID, "rto_filtering_train_forward: null pointer or bad size");
-    if (L < 1 || L > 6) return set_err(RTO_E_INVALID, "Kernel size == " + std::to_string(L * 2 + 1) + " not supported.");
-    if (img_in == img_out) return set_err(RTO_E_INVALID, "rto_filtering_train_forward: img_in and img_out must differ");
-    const int pdev_ = device_of(img_out);
-    if (pdev_ < 0) return set_err(RTO_E_INVALID, "filtering: the output pointer is not device memory");
-    DeviceGuard guard(pdev_);
-    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
-    hipError_t e = rto::launch_filter_train(weight_map, guidance_map, L, H, W, n, img_in, img_out, rgb_filtered, max_map,
-                                            inv_kernel_sum, (hipStream_t)stream);
-    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("filter launch failed: ") + hipGetErrorString(e));
-    return RTO_OK;
+    return filter_call("rto_filtering_train_forward", {weight_map, guidance_map, img_in, img_out, rgb_filtered, max_map, inv_kernel_sum}, L,
+                       H, W, n, img_in, img_out, img_out, "filter", [&] {
+                           return rto::launch_filter_train(weight_map, guidance_map, L, H, W, n, img_in, img_out, rgb_filtered, max_map,
+                                                           inv_kernel_sum, (hipStream_t)stream);
+                       });
 }
 
 int rto_filtering_backward(void* stream, const float* grad_output, const float* img_in, const float* weight_map,
                            const float* guidance_map, const float* rgb_filtered, const float* max_map,
                            const float* inv_kernel_sum, int L, int H, int W, int n, float* grad_weight,
                            float* grad_guidance) {
-    if (!grad_output || !img_in || !weight_map || !guidance_map || !rgb_filtered || !max_map || !inv_kernel_sum ||
-        !grad_weight || !grad_guidance || H <= 0 || W <= 0 || n < 1)
-        return set_err(RTO_E_INVALID, "rto_filtering_backward: null pointer or bad size");
-    if (L < 1 || L > 6) return set_err(RTO_E_INVALID, "Kernel size == " + std::to_string(L * 2 + 1) + " not supported.");
-    const int pdev_ = device_of(grad_guidance);
-    if (pdev_ < 0) return set_err(RTO_E_INVALID, "filtering: the output pointer is not device memory");
-    DeviceGuard guard(pdev_);
-    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
-    hipError_t e = rto::launch_filter_backward(grad_output, img_in, weight_map, guidance_map, rgb_filtered, max_map,
-                                               inv_kernel_sum, L, H, W, n, grad_weight, grad_guidance, (hipStream_t)stream);
-    if (e != hipSuccess) return set_err(RTO_E_HIP, std::string("filter backward launch failed: ") + hipGetErrorString(e));
-    return RTO_OK;
+    return filter_call("rto_filtering_backward",
+                       {grad_output, img_in, weight_map, guidance_map, rgb_filtered, max_map, inv_kernel_sum, grad_weight, grad_guidance}, L, H, W,
+                       n, nullptr, nullptr, grad_guidance, "filter backward", [&] {
+                           return rto::launch_filter_backward(grad_output, img_in, weight_map, guidance_map, rgb_filtered, max_map,
+                                                              inv_kernel_sum, L, H, W, n, grad_weight, grad_guidance, (hipStream_t)stream);
+                       });
 }
 
 int rto_filtering(void* stream, const float* weight_map, const float* guidance_map, int L, int H, int W,

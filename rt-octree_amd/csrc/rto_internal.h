@@ -1,5 +1,6 @@
-// rto_internal.h -- what the translation units behind the C ABI (rto_abi.cpp, rto_tree.cpp, rto_render_abi.cpp) share:
-// the two handle types, error plumbing and a few helpers.  Not installed; nothing here is an exported symbol.
+// rto_internal.h -- what the translation units of the render side of the C ABI (rto_abi.cpp, rto_tree.cpp, rto_render_abi.cpp,
+// rto_mesh.cpp) share: the two handle types and a few helpers, on top of rto_abi_common.h (error plumbing, device scope, shared
+// checks, scratch buffers).  Not installed; nothing here is an exported symbol.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,37 +13,13 @@
 #include <vector>
 
 #include "rto.h"
+#include "rto_abi_common.h"
 #include "rto_launch.h"
 
 #pragma GCC visibility push(hidden)
 
-// records msg as the calling thread's last error (rto_last_error; the string lives in rto_abi.cpp) and returns code
-int set_err(int code, const std::string& msg);
-
-#define HIP_TRY(expr)                                                                                        \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return set_err(RTO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + \
-                                          std::to_string(__LINE__) + ")");                                   \
-    } while (0)
-
-// set the device for the scope of one ABI call, restore the caller's device afterwards
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            ok = false;
-            return;
-        }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
+// check_device_index of the contexts and trees (the side handles say it without the parenthesis)
+constexpr const char* kNoDeviceMsg = "no HIP device available (librto has no CPU fallback)";
 constexpr int kKtRing = 256;
 constexpr int kProbeFloats = 128;  // >= 3 * RTO_BASIS_MAX: what the probe's disc reads of a leaf's data_dim - 1 coefficients
 #pragma GCC visibility pop

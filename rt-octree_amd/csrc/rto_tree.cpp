@@ -347,10 +347,8 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
     int rc = validate_upload(child, data, capacity, N, data_dim, fmt, quant, extra, extra_floats, out, &max_depth);
     if (rc != RTO_OK) return rc;
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return set_err(RTO_E_HIP, "no HIP device available (librto has no CPU fallback)");
-    if (device < 0 || device >= ndev) return set_err(RTO_E_INVALID, "device index out of range");
+    rc = check_device_index(device, kNoDeviceMsg);
+    if (rc != RTO_OK) return rc;
     DeviceGuard guard(device);
     if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
 

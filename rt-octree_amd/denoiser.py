@@ -202,31 +202,43 @@ class FusedGuidanceNet:
         self.packed_route = bool(info.packed_route)  # packed fp16 maps / sparse frames: the reference shape (32, 4, two layers) only
         self._out = {}
 
-    def __call__(self, aux, stream=None, squares_implied=False, cull=None, rgba=False):
-        """squares_implied: aux planes 4..7 are the fp32 squares of planes 0..3 (the renderer's aux buffer): the
-        kernel reads half the bytes, results are bit-identical.  cull = RenderContext.tile_marks() of the launch that
-        rendered aux: tiles whose inputs are all background get the background maps without being computed (same bits).
-        rgba: `aux` is the noisy image [n, H, W, 4] = (r, g, b, alpha) of a lean batched launch (RTO_NET_INPUT_RGBA)"""
-        from ._lib import check, lib
+    @staticmethod
+    def _frames(aux, rgba):
+        """(n, H, W) of the network's input: the aux planes [n, 8, H, W], or with rgba the noisy image [n, H, W, 4]"""
         if rgba:
             n, H, W, c = aux.shape
             assert c == 4 and aux.dtype == torch.float32 and aux.is_contiguous()
         else:
             n, c, H, W = aux.shape
             assert c == 8 and aux.dtype == torch.float32 and aux.is_contiguous()
-        key = (n, H, W)
-        if key not in self._out:
-            self._out[key] = (torch.empty((n, self.levels, H, W), device=self.device),
-                              torch.empty((n, self.levels, H, W), device=self.device))
-        wm, gm = self._out[key]
+        return n, H, W
+
+    def _launch_args(self, stream, cull, n, too_few):
+        """(stream pointer, marks, words per frame, background) of a call on n frames: `stream` or torch's current one, and
+        cull = RenderContext.tile_marks() taken apart (None: no marks); too_few: the ValueError for marks of fewer frames"""
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         marks, words, bg = (None, 0, 0.0)
         if cull is not None:
             marks, words, _slot0, frames, bg = cull
             if frames < n:
-                raise ValueError("GuidanceNet: %d frames but tile marks of %d" % (n, frames))
-        check(lib().rto_guidance_net_forward_culled(self._h, V._stream_ptr(s), aux.data_ptr(), n, H, W, wm.data_ptr(), gm.data_ptr(),
-                                                    2 if rgba else (1 if squares_implied else 0), marks, int(words), float(bg)))
+                raise ValueError(too_few % (n, frames))
+        return V._stream_ptr(s), marks, int(words), float(bg)
+
+    def __call__(self, aux, stream=None, squares_implied=False, cull=None, rgba=False):
+        """squares_implied: aux planes 4..7 are the fp32 squares of planes 0..3 (the renderer's aux buffer): the
+        kernel reads half the bytes, results are bit-identical.  cull = RenderContext.tile_marks() of the launch that
+        rendered aux: tiles whose inputs are all background get the background maps without being computed (same bits).
+        rgba: `aux` is the noisy image [n, H, W, 4] = (r, g, b, alpha) of a lean batched launch (RTO_NET_INPUT_RGBA)"""
+        from ._lib import check, lib
+        n, H, W = self._frames(aux, rgba)
+        key = (n, H, W)
+        if key not in self._out:
+            self._out[key] = (torch.empty((n, self.levels, H, W), device=self.device),
+                              torch.empty((n, self.levels, H, W), device=self.device))
+        wm, gm = self._out[key]
+        sp, marks, words, bg = self._launch_args(stream, cull, n, "GuidanceNet: %d frames but tile marks of %d")
+        check(lib().rto_guidance_net_forward_culled(self._h, sp, aux.data_ptr(), n, H, W, wm.data_ptr(), gm.data_ptr(),
+                                                    2 if rgba else (1 if squares_implied else 0), marks, words, bg))
         return wm, gm
 
     def denoise(self, ctx, n=1, mode=V.FILTER_FAST, stream=None):
@@ -241,15 +253,10 @@ class FusedGuidanceNet:
         """volrend.filtering on this network's fp32 maps [n, L, H, W], skipping the filter tiles that see only culled render
         tiles (cull = RenderContext.tile_marks(); rto_filtering_culled; same bits).  cull=None: volrend.filtering"""
         from ._lib import check, lib
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         n, L, H, W = (int(x) for x in guidance_map.shape)
-        marks, words, bg = (None, 0, 0.0)
-        if cull is not None:
-            marks, words, _slot0, frames, bg = cull
-            if frames < n:
-                raise ValueError("filter_planes: %d images but tile marks of %d frames" % (n, frames))
-        check(lib().rto_filtering_culled(self._h, V._stream_ptr(s), V._dev_ptr(weight_map), V._dev_ptr(guidance_map), H, W, n,
-                                         V._dev_ptr(img_in), V._dev_ptr(img_out), int(mode), marks, int(words), float(bg)))
+        sp, marks, words, bg = self._launch_args(stream, cull, n, "filter_planes: %d images but tile marks of %d frames")
+        check(lib().rto_filtering_culled(self._h, sp, V._dev_ptr(weight_map), V._dev_ptr(guidance_map), H, W, n,
+                                         V._dev_ptr(img_in), V._dev_ptr(img_out), int(mode), marks, words, bg))
 
     def reserve(self, n, H, W):
         """size the packed-map scratch up front (growing it later synchronises the device once)"""
@@ -264,21 +271,11 @@ class FusedGuidanceNet:
         sparse (with rgba and cull): ... of a SPARSE lean launch (RenderContext.set_lean_outputs(2)): pixels of unmarked tiles are
         taken as background, the skipped tiles' maps are not stored; filter_packed with the same marks completes the route"""
         from ._lib import check, lib
-        if rgba:
-            n, H, W, c = aux.shape
-            assert c == 4 and aux.dtype == torch.float32 and aux.is_contiguous()
-        else:
-            n, c, H, W = aux.shape
-            assert c == 8 and aux.dtype == torch.float32 and aux.is_contiguous()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        marks, words, bg = (None, 0, 0.0)
-        if cull is not None:
-            marks, words, _slot0, frames, bg = cull
-            if frames < n:
-                raise ValueError("forward_packed: %d frames but tile marks of %d" % (n, frames))
-        check(lib().rto_guidance_net_forward_packed_culled(self._h, V._stream_ptr(s), aux.data_ptr(), n, H, W,
+        n, H, W = self._frames(aux, rgba)
+        sp, marks, words, bg = self._launch_args(stream, cull, n, "forward_packed: %d frames but tile marks of %d")
+        check(lib().rto_guidance_net_forward_packed_culled(self._h, sp, aux.data_ptr(), n, H, W,
                                                            (2 if rgba else (1 if squares_implied else 0)) | (4 if sparse else 0),
-                                                           marks, int(words), float(bg)))
+                                                           marks, words, bg))
         self._packed_shape = (n, H, W)
 
     def filter_packed(self, img_in, img_out, stream=None, shape=None, cull=None):
@@ -287,16 +284,10 @@ class FusedGuidanceNet:
         cull = RenderContext.tile_marks() of the launch that rendered img_in (images = the marks' frames, in order): tiles
         that see only background are copied, not filtered (rto_filtering_packed_culled; same bits)"""
         from ._lib import check, lib
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         n, H, W = shape if shape is not None else self._packed_shape
-        if cull is None:
-            check(lib().rto_filtering_packed(self._h, V._stream_ptr(s), V._dev_ptr(img_in), V._dev_ptr(img_out), int(n), int(H), int(W)))
-            return
-        marks, words, _slot0, frames, bg = cull
-        if frames < n:
-            raise ValueError("filter_packed: %d images but tile marks of %d frames" % (n, frames))
-        check(lib().rto_filtering_packed_culled(self._h, V._stream_ptr(s), V._dev_ptr(img_in), V._dev_ptr(img_out), int(n), int(H), int(W),
-                                                marks, int(words), float(bg)))
+        sp, marks, words, bg = self._launch_args(stream, cull, n, "filter_packed: %d images but tile marks of %d frames")
+        # (without marks this is rto_filtering_packed)
+        check(lib().rto_filtering_packed_culled(self._h, sp, V._dev_ptr(img_in), V._dev_ptr(img_out), int(n), int(H), int(W), marks, words, bg))
 
     def __del__(self):
         try:

@@ -8,16 +8,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import RtoError, check, lib
+from .volrend import _stream_ptr
 
 IMAGE_RGBA32F, IMAGE_RGBA8 = 0, 1  # RTO_IMAGE_*
 TRUTH_OVER_BACKGROUND = 1  # RTO_METRICS_TRUTH_OVER_BACKGROUND
 
 FrameMetrics = collections.namedtuple("FrameMetrics", ["mse", "psnr", "smape", "ssim"])
-
-
-def _stream_ptr(stream):
-    from .volrend import _stream_ptr as sp
-    return sp(stream)
 
 
 def _describe(t, name):
