@@ -175,7 +175,7 @@ struct FilterCull {
     uint4 fill_maps;
 };
 
-constexpr int kMapHalo = 2;  // a GuidanceNet map value depends on the 5x5 aux pixels around it (two 3x3 convolutions)
+constexpr int kMapHalo = kNetHalo;  // a GuidanceNet map value depends on the 5x5 aux pixels around it (two 3x3 convolutions)
 
 // A workgroup whose staged region (outputs + halo, RW x RH pixels from (rx0, ry0)), grown by the network's receptive field,
 // lies inside the image and inside culled render tiles reads nothing but background pixels and the network's background
@@ -528,17 +528,17 @@ __global__ void __launch_bounds__(256, (PACKED || L <= 4) ? RTO_FAST_WGS : 3) fi
                 for (int r = 0; r < kFastRows; ++r)
                     img_out[(int64_t)(py0 + r) * W + (tx_first + ts) * kFastW + lx] = cull.fill[(ry * kFastRows + r) * kFastW + lx];
             }
-        // sparse frames: guidance_fused's decision to skip a 32 x 8 output tile (its 36 x 12 input region inside the image and in
-        // unmarked render tiles -- guidance_kernels.hip `skip_tiles`), restated for the network tile (ntx0 + (lane & 7), nty0 + (lane >> 3)) -- bit
+        // sparse frames: guidance_fused's decision to skip a kNetTileW x kNetTileH output tile (its kNetInW x kNetInH input region inside
+        // the image and in unmarked render tiles -- guidance_strip.inc strip_marks), restated for the network tile (ntx0 + (lane & 7), nty0 + (lane >> 3)) -- bit
         // lane of `nskip`; the staged region spans at most strip + 2 <= 7 columns and 4 rows of them
         if (PACKED && cull.sparse) {
             const int c = ln & 7, r = (ln >> 3) & 3, ntx = ntx0 + c, nty = nty0 + r;
-            const int nx0 = ntx * 32 - 2, ny0 = nty * 8 - 2;
+            const int nx0 = ntx * kNetTileW - kNetHalo, ny0 = nty * kNetTileH - kNetHalo;
             // (its render-tile rows nty - 1 .. nty + 1 are rows r .. r + 2 of the bitmap, its columns 4 ntx - 1 .. 4 ntx + 4 bits 4 c ..)
             const uint32_t m0 = rm[0] | rm[1] | rm[2], m1 = rm[1] | rm[2] | rm[3], m2 = rm[2] | rm[3] | rm[4], m3 = rm[3] | rm[4] | rm[5];
             const uint32_t m = r == 0 ? m0 : r == 1 ? m1 : r == 2 ? m2 : m3;
-            const bool sk = ln < 32 && c <= kFastStrip + 1 && ntx >= 0 && nty >= 0 && ntx * 32 < W && nty * 8 < H && nx0 >= 0 && ny0 >= 0 &&
-                            nx0 + 36 <= W && ny0 + 12 <= H && ((m >> (4 * c)) & 0x3fu) == 0u;
+            const bool sk = ln < 32 && c <= kFastStrip + 1 && ntx >= 0 && nty >= 0 && ntx * kNetTileW < W && nty * kNetTileH < H && nx0 >= 0 && ny0 >= 0 &&
+                            nx0 + kNetInW <= W && ny0 + kNetInH <= H && ((m >> (4 * c)) & 0x3fu) == 0u;
             nskip = (uint32_t)__builtin_amdgcn_ballot_w64(sk);
         }
     }

@@ -1,5 +1,6 @@
 // guidance_general.inc -- the fused GuidanceNet for every other trained shape (included by guidance_kernels.hip, inside
-// namespace rto { namespace { ).
+// namespace rto { namespace { , after guidance_strip.inc: the strip frame -- constants, NetCull, marks, skipped-tile fill,
+// stage A -- is that file's, with halo NL and without the sparse substitution).
 //
 // guidance_fused<32, 4> above is tuned for the reference configuration: both weight sets live in registers, the second layer
 // shares activation rows between output rows, the maps can leave packed.  None of that survives C1 = 64 (288 weight registers)
@@ -19,17 +20,11 @@
 //     the softmax over `levels` logits -- which lie in two MFMA lane groups for levels > 4 -- needs no cross-lane exchange
 //   * LDS is dynamic: C1P = 64 with three layers needs 128 KB (one workgroup per CU), see DESIGN.md "General GuidanceNet shapes"
 
-struct NetCullG {
-    const uint32_t* mask;
-    int mask_words, tiles_x;
-    float planes[12];  // background maps: 6 softmax weights, 6 guidance values (the first `levels` of each)
-};
-
 template <int C1P>
 struct GenShape {
     static_assert(C1P == 16 || C1P == 32 || C1P == 64, "mid channels are padded to 16, 32 or 64");
     static constexpr int KS = C1P == 16 ? 5 : 9 * C1P / 32;  // k-steps of a C1P-input layer (C1P = 16: tap pairs, the tenth half-step zero)
-    static constexpr int AS = C1P + 8;                       // activation pixel stride in halves (see RTO_NET_PAD above)
+    static constexpr int AS = C1P + kActPad;                 // activation pixel stride in halves
 };
 
 constexpr int gen_region(int NL, int l) { return (kGW + 2 * (NL - l)) * (kGH + 2 * (NL - l)); }  // pixels of layer l's output region
@@ -160,7 +155,7 @@ __global__ void __launch_bounds__(256) guidance_general(const float* __restrict_
                                                         const float* __restrict__ bl,    // [16]
                                                         float* __restrict__ weight_out,   // [n][L][H][W]
                                                         float* __restrict__ guidance_out, // [n][L][H][W]
-                                                        int H, int W, int L, const NetCullG cull, const int strip) {
+                                                        int H, int W, int L, const NetCull cull, const int strip) {
     static_assert(NL == 2 || NL == 3, "two or three layers");
     constexpr int IW = kGW + 2 * NL, IH = kGH + 2 * NL;              // input tile with halo NL
     constexpr int AW = kGW + 2 * (NL - 1), AH = kGH + 2 * (NL - 1);  // layer-1 output region
@@ -180,107 +175,29 @@ __global__ void __launch_bounds__(256) guidance_general(const float* __restrict_
     const int tx_first = blockIdx.x * strip;
     const int y0 = blockIdx.y * kGH;
     const int64_t HW = (int64_t)H * W;
-    constexpr bool SQ = IN != 0;
     aux += (int64_t)blockIdx.z * (IN == 2 ? 4 : kCIn) * HW;
     weight_out += (int64_t)blockIdx.z * L * HW;
     guidance_out += (int64_t)blockIdx.z * L * HW;
     const int col = lane & 15, kg = lane >> 4;
 
-    // Tile skipping as in guidance_fused: 3 rows x 64 columns of render-tile marks from ((y0 - NL) >> 3, 4 tx_first - 1) cover the
-    // input regions (IW x IH <= 38 x 14: 6 columns from bit 4 ts, 3 rows) of a strip; a tile whose input region lies inside the
-    // image and in unmarked render tiles is filled with the background maps.
-    uint32_t skip_tiles = 0;
-    constexpr int RX = (IW + 7) / 8 + 1, RY = (IH + 7) / 8 + 1;
-    static_assert(RX == 6 && RY == 3 && 4 * (kStrip - 1) + RX <= 64 && NL <= 8, "64 columns x 3 rows of render tiles cover a strip's input regions");
-    if (cull.mask) {
-        const uint32_t* const fm = cull.mask + (size_t)blockIdx.z * cull.mask_words;
-        const uint32_t keep_all = fm[cull.mask_words - 1] & 1u;
-        uint32_t word[RY];
-        bool inside[RY];
-#pragma unroll
-        for (int r = 0; r < RY; ++r) {
-            const int tx = 4 * tx_first - 1 + lane, ty = ((y0 - NL) >> 3) + r;
-            inside[r] = tx >= 0 && ty >= 0 && tx < cull.tiles_x && ty * 8 < H;
-            const uint32_t t = inside[r] ? (uint32_t)(ty * cull.tiles_x + tx) : 0u;
-            word[r] = fm[t >> 5] >> (t & 31u);
-        }
-        unsigned long long any_row = 0ull;
-#pragma unroll
-        for (int r = 0; r < RY; ++r) any_row |= __builtin_amdgcn_ballot_w64(inside[r] && ((word[r] | keep_all) & 1u) != 0u);
-        for (int ts = 0; ts < strip && tx_first + ts < tiles_x; ++ts) {
-            const int x0 = (tx_first + ts) * kGW - NL, ry0 = y0 - NL;
-            // (outside the image the zero padding is not background: computed)
-            if (x0 >= 0 && ry0 >= 0 && x0 + IW <= W && ry0 + IH <= H && ((any_row >> (4 * ts)) & 0x3full) == 0ull) skip_tiles |= 1u << ts;
-        }
-    }
-    auto next_live = [&](int ts) {  // first tile >= ts of the strip that has to be computed (kStrip: none)
-        while (ts < strip && tx_first + ts < tiles_x && ((skip_tiles >> ts) & 1u)) ++ts;
-        return (ts < strip && tx_first + ts < tiles_x) ? ts : kStrip;
-    };
-    if (cull.mask) {  // the skipped tiles first (interior tiles: every pixel of them is inside the image)
-        for (int ts = 0; ts < strip && tx_first + ts < tiles_x; ++ts)
-            if ((skip_tiles >> ts) & 1u) {
-                const int64_t pix = (int64_t)(y0 + (tid >> 5)) * W + (tx_first + ts) * kGW + (tid & 31);
-#pragma unroll
-                for (int l = 0; l < 6; ++l)
-                    if (l < L) {
-                        weight_out[l * HW + pix] = cull.planes[l];
-                        guidance_out[l * HW + pix] = cull.planes[6 + l];
-                    }
-            }
-    }
+    // Tile skipping as in guidance_fused, with halo NL (guidance_strip.inc): a tile whose input region lies inside the image and
+    // in unmarked render tiles is filled with the background maps.
+    unsigned long long rmk[3];
+    const uint32_t skip_tiles = strip_marks<NL>(cull, rmk, lane, tx_first, y0, strip, tiles_x, H, W);
+    if (cull.mask) fill_skipped_planes(cull, skip_tiles, weight_out, guidance_out, L, HW, W, tid, tx_first, y0, strip, tiles_x);
 
-    // ---- stage A: input tile, planar fp32 -> HWC fp16; the next computed tile's loads are issued before this tile's layers
-    constexpr int NPIX = IH * IW, NIT = (NPIX + 255) / 256;
-    constexpr int NLD = SQ ? kCIn / 2 : kCIn;  // planes actually read
-    float v[NIT][NLD];
-    auto fetch = [&](int x0) {
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int e = tid + it * 256;
-            const int ty = e / IW, tx = e - ty * IW;
-            const int gx = x0 - NL + tx, gy = y0 - NL + ty;
-            const bool in = e < NPIX && gx >= 0 && gx < W && gy >= 0 && gy < H;
-            const int gi = in ? gy * W + gx : 0;  // (8 * H * W < 2^31: rto_ctx_create's size check)
-            if constexpr (IN == 2) {
-                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (in) t = reinterpret_cast<const float4*>(aux)[gi];
-                v[it][0] = t.x;
-                v[it][1] = t.y;
-                v[it][2] = t.z;
-                v[it][3] = t.w;
-            } else {
-#pragma unroll
-                for (int c = 0; c < NLD; ++c) {
-                    const float t = aux[c * (int)HW + gi];
-                    v[it][c] = in ? t : 0.f;
-                }
-            }
-        }
-    };
-    int ts_live = next_live(0);
-    if (ts_live < kStrip) fetch((tx_first + ts_live) * kGW);
+    // ---- stage A (guidance_strip.inc); the next computed tile's loads are issued before this tile's layers
+    float v[kStageIters<NL>][kStagePlanes<IN>];
+    int ts_live = next_live(skip_tiles, 0, strip, tx_first, tiles_x);
+    if (ts_live < kStrip) fetch<NL, IN, false>(v, aux, cull, rmk, tx_first, ts_live, y0, H, W, HW, tid);
 
 #pragma nounroll
     while (ts_live < kStrip) {  // (workgroup-uniform)
         const int x0 = (tx_first + ts_live) * kGW;
-        ts_live = next_live(ts_live + 1);
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int e = tid + it * 256;
-            if (e < NPIX) {
-                half8 h;
-#pragma unroll
-                for (int c = 0; c < NLD; ++c) h[c] = (_Float16)v[it][c];
-                if (SQ) {
-#pragma unroll
-                    for (int c = 0; c < kCIn / 2; ++c) h[kCIn / 2 + c] = (_Float16)(v[it][c] * v[it][c]);
-                }
-                *reinterpret_cast<half8*>(s_in + (size_t)e * kCIn) = h;
-            }
-        }
+        ts_live = next_live(skip_tiles, ts_live + 1, strip, tx_first, tiles_x);
+        stage<NL, IN>(v, s_in, tid);
         __syncthreads();  // s_in complete; every thread is also done with the previous tile's s_out
-        if (ts_live < kStrip) fetch((tx_first + ts_live) * kGW);
+        if (ts_live < kStrip) fetch<NL, IN, false>(v, aux, cull, rmk, tx_first, ts_live, y0, H, W, HW, tid);
 
         // ---- layer 1: s_in -> s_a (halo NL - 1)
         conv_layer<8, NT1, 3, IW, kCIn, AW, AH, AS, true>(s_in, s_a, w1, nullptr, s_pad, x0 - (NL - 1), y0 - (NL - 1), H, W, wave, col, kg);
@@ -329,7 +246,7 @@ __global__ void __launch_bounds__(256) guidance_general(const float* __restrict_
 
 template <int C1P, int NL, int IN>
 hipError_t launch_general_one(dim3 grid, hipStream_t stream, const float* aux, const void* w1, const void* wm, const void* wl, const float* bm,
-                              const float* bl, float* weight_out, float* guidance_out, int H, int W, int L, const NetCullG& cull, int strip) {
+                              const float* bl, float* weight_out, float* guidance_out, int H, int W, int L, const NetCull& cull, int strip) {
     constexpr size_t lds = (size_t)gen_lds_halves<C1P, NL>() * sizeof(_Float16);
     static_assert(lds <= 160 * 1024, "the CU has 160 KB of LDS");
     if (lds > 64 * 1024) {  // beyond the default dynamic-LDS window: ask for it

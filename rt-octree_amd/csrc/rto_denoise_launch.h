@@ -46,6 +46,12 @@ hipError_t launch_filter_backward(const float* grad_out, const float* img_in, co
                                   const float* rgb_filtered, const float* max_map, const float* inv_kernel_sum, int L,
                                   int H, int W, int n, float* grad_weight, float* grad_guidance, hipStream_t stream);
 
+// Tile geometry of the reference GuidanceNet's kernel (guidance_fused): a workgroup step produces kNetTileW x kNetTileH map
+// values, each of which depends on the aux pixels within kNetHalo of it (two 3x3 convolutions), so a tile reads a kNetInW x
+// kNetInH region.  filter_fast restates that kernel's skip rule for sparse frames in these names.
+constexpr int kNetTileW = 32, kNetTileH = 8, kNetHalo = 2;
+constexpr int kNetInW = kNetTileW + 2 * kNetHalo, kNetInH = kNetTileH + 2 * kNetHalo;
+
 // fused compact GuidanceNet (guidance_kernels.hip): w1 fp16 [c1][96], w2 fp16 [16][9*c1], b2 [16];
 // guidance_out == nullptr: weight_out receives the packed fp16 maps [n][H][W][8] instead
 // sparse (round 6; in_mode 2, packed, tile_mask given): input pixels of unmarked render tiles are taken as (background x 3, 0)

@@ -131,6 +131,38 @@ def test_the_layer_pass_kernels_keep_their_registers_and_no_private_segment():
             assert k["vgprs"] <= vgprs and k["occupancy"] >= waves, (name, k)
 
 
+FUSED_BOUNDS = {(2, True): (128, 4), (1, True): (126, 4), (0, True): (134, 3),  # (IN, PACK): (VGPRs at most, waves per SIMD at least)
+                (2, False): (128, 4), (1, False): (124, 4), (0, False): (132, 3)}
+GENERAL_WAVES = {(16, 2, 0): 3, (16, 2, 1): 4, (16, 2, 2): 3, (16, 3, 0): 2, (16, 3, 1): 2, (16, 3, 2): 2,  # (C1P, NL, IN): waves per SIMD
+                 (32, 2, 0): 2, (32, 2, 1): 2, (32, 2, 2): 2, (32, 3, 0): 1, (32, 3, 1): 1, (32, 3, 2): 1,
+                 (64, 2, 0): 1, (64, 2, 1): 1, (64, 2, 2): 1, (64, 3, 0): 1, (64, 3, 1): 1, (64, 3, 2): 1}
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
+def test_the_guidance_kernels_keep_their_registers_on_the_shared_strip_frame():
+    """the strip frame both GuidanceNet kernels are built from (csrc/guidance_strip.inc: __forceinline__ templates taking the
+    staging registers and the mark rows by reference) costs neither kernel a private segment, a register or a wave: bounds =
+    the figures of the commit before the frame was shared, when each kernel carried its own copy, from the remarks of
+        hipcc --offload-arch=gfx950 -std=c++17 -O3 -ffp-contract=off -fno-fast-math -Iinclude -Irt-octree_amd/csrc -S
+              --cuda-device-only -Rpass-analysis=kernel-resource-usage rt-octree_amd/csrc/guidance_kernels.hip
+    (the Makefile adds no per-source flag).  The general kernel must not gain the sparse route's registers: its occupancy per
+    instantiation is that commit's."""
+    res = kernel_resources("guidance_kernels.hip", min_kernels=24)
+
+    def one(prefix):
+        found = [v for n, v in res.items() if n.startswith("_ZN3rto12_GLOBAL__N_1" + prefix)]  # (the argument types are not pinned)
+        assert len(found) == 1, (prefix, sorted(res))
+        return found[0]
+    assert not [(n, k) for n, k in res.items() if k["scratch"] != 0]
+    for (mode, pack), (vgprs, waves) in FUSED_BOUNDS.items():
+        k = one("14guidance_fusedILi32ELi4ELi%dELb%dEEE" % (mode, pack))
+        assert k["scratch"] == 0 and k["vgprs"] <= vgprs and k["occupancy"] >= waves, (mode, pack, k)
+    for (c1p, layers, mode), waves in GENERAL_WAVES.items():
+        k = one("16guidance_generalILi%dELi%dELi%dEEE" % (c1p, layers, mode))
+        assert k["scratch"] == 0 and k["occupancy"] >= waves, (c1p, layers, mode, k)
+    assert len(res) == len(FUSED_BOUNDS) + len(GENERAL_WAVES)
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 def test_the_valu_probe_loops_hold_exactly_the_instructions_they_claim(tmp_path):
     """tools/probe_valu.py divides instruction counts by clocks: the count must be what the code object holds.  Every
