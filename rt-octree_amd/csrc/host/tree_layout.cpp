@@ -74,14 +74,13 @@ bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3],
             if (!emit) continue;
             const double size = std::ldexp(1.0, -ls);
             const uint32_t q[3] = {cx[(size_t)n] * 2 + ((s >> 2) & 1), cy[(size_t)n] * 2 + ((s >> 1) & 1), cz[(size_t)n] * 2 + (s & 1)};
-            double r2 = 0;
             for (int i = 0; i < 3; ++i) {
                 const double ct = (q[i] + 0.5) * size;
                 out.push_back((float)((ct - offset[i]) / scale[i]));
-                const double hw = (0.5 * size + margin) / std::fabs((double)scale[i]);
-                r2 += hw * hw;
             }
-            out.push_back((float)(std::sqrt(r2) * 1.001));
+            // the padded half-edge in TREE units (a power of two + the margin: exact to 1e-10 as a float); the kernel divides
+            // by |TreeDev::scale| per axis for the world half-widths of the box
+            out.push_back((float)(0.5 * size + margin));
         }
     }
     return true;

@@ -18,8 +18,9 @@ namespace rto {
 float half_to_float(uint16_t h);
 
 // The culling cells of a tree (TreeDev::occ_cells): cubes of size >= 2^-kOccLevel that together contain every leaf of positive
-// density, as world-space bounding spheres.  Returns false when the node order does not allow the single top-down pass (a
-// child stored before its parent: cannot happen after the breadth-first relayout).
+// density, four floats each: the centre in WORLD coordinates and the half-edge, margin included, in TREE units (the box is
+// axis-aligned in both; its world half-widths are half-edge / |scale|).  Returns false when the node order does not allow
+// the single top-down pass (a child stored before its parent: cannot happen after the breadth-first relayout).
 bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3], const float offset[3], const uint16_t* sigma,
                    size_t stride, std::vector<float>& out);
 

@@ -253,22 +253,38 @@ __global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_
 // A ray that never meets a leaf of positive density composites nothing: its pixel is the background, its hit list empty
 // (rt_core.cuh:252-262 only ever accumulates in leaves with sigma > sigma_thresh).  73 % of the bench scene's rays are such
 // rays and a third of all march steps are theirs.  mark_tiles_kernel decides it per 8x8-pixel tile, conservatively and
-// without marching: every culling cell of the tree (TreeDev::occ_cells: world-space bounding spheres of the cubes that hold
-// the leaves of positive density, radius padded far above the float error of a sample point) is projected into every
-// frame of the batch; the tiles its projection can touch are marked.  An unmarked tile holds no ray that passes within a
-// sphere, hence no ray that visits a dense leaf: its rays are never queued, its pixels get no threshold draws.  The bound:
-// with the cell centre at camera coordinates (a, b, -d), d > 2 r, every point of the sphere lands within
-// f r / (d - r) (1 + |a| / d) pixels of the centre's pixel along x (same with b along y) -- from
-// |a'/d' - a/d| <= (r d + |a| r) / (d (d - r)).  A sphere nearer than that marks the whole frame; one behind the
-// camera nothing.  (Pixels are bit-identical with and without: tests/test_culling.py, and every parity test against the
-// oracle, which marches every ray, runs with it.)
+// without marching: every culling cell of the tree (TreeDev::occ_cells: the cubes that hold the leaves of positive density,
+// as world-space boxes padded far above the float error of a sample point) is projected into every frame of the batch; the
+// tiles its projection can touch are marked.  An unmarked tile holds no ray that passes through a box, hence no ray that
+// visits a dense leaf: its rays are never queued, its pixels get no threshold draws.
+// The ball bound (rounds 3-6 applied it to the box's bounding sphere): with a ball's centre at camera coordinates (a, b, -d),
+// d > 2 r, every point of the ball lands within f r / (d - r) (1 + |a| / d) pixels of the centre's pixel along x (same with b
+// along y) -- from |a'/d' - a/d| <= (r d + |a| r) / (d (d - r)).
+// The box rule: a box whose 8 corners all lie in front of the camera is convex and in front of it, so its projection lies
+// in the hull of the projected corners, hence in their bounding rectangle; the tiles of that rectangle are marked.  The
+// corners are centre +- hw[i] e_i through the same Cramer inverse (M need not be orthonormal, nor the tree's scale isotropic).
+// Two pads:
+//   * relative: a corner is taken as a ball of radius e = 1e-5 (|p|_1 |M^-1|_F + r) around its computed position and the ball
+//     bound widens the rectangle by it.  The float error of p, of Cramer's sums and of the corner offsets is a few ulp of
+//     those magnitudes (~1e-6 of them for a camera matrix that is not close to singular); e is 10 times that.  The
+//     rectangle is used only while every corner's depth exceeds 100 e (the ball bound needs > 2 e; the rest keeps 1 / depth tame).
+//   * absolute, 1.5 pixels, as before: the ray of pixel x leaves through image-plane point (x - W / 2) / fx exactly, so the
+//     pad is pure slack for the float error of the pixel coordinates here (0.5 W + fx x: ~1e-4 pixel) and of the ray's own
+//     direction (ray_setup: the same size).
+// A box with a corner nearer than that marks the whole frame; one with every corner behind the camera nothing.
+// The sphere rule stays as an upper clamp: where it yields a rectangle the tiles are the intersection of the two (each is a
+// bound by itself, and a box lies inside its bounding sphere: in exact arithmetic the box rectangle is the smaller one
+// already -- |M^-1|_F alone overstates an orthonormal camera's sphere by sqrt 3), where it marks nothing so does this, so
+// the marks are a subset of rounds 3-6's for every cell and camera whatever the rounding.  (Pixels are bit-identical with
+// and without: tests/test_culling.py, tests/test_culling_cubes.py, and every parity test against the oracle, which marches
+// every ray, runs with it.)
 // One workgroup = kMarkCells cells of one frame, marked into a private copy of the frame's mask in LDS (LDS_MASK; a frame
 // of more than kMarkLdsWords * 32 tiles marks straight into memory) that is OR-ed into the frame's mask once at the end:
 // tens of thousands of cells land on a few hundred mask words, and device-scope atomics on one address serialise
 // (the first version, one global atomic per cell and tile, took 2.5 ms per 100 frames; this one 0.1).
 constexpr int kMarkCells = 2048, kMarkLdsWords = 8192;
 template <class MarkFn>
-RTO_DEV void mark_cell(const float4 cell, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark);
+RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark);
 template <bool LDS_MASK>
 __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, const FrameBatch fb, uint32_t* __restrict__ mask) {
     extern __shared__ uint32_t s_mask[];
@@ -286,9 +302,9 @@ __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, con
         const int c = (int)blockIdx.x * kMarkCells + (int)threadIdx.x * (kMarkCells / 256) + i;
         if (c >= tree.n_occ_cells) break;
         if (LDS_MASK)
-            mark_cell(tree.occ_cells[c], fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });  // ds_or_b32
+            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });  // ds_or_b32
         else
-            mark_cell(tree.occ_cells[c], fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(gm + w, bits); });
+            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(gm + w, bits); });
     }
     if (LDS_MASK) {
         __syncthreads();
@@ -298,7 +314,7 @@ __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, con
 }
 
 template <class MarkFn>
-RTO_DEV void mark_cell(const float4 cell, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark) {
+RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark) {
     {
     const float* m = fd.transform;  // columns 0..2: camera axes, column 3: centre (common.cuh:29-44)
     const float p[3] = {cell.x - m[9], cell.y - m[10], cell.z - m[11]};
@@ -314,20 +330,59 @@ RTO_DEV void mark_cell(const float4 cell, const FrameDesc& fd, const FrameBatch&
     // |M^-1| <= its Frobenius norm: the sphere's radius in camera coordinates
     const float frob = sqrtf(c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2] + c20[0] * c20[0] + c20[1] * c20[1] + c20[2] * c20[2] +
                              c01[0] * c01[0] + c01[1] * c01[1] + c01[2] * c01[2]) * fabsf(inv);
-    const float r = cell.w * frob * 1.0001f;
+    // world half-widths of the box, and the radius of its bounding sphere (0.1 % above the half diagonal)
+    const float hw[3] = {cell.w / fabsf(tree.scale[0]), cell.w / fabsf(tree.scale[1]), cell.w / fabsf(tree.scale[2])};
+    const float r = sqrtf(hw[0] * hw[0] + hw[1] * hw[1] + hw[2] * hw[2]) * 1.001f * frob * 1.0001f;
     if (d <= -r) return;    // wholly behind the camera (a NaN pose falls through to "keep everything")
-    if (!(d > 2.f * r)) {   // too close for the bound: keep every tile of this frame
+    const float fx = fabsf(fd.fx), fy = fabsf(fd.fy);
+    // ---- the sphere rule (rounds 3-6): a rectangle while d > 2 r, else every tile.  Kept as an upper clamp of the box rule.
+    const bool sphere = d > 2.f * r;
+    float x0f = 0.f, x1f = 0.f, y0f = 0.f, y1f = 0.f;
+    if (sphere) {
+        const float xs = a / d, ys = b / d;
+        const float k = r / (d - r);
+        const float pxc = 0.5f * fb.width + fd.fx * xs, pyc = 0.5f * fb.height - fd.fy * ys;  // volrend.cu:139-141 inverted
+        const float rx = fx * k * (1.f + fabsf(xs)) + 1.5f, ry = fy * k * (1.f + fabsf(ys)) + 1.5f;
+        x0f = floorf((pxc - rx) * 0.125f), x1f = floorf((pxc + rx) * 0.125f);
+        y0f = floorf((pyc - ry) * 0.125f), y1f = floorf((pyc + ry) * 0.125f);
+    }
+    // ---- the box rule: the 8 corners centre +- hw[i] e_i in camera coordinates, each taken as a ball of radius e
+    const float ua[3] = {hw[0] * c12[0] * inv, hw[1] * c12[1] * inv, hw[2] * c12[2] * inv};   // M^-1 (hw[i] e_i): its a,
+    const float ub[3] = {hw[0] * c20[0] * inv, hw[1] * c20[1] * inv, hw[2] * c20[2] * inv};   // b
+    const float ud[3] = {-hw[0] * c01[0] * inv, -hw[1] * c01[1] * inv, -hw[2] * c01[2] * inv};  // and depth component
+    const float e = 1e-5f * ((fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2])) * frob + r);
+    const float dmin = 100.f * e;
+    bool front = true, behind = true;
+    float xlo = 3e38f, xhi = -3e38f, ylo = 3e38f, yhi = -3e38f;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const float sx = (s & 4) ? 1.f : -1.f, sy = (s & 2) ? 1.f : -1.f, sz = (s & 1) ? 1.f : -1.f;
+        const float A = a + sx * ua[0] + sy * ua[1] + sz * ua[2];
+        const float B = b + sx * ub[0] + sy * ub[1] + sz * ub[2];
+        const float D = d + sx * ud[0] + sy * ud[1] + sz * ud[2];
+        const float x = A / D, y = B / D, k = e / (D - e);
+        const float kx = k * (1.f + fabsf(x)), ky = k * (1.f + fabsf(y));
+        front = front && D > dmin && fabsf(x) + fabsf(y) < 3e38f;  // (false for a NaN anywhere)
+        behind = behind && D < -e;
+        xlo = fminf(xlo, x - kx), xhi = fmaxf(xhi, x + kx);
+        ylo = fminf(ylo, y - ky), yhi = fmaxf(yhi, y + ky);
+    }
+    if (behind) return;  // every corner behind the camera: so is the box
+    const float px0 = 0.5f * fb.width + fd.fx * xlo, px1 = 0.5f * fb.width + fd.fx * xhi;    // (fx, fy may be negative)
+    const float py0 = 0.5f * fb.height - fd.fy * ylo, py1 = 0.5f * fb.height - fd.fy * yhi;
+    const bool box = front && fabsf(px0) + fabsf(px1) + fabsf(py0) + fabsf(py1) < 3e38f;
+    if (!box && !sphere) {  // a corner too close to the camera plane (or a NaN pose): keep every tile of this frame
         mark((uint32_t)fb.mask_words - 1u, 1u);
         return;
     }
-    const float xs = a / d, ys = b / d;
-    const float k = r / (d - r);
-    const float fx = fabsf(fd.fx), fy = fabsf(fd.fy);
-    const float pxc = 0.5f * fb.width + fd.fx * xs, pyc = 0.5f * fb.height - fd.fy * ys;  // volrend.cu:139-141 inverted
-    const float rx = fx * k * (1.f + fabsf(xs)) + 1.5f, ry = fy * k * (1.f + fabsf(ys)) + 1.5f;
+    if (box) {
+        const float bx0 = floorf((fminf(px0, px1) - 1.5f) * 0.125f), bx1 = floorf((fmaxf(px0, px1) + 1.5f) * 0.125f);
+        const float by0 = floorf((fminf(py0, py1) - 1.5f) * 0.125f), by1 = floorf((fmaxf(py0, py1) + 1.5f) * 0.125f);
+        // with both rules in hand the tiles are the intersection of the two rectangles (each alone is a valid bound)
+        x0f = sphere ? fmaxf(x0f, bx0) : bx0, x1f = sphere ? fminf(x1f, bx1) : bx1;
+        y0f = sphere ? fmaxf(y0f, by0) : by0, y1f = sphere ? fminf(y1f, by1) : by1;
+    }
     const int tiles_x = (fb.width + 7) >> 3, tiles_y = (fb.height + 7) >> 3;
-    const float x0f = floorf((pxc - rx) * 0.125f), x1f = floorf((pxc + rx) * 0.125f);
-    const float y0f = floorf((pyc - ry) * 0.125f), y1f = floorf((pyc + ry) * 0.125f);
     if (!(x1f >= 0.f && y1f >= 0.f && x0f < (float)tiles_x && y0f < (float)tiles_y)) {
         if (!(x0f == x0f && y0f == y0f)) mark((uint32_t)fb.mask_words - 1u, 1u);  // NaN: keep everything
         return;
@@ -360,9 +415,9 @@ __global__ void __launch_bounds__(256) mark_tiles_one_kernel(const TreeDev tree,
         const int c = (int)blockIdx.x * kMarkCells + (int)threadIdx.x * (kMarkCells / 256) + i;
         if (c >= tree.n_occ_cells) break;
         if (lds)
-            mark_cell(tree.occ_cells[c], fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });
+            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });
         else
-            mark_cell(tree.occ_cells[c], fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(mask + w, bits); });
+            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(mask + w, bits); });
     }
     if (lds) {
         __syncthreads();

@@ -76,9 +76,10 @@ struct TreeDev {
     // Same bytes as quant_map + data_retained of the file, slot-major so that one hit leaf touches
     // one or two cache lines instead of one per basis function.
     // Empty-space culling (round 3): the cubes, no finer than kOccLevel, that together contain every leaf of positive
-    // density, as bounding spheres in WORLD coordinates {x, y, z, radius} (radius = half diagonal + a margin far above the
-    // float error of a ray's sample points).  mark_tiles_kernel projects them into each frame: an 8x8-pixel tile that no
-    // sphere touches holds only rays that can never meet density -- background pixels, known without marching.
+    // density, as {x, y, z, h}: the centre in WORLD coordinates and the half-edge in TREE units (half the cube + a margin far
+    // above the float error of a ray's sample points); the box's world half-widths are h / |scale|.  mark_tiles_kernel projects
+    // them into each frame: an 8x8-pixel tile that no box touches holds only rays that can never meet density -- background
+    // pixels, known without marching.
     const float4* occ_cells;
     int n_occ_cells;  // (0 with occ_cells != nullptr: a tree without density; occ_cells == nullptr: no culling)
     const uint16_t* qrec;

@@ -22,15 +22,16 @@ def main():
             env = dict(os.environ, RTO_LIB=os.path.abspath(lib))
             p = subprocess.run(base, capture_output=True, text=True, env=env, cwd=ROOT)
             lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
-            if p.returncode or not lines:
+            if p.returncode or not lines:  # (a failed run may have left the GPU in a bad state: start nothing after it)
                 print("round %d %s: FAILED rc %d %s" % (r, lib, p.returncode, p.stderr[-300:]), flush=True)
-                continue
+                sys.exit(1)
             d = json.loads(lines[-1])
             rf, rt = d["roofline"], d["reference_timer"]
             print("round %d %-44s %8.0f frames/s  marks+lists+thresholds %.3f  traverse %.3f  shade %.3f  net %.4f  filter %.4f ms/frame x100  "
-                  "parity mismatches %s" % (r, os.path.basename(lib), d["value"], rf["thresholds_kernel_avg_launch_ms"], rf["avg_launch_ms"],
-                                           rf["shade_kernel_avg_launch_ms"], rt["torch_ms"] * 100, rt["filter_ms"] * 100,
-                                           (d.get("parity_spot") or {}).get("mismatches")), flush=True)
+                  "tile slots marched %.4f  parity mismatches %s"
+                  % (r, os.path.basename(lib), d["value"], rf["thresholds_kernel_avg_launch_ms"], rf["avg_launch_ms"],
+                     rf["shade_kernel_avg_launch_ms"], (rt["torch_ms"] or 0.0) * 100, (rt["filter_ms"] or 0.0) * 100, rf.get("tiles_marched_frac") or 0.0,
+                     (d.get("parity_spot") or {}).get("mismatches")), flush=True)
 
 
 if __name__ == "__main__":
