@@ -816,6 +816,39 @@ int rto_image_read_png(const char* path, int* width, int* height, uint8_t* rgba,
  * filter 0, stored deflate blocks).  RTO_E_INVALID: a null argument or a non-positive extent; RTO_E_IO: the file cannot be written. */
 int rto_image_write_png(const char* path, const uint8_t* rgba, int width, int height);
 
+/* ---- quantiser (renderer/scripts/compress_octree.py:68-119; the median cut that script takes from svox) ----
+ * A deterministic median cut of m rows of three fp16 values into 2^bits boxes: ids[m] (uint16) = the box of every row,
+ * palette[2^bits][3] (fp16) = the mean of every box.  All 16-bit arrays are bit patterns.  1 <= m <= 2^31 - 1, bits in 1..16.
+ *   key      of a value with bit pattern h: the order-preserving uint16 (h & 0x8000 ? ~h : h | 0x8000); the order of values IS the
+ *            order of keys, so -0 sorts before +0.
+ *   a round  All rows start in box 0.  Round l = 0 .. bits - 1, for every box b < 2^l holding cnt rows: lo[c], hi[c] = the
+ *            minimum and maximum of the box on axis c, converted to float32; the extent hi[c] - lo[c] is one IEEE float32
+ *            subtraction; the split axis is the lowest c with the largest extent.  Order the box's rows by (key on that axis,
+ *            original row index): the first (cnt + 1) / 2 rows (integer division) go to box 2b, the rest to box 2b + 1.  An
+ *            empty box yields two empty boxes; a one-row box sends its row to 2b.
+ *   ids      after `bits` rounds, ids[row] = the row's box.
+ *   palette  for box b and channel c, S = the exact integer sum of value * 2^24 (every fp16 value is an integer in those units);
+ *            mean = (double)S / (double)cnt * 2^-24, converted to float32 and then to fp16, round to nearest even both times;
+ *            cnt = 0 gives +0.  Integer sums: the palette does not depend on any order of summation.
+ * Nothing is left to the implementation: the device entry, the host twin and the numpy model of the tests give the same bits.
+ * RTO_E_INVALID, with a text: a NaN or an infinity in any row; m * max|value| * 2^24 >= 2^63 (a box sum could leave an int64;
+ * decided on the actual maximum, out of reach of real SH coefficients); a null argument, m < 1 or above 2^31 - 1, bits outside
+ * 1..16; on the device entry also pointers that are misaligned or not memory of the handle's device.  The argument refusals are
+ * decided before anything is enqueued; the two that depend on the values are found by the kernels and reported after the run,
+ * with palette and ids unspecified.
+ * rto_quantize_median_cut is a TOOL path, not a frame path: it enqueues its kernels on `stream`, reads the refusal flags back and
+ * returns after the stream has drained.  Kernel boundaries are its only grid-wide synchronisation and integer atomics its only
+ * atomics: two runs give the same bits.  The handle owns all scratch (about 24 m bytes), which grows on demand and is reused
+ * across calls; growing synchronises the device once.  One handle serves one stream at a time.
+ * rto_quantize_median_cut_host is the host twin: host pointers, no device, the definition followed literally. */
+typedef struct rto_quantizer rto_quantizer;
+int rto_quantizer_create(int device, rto_quantizer** out);
+void rto_quantizer_free(rto_quantizer* q);
+int rto_quantize_median_cut(rto_quantizer* q, void* stream, const uint16_t* rows /* device [m][3] */, int64_t m, int bits,
+                            uint16_t* palette /* device [2^bits][3] */, uint16_t* ids /* device [m] */);
+int rto_quantize_median_cut_host(const uint16_t* rows /* [m][3] */, int64_t m, int bits, uint16_t* palette /* [2^bits][3] */,
+                                 uint16_t* ids /* [m] */);
+
 /* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
  * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
  * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that

@@ -214,6 +214,10 @@ SYMBOLS = {
     "rto_metrics_compute": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "rto_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
     "rto_image_write_png": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
+    "rto_quantizer_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_quantizer_free": (None, [_P]),
+    "rto_quantize_median_cut": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
+    "rto_quantize_median_cut_host": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_guidance_train_free": (None, [_P]),
     "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
