@@ -849,6 +849,53 @@ int rto_quantize_median_cut(rto_quantizer* q, void* stream, const uint16_t* rows
 int rto_quantize_median_cut_host(const uint16_t* rows /* [m][3] */, int64_t m, int bits, uint16_t* palette /* [2^bits][3] */,
                                  uint16_t* ids /* [m] */);
 
+/* ---- simplifier (what svox's shrink_to_fit and the pruning of PlenOctree extraction do; the reference holds no counterpart) ----
+ * Makes a tree smaller AS A TREE without changing the field it stores: every point query of the result returns the bits the
+ * input returns (+0 in all D halves where a leaf was killed).
+ *   input    child[cap][N^3] (int32): relative node offsets, 0 = leaf, as svox writes them; data[cap][N^3][D]: fp16 bit patterns,
+ *            the density is the last of the D; kill_thresh: a float, NaN = no kill.  1 <= cap, cap * N^3 < 2^31, N >= 2, D >= 1.
+ *   links    Node 0 is the root.  Slot s of node n with c = child[n][s] != 0 refers to node n + c -- for EVERY n < cap, whether
+ *            the walk reaches it or not.  RTO_E_FORMAT, with a text and the outputs unspecified: an n + c outside [1, cap); a
+ *            node referred to by more than one slot; a node at level 32 (the root is level 0, a node referred to by a node of
+ *            level l is level l + 1).  With those excluded the walk from the root is a tree; a node it does not reach (never
+ *            referred to, below such a node, or on a cycle apart from the root) is UNREACHABLE and is dropped.  Every read that
+ *            decides this is bounds-checked before the dereference it guards: a malformed array is refused, it never faults.
+ *   kill     (kill_thresh not NaN) th = kill_thresh rounded to fp16 (to nearest even, beyond 65504 an infinity).  A leaf slot of
+ *            a reachable node whose density half d is not IEEE d > th is DEAD (a NaN density is dead; -0 == +0): its record
+ *            becomes D halves +0.
+ *   merge    Deepest level first, a parent after all its children: a reachable node other than the root is UNIFORM when its N^3
+ *            slots are all leaves and their N^3 records (after the kill) are equal bit for bit.  The slot that refers to it
+ *            becomes a leaf holding that record and the node is dropped; cascades finish within the call; the root stays.
+ *   compact  The survivors keep their order; a node's new index is its rank among them; an offset becomes
+ *            new[target] - new[node]; records move unchanged.  child_out and data_out have room for cap nodes and hold
+ *            *out_capacity nodes afterwards (what lies behind is unspecified); node_map[i] (optional, int64, room for cap) = the
+ *            old index of new node i.
+ *   stats    reachable: nodes the walk reaches; unreachable = cap - reachable; killed: dead leaf slots of reachable nodes,
+ *            whatever their record held; merged: uniform nodes dropped; levels: 1 + the deepest level of a surviving node.
+ * Nothing is left to the implementation: the device entry, the host twin and the numpy model of the tests give the same bits.
+ * RTO_E_INVALID, decided before anything is enqueued: a null pointer (node_map and stats may be NULL), cap < 1, cap * N^3 >= 2^31,
+ * N < 2, D < 1, an output that overlaps an input or another output, a pointer not aligned to its element; on the device entry
+ * also child, data, child_out, data_out or node_map not memory of the handle's device (out_capacity and stats are host memory).
+ * rto_tree_simplify is a TOOL path like rto_quantize_median_cut: it enqueues on `stream`, reads the link flags and the level
+ * counts back once before the merge passes (one per level) and the result words once at the end, and returns after the stream
+ * has drained.  Kernel boundaries are its only grid-wide synchronisation, integer atomics its only atomics, the scan of the keep
+ * flags is reduce-then-scan: two runs give the same bytes.  The handle owns all scratch (about 8 N^3 + 16 bytes per node), which
+ * grows on demand and is reused; one handle serves one stream at a time.  data and data_out aligned to 16 bytes with N^3 * D a
+ * multiple of 8 (always for N = 2 or 4) take the 16-byte scatter, anything else a half-by-half one.
+ * rto_tree_simplify_host is the host twin: host pointers, no handle, no device. */
+typedef struct rto_simplify_stats {
+    int64_t reachable, unreachable, killed, merged, levels;
+} rto_simplify_stats;
+typedef struct rto_simplifier rto_simplifier;
+int rto_simplifier_create(int device, rto_simplifier** out);
+void rto_simplifier_free(rto_simplifier* s);
+int rto_tree_simplify(rto_simplifier* s, void* stream, const int32_t* child, const uint16_t* data, int64_t cap, int N, int D,
+                      float kill_thresh, int32_t* child_out, uint16_t* data_out, int64_t* out_capacity /* host */,
+                      int64_t* node_map /* device, or NULL */, rto_simplify_stats* stats /* host, or NULL */);
+int rto_tree_simplify_host(const int32_t* child, const uint16_t* data, int64_t cap, int N, int D, float kill_thresh,
+                           int32_t* child_out, uint16_t* data_out, int64_t* out_capacity, int64_t* node_map,
+                           rto_simplify_stats* stats);
+
 /* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
  * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
  * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that

@@ -13,6 +13,7 @@ from .volrend import (  # noqa: F401
 from .meshes import Mesh, MeshSet, MeshParams, draw_mesh_layers, trace_mesh_rays, MESH_MERGE  # noqa: F401
 from .metrics import FrameMetrics, ImageMetrics, read_png  # noqa: F401
 from .quantize import Quantizer, quantize_median_cut  # noqa: F401
+from .simplify import Simplifier, simplify_tree  # noqa: F401
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
@@ -21,5 +22,5 @@ __all__ = [
     "GridParams", "draw_grid_layers", "GRID_MERGE",
     "Mesh", "MeshSet", "MeshParams", "draw_mesh_layers", "trace_mesh_rays", "MESH_MERGE",
     "FrameMetrics", "ImageMetrics", "read_png",
-    "Quantizer", "quantize_median_cut",
+    "Quantizer", "quantize_median_cut", "Simplifier", "simplify_tree",
 ]

@@ -107,6 +107,12 @@ class CTreeInfo(C.Structure):
     ]
 
 
+class CSimplifyStats(C.Structure):
+    """rto_simplify_stats (include/rto.h)"""
+    _fields_ = [("reachable", C.c_int64), ("unreachable", C.c_int64), ("killed", C.c_int64), ("merged", C.c_int64),
+                ("levels", C.c_int64)]
+
+
 # every symbol include/rto.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -218,6 +224,12 @@ SYMBOLS = {
     "rto_quantizer_free": (None, [_P]),
     "rto_quantize_median_cut": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     "rto_quantize_median_cut_host": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
+    "rto_simplifier_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_simplifier_free": (None, [_P]),
+    "rto_tree_simplify": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P, C.POINTER(C.c_int64), _P,
+                                    C.POINTER(CSimplifyStats)]),
+    "rto_tree_simplify_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P, C.POINTER(C.c_int64), _P,
+                                         C.POINTER(CSimplifyStats)]),
     "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_guidance_train_free": (None, [_P]),
     "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
