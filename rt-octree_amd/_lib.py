@@ -254,12 +254,21 @@ SYMBOLS = {
 }
 
 
+def build_jobs(env=None):
+    """make's job count: MAX_JOBS when it is set to a positive number (16 at most), else 4"""
+    try:
+        jobs = int((os.environ if env is None else env).get("MAX_JOBS", ""))
+    except ValueError:
+        jobs = 0
+    return min(jobs, 16) if jobs > 0 else 4
+
+
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 build of librto.so (cross-compiles without a GPU)."""
     if force:
         subprocess.check_call(["make", "-C", CSRC, "clean"], stdout=subprocess.DEVNULL)
     out = None if verbose else subprocess.DEVNULL
-    subprocess.check_call(["make", "-C", CSRC, "-j4"], stdout=out)
+    subprocess.check_call(["make", "-C", CSRC, "-j%d" % build_jobs()], stdout=out)
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("librto.so was not produced at " + LIB_PATH)
     return LIB_PATH

@@ -1,7 +1,8 @@
 // depth_kernels.hip -- the depth-carrying instantiations of the single-frame and ray kernels (include/rto.h "depth outputs";
-// DESIGN.md section 7e): the bodies of render_kernels.hip (rto_render_fast.inc, rto_render_generic.inc) with RTO_DEPTH defined, which
-// also keep the distance of a ray's hits and store depth and t_near through a DepthOut argument.  A translation unit of its own:
-// render_kernels.hip keeps its kernels, their text and its compile time, and the two compile side by side.
+// DESIGN.md section 7e): the bodies of frame_kernels.hip and render_kernels.hip (rto_render_fast.inc, rto_render_generic.inc,
+// rto_render_persist.inc) with RTO_DEPTH defined, which also keep the distance of a ray's hits and store depth and t_near through a
+// DepthOut argument.  A translation unit of its own: those units keep their kernels, their text and their compile time, and all
+// compile side by side (the unit map: render_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include "rto_kernel_types.h"
@@ -10,7 +11,7 @@
 
 #pragma clang fp contract(off)
 
-#include "rto_depth_launch.h"
+#include "rto_render_internal.h"
 #include "rto_dispatch.h"
 #include "rto_render_shared.h"
 
@@ -95,8 +96,8 @@ __global__ void __launch_bounds__(256, persist_depth_wps(SPP, WPS, WIDE)) render
 #undef RTO_PERSIST_LAYERS
 }
 
-// ------------------------------------------------------------------ launchers (declared in rto_depth_launch.h)
-// spp, lobe form and traversal image are dispatched here, by the helpers render_kernels.hip's launchers use (rto_dispatch.h)
+// ------------------------------------------------------------------ launchers (declared in rto_render_internal.h)
+// spp, lobe form and traversal image are dispatched here, by the helpers the other render units' launchers use (rto_dispatch.h)
 
 const void* persist_depth_kernel(int spp, const TreeDev& tree) {
     const void* fn = nullptr;

@@ -256,7 +256,7 @@ void wide_image_lookup(const WideImage& wi, const int32_t* child, int G, const u
             node = w;  // internal: the node two levels down (from the grid: the level-G node's)
             off -= 2u;
         }
-        // hit index -> leaf slot (render_kernels.hip wide_to_slot)
+        // hit index -> leaf slot (rto_tree_device.h wide_to_slot)
         int64_t slot;
         const uint32_t pad = wi.grid_nodes * 64u;
         if (u < pad) {

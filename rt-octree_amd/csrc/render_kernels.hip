@@ -30,6 +30,17 @@
 // [0, 1-1e-6] every operation of the reference descent (x*=2; floor; x-=floor) is exact in fp32,
 // so the child digit at level l is bit (23-l) of floor(pos*2^24) and the leaf-local coordinate is
 // frac(pos * 2^(l+1)) exactly.
+//
+// The render stage is one translation unit per group of kernels, each with the launchers of its kernels, so that they
+// compile side by side; the launchers the units call in each other are rto_render_internal.h:
+//   tree_image_kernels.hip  the builders of a tree's derived arrays (nodew, shrec, topgrid, qrec), the rebuild of the reference
+//                           layout, the frame table and the u8 conversion
+//   frame_kernels.hip       render_generic and render_fast, offscreen and over layers: launch_render
+//   ray_kernels.hip         the same bodies over a batch of rays, render_rays_generic and render_rays: launch_rays
+//   render_kernels.hip      (this unit) the batched traversal stage -- tile marks, ray queues, sample_kernel, render_persist --
+//                           and the batched launch itself, launch_render_batch
+//   shade_kernels.hip       shade_kernel and its knobs behind launch_shade; the basis probe
+//   depth_kernels.hip       the depth-carrying forms of the frame, ray and batched traversal kernels
 #include <hip/hip_runtime.h>
 
 #include "rto_kernel_types.h"
@@ -37,200 +48,11 @@
 
 #pragma clang fp contract(off)
 
-// ray set-up, pixel / ray outputs, tiles, hit entries, packed shading, RTO_FAST_WPS: shared with depth_kernels.hip
+// ray set-up, pixel / ray outputs, tiles, hit entries, packed shading, RTO_FAST_WPS: shared with the other render units
 #include "rto_render_shared.h"
-#include "rto_depth_launch.h"  // the launchers of depth_kernels.hip, which launch_render / launch_rays forward to
+#include "rto_render_internal.h"  // launch_shade (shade_kernels.hip) and the batched depth traversal (depth_kernels.hip)
 
 namespace rto {
-
-// ------------------------------------------------------------------ generic kernel (any N)
-
-template <int SPP>
-__global__ void __launch_bounds__(256) render_generic(const TreeDev tree, const CamDev cam, const OptDev opt,
-                                                       const Pcg32 rng_base, const FrameOut fo) {
-#include "rto_render_generic.inc"
-}
-
-// rto_launch_rays on any tree the fast kernel does not take (N != 2, hit entries too wide) and RTO_KERNEL_GENERIC
-template <int SPP>
-__global__ void __launch_bounds__(256) render_rays_generic(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
-                                                            const RayBatch rays) {
-#define RTO_GENERIC_RAYS 1
-#include "rto_render_generic.inc"
-#undef RTO_GENERIC_RAYS
-}
-
-// rto_launch_renderer over the context's layers (rto_ctx_set_layers) on any tree the fast kernel does not take and RTO_KERNEL_GENERIC
-template <int SPP>
-__global__ void __launch_bounds__(256) render_generic_layers(const TreeDev tree, const CamDev cam, const OptDev opt, const Pcg32 rng_base,
-                                                              const FrameOut fo, const LayerDev layers) {
-#define RTO_GENERIC_LAYERS 1
-#include "rto_render_generic.inc"
-#undef RTO_GENERIC_LAYERS
-}
-
-// ------------------------------------------------------------------ traversal image
-
-// One word per child slot: internal -> child[] value, leaf -> kLeafTag | sigma fp16 bits.
-// Derived data (like the reference's commented-out occupancy LUT, n3tree.cpp:206-225): it only
-// re-packs what child[]/data[] already say, so traversal decisions cannot change.
-__global__ void build_nodew_kernel(const int32_t* __restrict__ child, const uint16_t* __restrict__ data,
-                                   int64_t n_slots, int data_dim, uint32_t* __restrict__ nodew,
-                                   int* __restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots) return;
-    const int32_t c = child[i];
-    if (c == 0) {
-        nodew[i] = kLeafTag | (uint32_t)data[i * data_dim + data_dim - 1];
-    } else {
-        if (nodew_is_leaf((uint32_t)c)) atomicExch(bad, 1);  // |offset| >= 2^30: not encodable
-        nodew[i] = (uint32_t)c;
-    }
-}
-
-// Aligned copy of the SH coefficients for the shading kernels (TreeDev::shrec): per slot the 3 B coefficients of
-// data[] in the same order, zero-padded to shrec_halves(B).  Derived data: the same fp16 values.
-__global__ void build_shrec_kernel(const uint16_t* __restrict__ data, int64_t n_slots, int data_dim, int rec,
-                                   const uint32_t* __restrict__ recidx, uint16_t* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one thread per half of a slot's record
-    if (i >= n_slots * rec) return;
-    const int64_t slot = i / rec;
-    const int k = (int)(i - slot * rec);
-    int64_t dst = slot;
-    if (recidx) {  // compact records (RTO_TREE_COMPACT_RECORDS): only the slots that own one
-        const uint32_t r = recidx[slot];
-        if (r == kNoRecord) return;
-        dst = r;
-    }
-    out[dst * rec + k] = k < data_dim - 1 ? data[slot * data_dim + k] : (uint16_t)0;
-}
-
-// The reference-layout arrays back from the derived ones (rto_tree.cpp ensure_reference_arrays): a tree that renders through
-// the fast / batched kernels keeps only nodew + shrec resident; the generic kernel's child[] / data[] are rebuilt on
-// first use.  Leaf slots get their exact fp16 values back (coefficients from shrec, sigma from the leaf word); an
-// internal slot's sigma -- which no query ever returns -- becomes 0.
-__global__ void rebuild_reference_kernel(const uint16_t* __restrict__ shrec, const uint32_t* __restrict__ nodew,
-                                         const uint32_t* __restrict__ recidx, int64_t n_slots, int data_dim, int rec,
-                                         uint16_t* __restrict__ data, int32_t* __restrict__ child) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one thread per half of data[]
-    if (i >= n_slots * data_dim) return;
-    const int64_t slot = i / data_dim;
-    const int k = (int)(i - slot * data_dim);
-    const uint32_t w = nodew[slot];
-    const bool leaf = nodew_is_leaf(w);
-    int64_t src = slot;
-    bool has = true;
-    if (recidx) {  // compact records: a slot without one (internal, or a leaf of zero density) reads as zeros
-        const uint32_t r = recidx[slot];
-        has = r != kNoRecord;
-        src = r;
-    }
-    // (shrec == nullptr: entry-ordered records -- rebuild_reference_wide_kernel fills the coefficients in afterwards)
-    data[i] = k < data_dim - 1 ? (has && shrec ? shrec[src * rec + k] : (uint16_t)0) : (leaf ? (uint16_t)(w & 0xffffu) : (uint16_t)0);
-    if (k == 0) child[slot] = leaf ? 0 : (int32_t)w;
-}
-
-// Top-of-tree shortcut (TreeDev::topgrid): one thread per cell of the 2^G-per-axis grid walks its
-// root path over node levels 0..G-1 and records where it ends: {slot | level << kGridSlotBits, nodew[slot]}.
-__global__ void build_topgrid_kernel(const uint32_t* __restrict__ nodew, int G, uint2* __restrict__ grid) {
-    const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-    if (key >= (1u << (3 * G))) return;
-    const uint32_t mask = (1u << G) - 1u;
-    const uint32_t cx = key >> (2 * G), cy = (key >> G) & mask, cz = key & mask;
-    uint32_t node = 0, slot = 0, w = 0;
-    int lvl = 0;
-    for (;;) {
-        const int sh = G - 1 - lvl;
-        const uint32_t ci = (((cx >> sh) & 1u) << 2) | (((cy >> sh) & 1u) << 1) | ((cz >> sh) & 1u);
-        slot = node * 8u + ci;
-        w = nodew[slot];
-        if (nodew_is_leaf(w) || lvl == G - 1) break;
-        node += w;
-        ++lvl;
-    }
-    grid[key] = make_uint2(slot | ((uint32_t)lvl << kGridSlotBits), w);
-}
-
-// ------------------------------------------------------------------ fast kernel (N == 2)
-
-// the aligned coefficient records in the order of the two-level image's entries (TreeDev::rec_by_entry): record e = the 3 B
-// coefficients of the leaf that entry e of widew names, zero-padded to `rec` halves; entries that are internal nodes (or
-// padding) keep zeros.  One thread per half.  Derived data: the same fp16 values.
-__global__ void build_shrec_wide_kernel(const TreeDev tree, const uint16_t* __restrict__ data, int64_t n_entries, int rec,
-                                        uint16_t* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_entries * rec) return;
-    const uint32_t e = (uint32_t)(i / rec);
-    const int k = (int)(i - (int64_t)e * rec);
-    uint16_t v = 0;
-    if (nodew_is_leaf(tree.widew[e]) && k < tree.data_dim - 1) {
-        const uint32_t pad = tree.wide_grid_nodes * 64u, cells = 1u << (3 * tree.top_levels);
-        if (e >= pad || e < cells) v = data[(uint64_t)wide_to_slot(tree, e) * tree.data_dim + k];
-    }
-    out[i] = v;
-}
-
-// ... and back: the coefficients of data[] from entry-ordered records (rebuild_reference_kernel wrote child[], sigma and
-// zeros before).  A first-level leaf's 8 entries write the same values to the same place.
-__global__ void rebuild_reference_wide_kernel(const TreeDev tree, int64_t n_entries, int rec, uint16_t* __restrict__ data) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_entries * rec) return;
-    const uint32_t e = (uint32_t)(i / rec);
-    const int k = (int)(i - (int64_t)e * rec);
-    if (k >= tree.data_dim - 1 || !nodew_is_leaf(tree.widew[e])) return;
-    const uint32_t pad = tree.wide_grid_nodes * 64u, cells = 1u << (3 * tree.top_levels);
-    if (e < pad && e >= cells) return;  // padding behind the grid cells
-    data[(uint64_t)wide_to_slot(tree, e) * tree.data_dim + k] = tree.shrec[(uint64_t)e * rec + k];
-}
-
-// STATS: also count the units of SURVEY 8(d)'s algorithmic-byte formula (march steps, descent
-// levels a root-restart walk would visit, distinct hit leaves, ...) into fo.stats.  Separate
-// instantiation; the timed kernel carries none of it.
-// STACK == 1 (two-level image, at most two pairs of levels below the grid; the launcher decides): the restart of render_persist's
-// register-stack form -- the node a step starts from is chosen by where the ray is and which coordinate bits changed
-// (rto_march_leaf.inc), positions are kept scaled by 2^24 (kPos24), the step's power-of-two factors come from the level bits of
-// the leaf word -- seven dependent instructions fewer on the chain a lone frame's longest rays wait for
-// The body (rto_render_fast.inc) serves two kernels: render_fast for SH and RGBA trees and render_fast_lobes for SG / ASG trees
-// (LOBES = kFmtSG / kFmtASG, see ray_basis), so that the SH kernels keep their names and their code.
-template <int SPP, bool STATS, bool WIDE, int STACK = 0>
-__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast(const TreeDev tree, const CamDev cam, const OptDev opt,
-                                                    const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
-                                                    const TileMap tm, const FrameOut fo) {
-    constexpr int LOBES = 0;
-#include "rto_render_fast.inc"
-}
-
-// the single-frame kernel of an SG / ASG tree (LOBES = kFmtSG / kFmtASG): the same body under its own name
-template <int SPP, bool STATS, bool WIDE, int STACK, int LOBES>
-__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_lobes(const TreeDev tree, const CamDev cam, const OptDev opt,
-                                                          const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
-                                                          const TileMap tm, const FrameOut fo) {
-#include "rto_render_fast.inc"
-}
-
-// rto_launch_rays on an N == 2 tree: the same body with the rays of the batch for the camera's pixels -- one thread per ray, no
-// tile map and no culling marks (both are per camera tile), each ray's own depth limit and backdrop, a float4 per ray
-template <int SPP, bool WIDE, int STACK, int LOBES>
-__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_rays(const TreeDev tree, const OptDev opt, const Pcg32 rng_base,
-                                                    const PcgJumpEntry* __restrict__ jump, const RayBatch rays) {
-    constexpr bool STATS = false;
-#define RTO_FAST_RAYS 1
-#include "rto_render_fast.inc"
-#undef RTO_FAST_RAYS
-}
-
-// rto_launch_renderer over the context's layers (rto_ctx_set_layers) on an N == 2 tree: the same body, each pixel's ray stopped at
-// its depth and composited over its colour; the tiles culled by fo.cull_marks get their backdrop.  No counting instantiation
-// (layers and rto_ctx_enable_stats are refused together).
-template <int SPP, bool WIDE, int STACK, int LOBES>
-__global__ void __launch_bounds__(256, SPP <= 8 ? RTO_FAST_WPS : 4) render_fast_layers(const TreeDev tree, const CamDev cam, const OptDev opt,
-                                                           const Pcg32 rng_base, const PcgJumpEntry* __restrict__ jump,
-                                                           const TileMap tm, const FrameOut fo, const LayerDev layers) {
-    constexpr bool STATS = false;
-#define RTO_FAST_LAYERS 1
-#include "rto_render_fast.inc"
-#undef RTO_FAST_LAYERS
-}
 
 // ------------------------------------------------------------------ persistent kernel (N == 2)
 //
@@ -620,182 +442,6 @@ __global__ void __launch_bounds__(256, WPS) render_persist_layers(const TreeDev 
 #undef RTO_PERSIST_LAYERS
 }
 
-
-// One hit leaf of a quantised tree, shaded straight from the codebooks (TreeDev::qrec / qcolors): the
-// coefficients are the very fp16 values N3Tree::load_npz would have expanded (n3tree.cpp:310-339),
-// summed in shade_leaf's order, so the pixel is bit-identical to rendering the decoded tree.
-template <int B>
-RTO_DEV void shade_leaf_quant(const TreeDev& tree, uint32_t slot, const float* basis_fn, float cnt, float* out) {
-    const int nr = tree.q_retain;
-    const uint16_t* __restrict__ rec = tree.qrec + (uint64_t)slot * (uint32_t)tree.q_rec;
-    float v[B][3];
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        if (k < nr) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[k][c] = half_bits_to_float(rec[k * 3 + c]);
-        } else {
-            const uint32_t id = rec[2 * nr + k];  // 3 * nr + (k - nr)
-            const uint2 e = tree.qcolors[(uint32_t)(k - nr) * 65536u + id];
-            v[k][0] = half_bits_to_float((uint16_t)(e.x & 0xffffu));
-            v[k][1] = half_bits_to_float((uint16_t)(e.x >> 16));
-            v[k][2] = half_bits_to_float((uint16_t)(e.y & 0xffffu));
-        }
-    }
-    float t3[3], o3[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float tmp = basis_fn[0] * v[0][c];
-        if constexpr (B >= 25) {
-            tmp += basis_fn[16] * v[16][c] + basis_fn[17] * v[17][c] + basis_fn[18] * v[18][c] +
-                   basis_fn[19] * v[19][c] + basis_fn[20] * v[20][c] + basis_fn[21] * v[21][c] +
-                   basis_fn[22] * v[22][c] + basis_fn[23] * v[23][c] + basis_fn[24] * v[24][c];
-        }
-        if constexpr (B >= 16) {
-            tmp += basis_fn[9] * v[9][c] + basis_fn[10] * v[10][c] + basis_fn[11] * v[11][c] +
-                   basis_fn[12] * v[12][c] + basis_fn[13] * v[13][c] + basis_fn[14] * v[14][c] +
-                   basis_fn[15] * v[15][c];
-        }
-        if constexpr (B >= 9) {
-            tmp += basis_fn[4] * v[4][c] + basis_fn[5] * v[5][c] + basis_fn[6] * v[6][c] + basis_fn[7] * v[7][c] +
-                   basis_fn[8] * v[8][c];
-        }
-        if constexpr (B >= 4) {
-            tmp += basis_fn[1] * v[1][c] + basis_fn[2] * v[2][c] + basis_fn[3] * v[3][c];
-        }
-        t3[c] = tmp;
-    }
-    sigmoid_cnt3(t3, cnt, o3);  // out[c] += cnt / (1.f + det_expf(-tmp)), rt_core.cuh:314-318
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] += o3[c];
-    out[3] += cnt;
-}
-
-// quant_map [nq][ns] + data_retained [nr][ns][3]  ->  slot-major records (TreeDev::qrec)
-__global__ void pack_quant_kernel(const uint16_t* __restrict__ qmap, const uint16_t* __restrict__ retained,
-                                  int64_t ns, int nr, int nq, int rec, uint16_t* __restrict__ out) {
-    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= ns) return;
-    uint16_t* o = out + slot * rec;
-    for (int k = 0; k < nr; ++k)
-        for (int c = 0; c < 3; ++c) o[k * 3 + c] = retained[((int64_t)k * ns + slot) * 3 + c];
-    for (int j = 0; j < nq; ++j) o[3 * nr + j] = qmap[(int64_t)j * ns + slot];
-    if (rec > 3 * nr + nq) o[rec - 1] = 0;
-}
-
-hipError_t launch_pack_quant(const uint16_t* qmap, const uint16_t* retained, int64_t ns, int nr, int nq, int rec,
-                             uint16_t* out, hipStream_t stream) {
-    hipLaunchKernelGGL(pack_quant_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, qmap, retained, ns, nr,
-                       nq, rec, out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ shading kernel
-// Second half of trace_ray (rt_core.cuh:272-331) + the pixel epilogue (volrend.cu:174-212) for the
-// batched path.  hits: packed entries per frame, ended by the first word without kHitValid (layout: hit_index).
-//
-// Only about a quarter of the pixels hit anything and those that do hold 1..SPP leaves, so a
-// thread-per-pixel loop leaves most lanes idle while the gathers of a few run.  Instead each wave
-// owns 64 * P consecutive pixels, compacts their hit entries into an LDS list (wave prefix sum),
-// shades the entries one per lane -- every lane busy, all of an entry's loads independent -- and
-// the pixel lanes then add their entries' contributions up in hit order, which keeps the float sums
-// those of the reference's loop.  The list is processed in windows of kShadeCap entries so LDS use
-// does not depend on SPP.
-#ifndef RTO_SHADE_CAP
-#define RTO_SHADE_CAP 320
-#endif
-constexpr int kShadeCap = RTO_SHADE_CAP;
-
-// contribution of one hit leaf: rgb[c] = cnt * sigmoid(<basis, coeffs_c>) (or cnt * rgb for RGBA trees)
-// MODE (host-chosen, so that each instantiation carries one leaf layout's registers only):
-// 0 any dense tree; 28 / 49 / 76 dense SH9 / SH16 / SH25 records (or SG / ASG records of the same data_dim: the layout does
-// not depend on the basis); -B quantised SH<B>, not expanded
-template <int MODE>
-RTO_DEV void leaf_contrib(const TreeDev& tree, uint32_t slot, const float* basis_fn, float cnt, float* o) {
-    o[0] = o[1] = o[2] = o[3] = 0.f;  // 0 + x == x: the helpers' "+=" yields the bare term
-    if constexpr (MODE < 0) {
-        shade_leaf_quant<-MODE>(tree, slot, basis_fn, cnt, o);
-    } else if constexpr (MODE == 0) {
-        shade_leaf(tree, tree.data + (uint64_t)slot * tree.data_dim, basis_fn, cnt, o);
-    } else {
-        shade_leaf_packed<MODE>(tree, slot, basis_fn, cnt, o);
-    }
-}
-
-#ifndef RTO_SHADE_WPS
-#define RTO_SHADE_WPS 4
-#endif
-// workgroups per CU the kernel is built for: the SH25 layouts (76 coefficients in registers) and the quantised SH16 one need
-// more than the 128 VGPRs that 4 leave them (they spilled 10-50 registers to scratch: SH25 shading 9.6 -> 8.7 ms per 100
-// frames of 1920x1080 without the spills, at 3)
-#ifndef RTO_SHADE_WPS_SH25
-#define RTO_SHADE_WPS_SH25 3
-#endif
-constexpr int shade_wps(int mode) { return (mode == 76 || mode == -25 || mode == -16) ? RTO_SHADE_WPS_SH25 : RTO_SHADE_WPS; }
-#ifdef RTO_DBG_COUNTERS
-// where a shading wave's lifetime goes (tools/dbg_shade_phases.py): per wave (blockIdx.x * 4 + wave, up to 2^19 of them) the s_memtime
-// stamps 0..5 and its number of hit entries; plain stores, reduced on the host (atomics would slow the very kernel they time)
-constexpr int kShadeStampWaves = 1 << 19;
-__device__ unsigned long long g_shade_phase[kShadeStampWaves * 8];
-#define RTO_SHADE_STAMP(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ph[i] = __builtin_amdgcn_s_memtime(); }
-#else
-#define RTO_SHADE_STAMP(i) {}
-#endif
-// Waves per workgroup: ONE (round 6).  The waves of this kernel never talk to each other (wave-level barriers only), and their
-// lifetimes differ by a factor of eight -- a wave over culled tiles ends after ~7 k clocks, one with 500 hit entries after ~58 k
-// (tools/dbg_shade_phases.py, profiles/r6_d_shade_phases.txt) -- but a workgroup's LDS and wave slots are released only when its
-// LAST wave ends: with 4 waves per workgroup the SIMDs held 2.9 waves of the 4 they have room for.
-#ifndef RTO_SHADE_WG_WAVES
-#define RTO_SHADE_WG_WAVES 1
-#endif
-constexpr int kShadeWaves = RTO_SHADE_WG_WAVES;
-#ifndef RTO_SHADE_BAND_ROWS
-#define RTO_SHADE_BAND_ROWS 8
-#endif
-// pixel blocks (of block_px consecutive pixels, scanline order) per band of RTO_SHADE_BAND_ROWS rows
-__host__ __device__ constexpr uint32_t shade_blocks_per_band(int W, int block_px) {
-    return (uint32_t)((RTO_SHADE_BAND_ROWS > 0 ? RTO_SHADE_BAND_ROWS : 1) * W + block_px - 1) / (uint32_t)block_px;
-}
-// LOBES: 0 for SH and RGBA trees, kFmtSG / kFmtASG for a tree of that format (with MODE 0 / 28 / 49 / 76)
-template <int SPP, int P, int MODE, int LOBES = 0>
-__global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kernel(const TreeDev tree, const OptDev opt, const FrameBatch fb,
-                                                                              const uint32_t* __restrict__ hits0) {
-#include "rto_shade.inc"
-}
-
-// the shading kernel over the context's colour layer (rto_ctx_set_layers): the same body, the epilogue composites every pixel --
-// hit, missed or culled -- over its pixel of the colour plane of its frame
-template <int SPP, int P, int MODE, int LOBES = 0>
-__global__ void __launch_bounds__(64 * kShadeWaves, shade_wps(MODE)) shade_kernel_layers(const TreeDev tree, const OptDev opt, const FrameBatch fb,
-                                                                                     const uint32_t* __restrict__ hits0, const LayerDev layers) {
-#define RTO_SHADE_LAYERS 1
-#include "rto_shade.inc"
-#undef RTO_SHADE_LAYERS
-}
-
-// ------------------------------------------------------------------ frame table
-// The frame descriptors of a batch reach the device as kernel arguments of this one-wave kernel, at most kFrameChunk
-// per launch (a kernarg segment holds 4 KB; 64 descriptors are 6 KB), and are written to the context's table on the
-// launch stream: no host staging buffer whose lifetime would have to outlast an asynchronous copy.
-__global__ void write_frames_kernel(const FrameChunk c, FrameDesc* __restrict__ dst, int n) {
-    const int i = threadIdx.x;
-    if (i < n) dst[i] = c.f[i];
-}
-
-// ------------------------------------------------------------------ u8 conversion
-// main_headless.cpp:535-538: (uint8_t)(f * 255), truncation, all four channels
-__global__ void rgba8_kernel(const float4* __restrict__ in, uchar4* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 v = in[i];
-    uchar4 o;
-    o.x = (unsigned char)(v.x * 255);
-    o.y = (unsigned char)(v.y * 255);
-    o.z = (unsigned char)(v.z * 255);
-    o.w = (unsigned char)(v.w * 255);
-    out[i] = o;
-}
-
 }  // namespace rto
 
 // ------------------------------------------------------------------ host launchers (C++ linkage,
@@ -804,107 +450,6 @@ __global__ void rgba8_kernel(const float4* __restrict__ in, uchar4* __restrict__
 #include "rto_launch.h"
 
 namespace rto {
-
-hipError_t launch_build_nodew(const int32_t* child, const uint16_t* data, int64_t n_slots, int data_dim,
-                              uint32_t* nodew, int* bad_flag, hipStream_t stream) {
-    const int threads = 256;
-    const int64_t blocks = (n_slots + threads - 1) / threads;
-    hipLaunchKernelGGL(build_nodew_kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, child, data, n_slots,
-                       data_dim, nodew, bad_flag);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_shrec(const uint16_t* data, int64_t n_slots, int data_dim, int rec, const uint32_t* recidx, uint16_t* out,
-                              hipStream_t stream) {
-    const int64_t n = n_slots * rec;
-    hipLaunchKernelGGL(build_shrec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, data, n_slots, data_dim, rec, recidx, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_shrec_wide(const TreeDev& tree, const uint16_t* data, int64_t n_entries, int rec, uint16_t* out, hipStream_t stream) {
-    const int64_t n = n_entries * rec;
-    hipLaunchKernelGGL(build_shrec_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tree, data, n_entries, rec, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_rebuild_reference_wide(const TreeDev& tree, int64_t n_entries, int rec, uint16_t* data, hipStream_t stream) {
-    const int64_t n = n_entries * rec;
-    hipLaunchKernelGGL(rebuild_reference_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tree, n_entries, rec, data);
-    return hipGetLastError();
-}
-
-hipError_t launch_rebuild_reference(const uint16_t* shrec, const uint32_t* nodew, const uint32_t* recidx, int64_t n_slots, int data_dim,
-                                    int rec, uint16_t* data, int32_t* child, hipStream_t stream) {
-    const int64_t n = n_slots * data_dim;
-    hipLaunchKernelGGL(rebuild_reference_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, shrec, nodew, recidx, n_slots,
-                       data_dim, rec, data, child);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_topgrid(const uint32_t* nodew, int G, uint2* grid, hipStream_t stream) {
-    const unsigned n = 1u << (3 * G);
-    hipLaunchKernelGGL(build_topgrid_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, nodew, G, grid);
-    return hipGetLastError();
-}
-
-TileMap make_tile_map(int width, int height, int strip_rows) {
-    TileMap tm;
-    tm.tiles_x = (width + kTileW - 1) / kTileW;
-    tm.tiles_y = (height + kTileH - 1) / kTileH;
-    tm.strip_rows = strip_rows < 1 ? 1 : strip_rows;
-    const int strips = (tm.tiles_y + tm.strip_rows - 1) / tm.strip_rows;
-    const int strips_per_xcd = (strips + 7) / 8;
-    tm.per_xcd = strips_per_xcd * tm.strip_rows * tm.tiles_x;
-    return tm;
-}
-
-template <int SPP, int LOBES>
-static void launch_fast(const TreeDev& tree, const CamDev& cam, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                        const FrameOut& fo, int strip_rows, const LayerDev* layers, hipStream_t stream) {
-    const TileMap tm = make_tile_map(cam.width, cam.height, strip_rows);
-    const size_t lds = fast_lds_bytes(tree);
-    const dim3 grid(8 * tm.per_xcd), block(256);
-    const auto offscreen = [&](auto stats, auto wide, auto stack) {
-        if constexpr (LOBES == 0)
-            hipLaunchKernelGGL((render_fast<SPP, stats, wide, stack>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
-        else
-            hipLaunchKernelGGL((render_fast_lobes<SPP, stats, wide, stack, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo);
-    };
-    if (fo.stats && !layers) {  // (the counting instantiation walks the one-level image: its units are defined on that walk)
-        offscreen(std::true_type{}, std::false_type{}, int_c<0>{});
-        return;
-    }
-    with_image(tree, [&](auto wide, auto stack) {
-        if (layers)  // (the host refuses layers with work counters)
-            hipLaunchKernelGGL((render_fast_layers<SPP, wide, stack, LOBES>), grid, block, lds, stream, tree, cam, opt, rng, jump, tm, fo, *layers);
-        else
-            offscreen(std::false_type{}, wide, stack);
-    });
-}
-
-hipError_t launch_rays(int kernel, int spp, const TreeDev& tree, const OptDev& opt, const Pcg32& rng, const PcgJumpEntry* jump,
-                       const RayBatch& rb_in, const DepthOut* depth, bool xcd_order, hipStream_t stream) {
-    if (rb_in.n == 0) return hipSuccess;
-    if ((uint64_t)rb_in.n * (uint64_t)spp >= (uint64_t(1) << 32)) return hipErrorInvalidValue;  // (the RNG offset of a ray is 32-bit)
-    RayBatch rb = rb_in;
-    const uint32_t blocks = (uint32_t)(((uint64_t)rb.n + 255) / 256);
-    rb.per_xcd = xcd_order ? (blocks + 7) / 8 : 0u;
-    const dim3 grid(xcd_order ? 8 * rb.per_xcd : blocks);
-    if (depth)  // the depth-carrying kernels (depth_kernels.hip)
-        return kernel == 2 ? launch_rays_depth_fast(spp, tree, opt, rng, jump, rb, *depth, grid, stream)
-                           : launch_rays_depth_generic(spp, tree, opt, rng, rb, *depth, grid, stream);
-    return with_spp(spp, [&](auto SPP) {
-        if (kernel == 2)
-            with_lobes(tree, [&](auto LOBES) {
-                with_image(tree, [&](auto wide, auto stack) {
-                    hipLaunchKernelGGL((render_rays<SPP, wide, stack, LOBES>), grid, dim3(256), fast_lds_bytes(tree), stream, tree, opt, rng, jump, rb);
-                });
-            });
-        else
-            hipLaunchKernelGGL(render_rays_generic<SPP>, grid, dim3(256), 0, stream, tree, opt, rng, rb);
-        return hipGetLastError();
-    });
-}
 
 hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_t* mask, int mask_words, hipStream_t stream) {
     FrameDesc fd = {};
@@ -918,26 +463,6 @@ hipError_t launch_mark_tiles_one(const TreeDev& tree, const CamDev& cam, uint32_
         hipLaunchKernelGGL(mark_tiles_one_kernel, grid, dim3(256), lds, stream, tree, fd, cam.width, cam.height, mask_words, mask);
     }
     return hipGetLastError();
-}
-
-hipError_t launch_render(int kernel, int spp, const TreeDev& tree, const CamDev& cam, const OptDev& opt,
-                         const Pcg32& rng, const PcgJumpEntry* jump, const FrameOut& fo, int strip_rows,
-                         const LayerDev* layers, const DepthOut* depth, hipStream_t stream) {
-    if (depth) {  // the depth-carrying layered kernels (depth_kernels.hip), over the context's layers or none
-        const LayerDev ld = layers ? *layers : LayerDev{nullptr, nullptr};
-        return kernel == 2 ? launch_fast_depth(spp, tree, cam, opt, rng, jump, fo, strip_rows, ld, *depth, stream)
-                           : launch_generic_depth(spp, tree, cam, opt, rng, fo, ld, *depth, stream);
-    }
-    return with_spp(spp, [&](auto SPP) {
-        const dim3 ggrid((unsigned)(((int64_t)cam.width * cam.height + 255) / 256));
-        if (kernel == 2)
-            with_lobes(tree, [&](auto LOBES) { launch_fast<SPP, LOBES>(tree, cam, opt, rng, jump, fo, strip_rows, layers, stream); });
-        else if (layers)
-            hipLaunchKernelGGL(render_generic_layers<SPP>, ggrid, dim3(256), 0, stream, tree, cam, opt, rng, fo, *layers);
-        else
-            hipLaunchKernelGGL(render_generic<SPP>, ggrid, dim3(256), 0, stream, tree, cam, opt, rng, fo);
-        return hipGetLastError();
-    });
 }
 
 // (RTO_WPS_DEFAULT, the waves per SIMD the default instantiation is built for: rto_render_shared.h)
@@ -960,10 +485,9 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     const size_t lds = (size_t)((regstack ? 2 : tree.max_depth + 1 - tree.top_levels) + SPP + 1 + (with_depth ? (regstack ? 2 : 4) : 0)) * 256 * sizeof(uint32_t) + sizeof(float) * kCamFloats * (size_t)fb.n;
     // the traversal kernel of this launch: the key of the occupancy cache, of the occupancy query and of the LDS request below
     const void* fn = reinterpret_cast<const void*>(&render_persist<SPP, REFILL, WPS, WIDE, STACK>);
-    bool depth_layer = false, color_layer = false;
+    bool depth_layer = false;
     if constexpr (LAYERS) {
         depth_layer = layers && layers->depth;
-        color_layer = layers && layers->color;
         if (depth_layer) fn = reinterpret_cast<const void*>(&render_persist_layers<SPP, REFILL, WPS, WIDE, STACK>);
         if (with_depth) fn = persist_depth_kernel(SPP, tree);
     }
@@ -1002,7 +526,6 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
     //  C5 2.44 -> 2.41, C4 11.85 -> 11.71, 8 scenes 3.26 -> 3.13; one tile 3.74 / 2.48 / 11.73 / 3.14, eight 3.90 on C2:
     //  profiles/r6_zz_ab_chunk_*.txt)
     const uint32_t chunk = chunk_override > 0 ? (uint32_t)chunk_override : (rays_per_wave >= 512 ? 128u : 64u);
-    const int64_t size = (int64_t)fb.width * fb.height;
     if (ev) (void)hipEventRecord(ev[0], stream);
     // tile marks (empty-space culling; all ones when it is off), then the ray queues as lists of the marked tile slots
     uint32_t* mask = const_cast<uint32_t*>(fb.tile_mask);
@@ -1044,40 +567,10 @@ static hipError_t launch_batch_impl(const TreeDev& tree, const OptDev& opt, cons
         hipLaunchKernelGGL((render_persist<SPP, REFILL, WPS, WIDE, STACK>), dim3(grid), dim3(256), lds, stream, tree, opt, fb, queue, hits, chunk);
     if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
     if (ev) (void)hipEventRecord(ev[2], stream);
-#ifndef RTO_SHADE_P
-#define RTO_SHADE_P 2
-#endif
-    constexpr int SP = SPP <= 8 ? RTO_SHADE_P : 1;  // pixels per lane of the shading kernel (its hit lists live in registers)
-    const unsigned pblocks = (unsigned)((size + 64 * kShadeWaves * SP - 1) / (64 * kShadeWaves * SP));
-#if RTO_SHADE_BAND_ROWS > 0
-    const unsigned cpb = shade_blocks_per_band(fb.width, 64 * kShadeWaves * SP), bands = (pblocks + cpb - 1u) / cpb;
-    const dim3 sgrid(((bands + 7u) / 8u) * 8u * cpb * (unsigned)fb.n);  // see shade_kernel: (band, frame, pixel block of the band) <- block id
-#else
-    const dim3 sgrid(((pblocks + 7u) / 8u) * 8u * (unsigned)fb.n);  // see shade_kernel: (pixel block, frame) <- block id
-#endif
-    const dim3 sblock(64 * kShadeWaves);
-    if (tree.qrec && !color_layer) {  // (the host admits SH4/9/16/25 only, and refuses a quantised-direct tree layers)
-        const auto quant = [&](auto mode) { hipLaunchKernelGGL((shade_kernel<SPP, SP, mode>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits); };
-        if (tree.basis_dim == 4)
-            quant(int_c<-4>{});
-        else if (tree.basis_dim == 9)
-            quant(int_c<-9>{});
-        else if (tree.basis_dim == 16)
-            quant(int_c<-16>{});
-        else
-            quant(int_c<-25>{});
-    } else {  // an expanded tree: the record modes for SH, SG and ASG trees, over the colour layer or not
-        with_lobes(tree, [&](auto lobes) {
-            with_record_mode(tree, lobes != 0 || tree.format == kFmtSH, [&](auto mode) {
-                if (!color_layer)
-                    hipLaunchKernelGGL((shade_kernel<SPP, SP, mode, lobes>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits);
-                else if constexpr (LAYERS)
-                    hipLaunchKernelGGL((shade_kernel_layers<SPP, SP, mode, lobes>), sgrid, sblock, 0, stream, tree, opt, fb, (const uint32_t*)hits, *layers);
-            });
-        });
-    }
+    // the shading stage (shade_kernels.hip): over the colour layer where the launch carries one
+    const hipError_t shaded = launch_shade(SPP, tree, opt, fb, hits, layers, stream);
     if (ev) (void)hipEventRecord(ev[3], stream);
-    return hipGetLastError();
+    return shaded;
 }
 
 template <int SPP>
@@ -1135,94 +628,6 @@ hipError_t launch_render_batch(int spp, const TreeDev& tree, const OptDev& opt, 
     return with_spp(spp, [&](auto SPP) {
         return launch_batch_spp<SPP>(tree, opt, fb, jump, queue, hits, num_cus, refill, cull, occ, ev, layers, depth, stream);
     });
-}
-
-#ifdef RTO_DBG_COUNTERS
-hipError_t debug_shade_phases(unsigned long long* out, bool reset) {  // out: kShadeStampWaves * 8 words
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_shade_phase), sizeof(unsigned long long) * kShadeStampWaves * 8);
-    if (e == hipSuccess && reset) {
-        void* p = nullptr;
-        e = hipGetSymbolAddress(&p, HIP_SYMBOL(g_shade_phase));
-        if (e == hipSuccess) e = hipMemset(p, 0, sizeof(unsigned long long) * kShadeStampWaves * 8);
-    }
-    return e;
-}
-#endif
-
-// ------------------------------------------------------------------ basis probe (rto_probe_basis)
-// out[i][0..24] = the basis the kernels compute for the view direction dirs[i] (before the rot_dirs rotation): PATH 0 the run-time
-// ray_basis of the generic / fast kernels and shade_kernel<..., 0>, PATH 1 the per-B forms of the shading kernel's record modes
-// (ray_basis_sh<B> / ray_basis_lobes<LOBES, B>; entries from B on are 0)
-template <int PATH, int LOBES, int B>
-__global__ void __launch_bounds__(256) basis_probe_kernel(const TreeDev tree, const OptDev opt, const float* __restrict__ dirs, int64_t n,
-                                                          float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float vdir[3] = {dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
-    float basis_fn[RTO_BASIS_MAX_DEV];
-#pragma unroll
-    for (int k = 0; k < RTO_BASIS_MAX_DEV; ++k) basis_fn[k] = 0.f;
-    if constexpr (PATH == 0)
-        ray_basis_any(tree, opt, vdir, basis_fn);
-    else if constexpr (LOBES == 0)
-        ray_basis_sh<B>(opt, vdir, basis_fn);
-    else
-        ray_basis_lobes<LOBES, B>(tree, opt, vdir, basis_fn);
-#pragma unroll
-    for (int k = 0; k < RTO_BASIS_MAX_DEV; ++k) out[i * RTO_BASIS_MAX_DEV + k] = basis_fn[k];
-}
-
-template <int LOBES, int B = 1>
-static hipError_t launch_probe_lobes(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, float* out, hipStream_t stream) {
-    if (tree.basis_dim == B) {
-        hipLaunchKernelGGL((basis_probe_kernel<1, LOBES, B>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tree, opt, dirs, n, out);
-        return hipGetLastError();
-    }
-    if constexpr (B < RTO_BASIS_MAX_DEV)
-        return launch_probe_lobes<LOBES, B + 1>(tree, opt, dirs, n, out, stream);
-    else
-        return hipErrorInvalidValue;
-}
-
-hipError_t launch_probe_basis(const TreeDev& tree, const OptDev& opt, const float* dirs, int64_t n, int path, float* out, hipStream_t stream) {
-    const dim3 grid((unsigned)((n + 255) / 256));
-#define RTO_PROBE(P, L, B) hipLaunchKernelGGL((basis_probe_kernel<P, L, B>), grid, dim3(256), 0, stream, tree, opt, dirs, n, out)
-    if (path == 0) {
-        RTO_PROBE(0, 0, 0);
-    } else if (tree.format == kFmtSG) {
-        return launch_probe_lobes<kFmtSG>(tree, opt, dirs, n, out, stream);
-    } else if (tree.format == kFmtASG) {
-        return launch_probe_lobes<kFmtASG>(tree, opt, dirs, n, out, stream);
-    } else if (tree.format == kFmtSH) {  // (the basis sizes the shading kernel has per-B forms for)
-        switch (tree.basis_dim) {
-            case 4: RTO_PROBE(1, 0, 4); break;
-            case 9: RTO_PROBE(1, 0, 9); break;
-            case 16: RTO_PROBE(1, 0, 16); break;
-            case 25: RTO_PROBE(1, 0, 25); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef RTO_PROBE
-    return hipGetLastError();
-}
-
-hipError_t launch_write_frames(const FrameDesc* host, int n, FrameDesc* dev_table, hipStream_t stream) {
-    for (int f0 = 0; f0 < n; f0 += kFrameChunk) {
-        FrameChunk c;
-        const int m = n - f0 < kFrameChunk ? n - f0 : kFrameChunk;
-        for (int i = 0; i < m; ++i) c.f[i] = host[f0 + i];
-        hipLaunchKernelGGL(write_frames_kernel, dim3(1), dim3(64), 0, stream, c, dev_table + f0, m);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_rgba8(const float* rgba, uint8_t* out, int64_t n_pixels, hipStream_t stream) {
-    const int threads = 256;
-    hipLaunchKernelGGL(rgba8_kernel, dim3((unsigned)((n_pixels + threads - 1) / threads)), dim3(threads), 0, stream,
-                       reinterpret_cast<const float4*>(rgba), reinterpret_cast<uchar4*>(out), n_pixels);
-    return hipGetLastError();
 }
 
 }  // namespace rto

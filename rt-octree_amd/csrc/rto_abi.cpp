@@ -1,7 +1,7 @@
 // rto_abi.cpp -- the C ABI declared in include/rto.h: version, errors, options, the rto_ctx_* surface, the filtering entry
 // points, downloads and timers.  Trees: rto_tree.cpp; the launch entries: rto_render_abi.cpp.  Owns the error string that
 // set_err (rto_abi_common.h) records for every unit of the library.  Host logic only; every computation on frame data
-// happens in the gfx950 kernels (render_kernels.hip, filter_kernels.hip).  There is no CPU fallback.
+// happens in the gfx950 kernels (the render units mapped in render_kernels.hip, filter_kernels.hip).  There is no CPU fallback.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -1,7 +1,7 @@
 // rto_dispatch.h -- host only: the run-time values a launcher turns into template arguments, each rule stated once.  A helper calls
 // a generic lambda with std::integral_constant arguments, which convert to the kernels' template arguments:
 //     with_spp(spp, [&](auto SPP) { hipLaunchKernelGGL(render_rays_generic<SPP>, ...); return hipGetLastError(); });
-// Used by the launchers of render_kernels.hip and depth_kernels.hip ("Where dispatch lives").
+// Used by the launchers of the render units (render_kernels.hip, frame_kernels.hip, shade_kernels.hip) and depth_kernels.hip ("Where dispatch lives").
 #pragma once
 #include <hip/hip_runtime.h>
 

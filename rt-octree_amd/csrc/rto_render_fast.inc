@@ -1,4 +1,4 @@
-// rto_render_fast.inc -- body of the single-frame fast kernel, included by render_kernels.hip into render_fast (LOBES = 0: SH and
+// rto_render_fast.inc -- body of the single-frame fast kernel, included by frame_kernels.hip into render_fast (LOBES = 0: SH and
 // RGBA trees), render_fast_lobes (LOBES = kFmtSG / kFmtASG) and render_rays (RTO_FAST_RAYS defined to 1 around the include: the
 // rays of rto_launch_rays instead of a camera's pixels) and render_fast_layers (RTO_FAST_LAYERS defined to 1: a camera's pixels,
 // each ray stopped at its pixel of the depth layer and composited over its pixel of the colour layer -- `layers`, rto_ctx_set_layers).

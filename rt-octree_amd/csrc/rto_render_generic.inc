@@ -1,4 +1,4 @@
-// rto_render_generic.inc -- body of the generic kernel, included by render_kernels.hip into render_generic (a camera's pixels)
+// rto_render_generic.inc -- body of the generic kernel, included by frame_kernels.hip into render_generic (a camera's pixels)
 // render_rays_generic (RTO_GENERIC_RAYS defined to 1 around the include: the rays of rto_launch_rays) and render_generic_layers
 // (RTO_GENERIC_LAYERS defined to 1: a camera's pixels over the layers of rto_ctx_set_layers).  In scope: the kernel
 // parameters and SPP.  (The ray source is switched by the preprocessor: render_generic's text and code are unchanged.)

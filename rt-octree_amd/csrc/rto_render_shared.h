@@ -1,7 +1,7 @@
 // rto_render_shared.h -- the device pieces the render kernel bodies (rto_render_fast.inc, rto_render_generic.inc) are built from:
 // ray set-up, the pixel / ray outputs, the workgroup tiles, hit-list entries and the packed leaf shading.  Included by
-// render_kernels.hip and by depth_kernels.hip (the depth-carrying instantiations of the same bodies, a translation unit of their
-// own so that the two compile side by side).  Everything here is RTO_DEV (forced inline) or constexpr.  Include it behind the
+// the render units (frame_kernels.hip, render_kernels.hip, shade_kernels.hip) and by depth_kernels.hip (the depth-carrying
+// instantiations of the same bodies): translation units of their own so that they compile side by side.  Everything here is RTO_DEV (forced inline) or constexpr.  Include it behind the
 // translation unit's `#pragma clang fp contract(off)`: the bodies are compared bit for bit with the CPU oracle.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// rto_shade.inc -- body of the batched path's shading kernel, included by render_kernels.hip into shade_kernel and
+// rto_shade.inc -- body of the batched path's shading kernel, included by shade_kernels.hip into shade_kernel and
 // shade_kernel_layers (RTO_SHADE_LAYERS defined to 1 around the include: a pixel -- live or culled -- is composited over its pixel
 // of the colour layer, `layers`, rto_ctx_set_layers, where it is stored).  In scope: the kernel parameters and SPP, P, MODE, LOBES.
 // (Switched by the preprocessor: shade_kernel's text and code are what they were before the layered kernel existed.)

@@ -11,7 +11,7 @@
 
 namespace rto {
 
-// Leaf tag of the traversal image `nodew` (see build_nodew_kernel in render_kernels.hip):
+// Leaf tag of the traversal image `nodew` (see build_nodew_kernel in tree_image_kernels.hip):
 //   internal slot: the reference's child[] value (relative node offset, |v| < 2^30)
 //   leaf slot:     0x80000000 | fp16 bits of the slot's sigma  -> top two bits are 0b10
 constexpr uint32_t kLeafTag = 0x80000000u;

@@ -1,7 +1,7 @@
 // rto_tree_device.h -- device functions that more than one translation unit of the library states the tree's answers with:
 // the view-direction basis (SH, SG / ASG, the basis_minmax mask), the reference's float descent over child[], and the
-// entry <-> slot relations of the two-level traversal image.  render_kernels.hip and query_kernels.hip include it; the
-// functions are force-inlined, so each kernel's code is what it was when they stood in render_kernels.hip.
+// entry <-> slot relations of the two-level traversal image.  The render units (render_kernels.hip's map) and query_kernels.hip include it; the
+// functions are force-inlined, so each kernel's code is what it was when they stood beside the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

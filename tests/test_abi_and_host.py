@@ -41,6 +41,13 @@ def test_library_has_gfx950_code_object():
     assert b"gfx950" in blob and b"render_fast" in blob
 
 
+def test_build_takes_its_job_count_from_max_jobs():
+    """build_library's `make -j`: MAX_JOBS where it is set to a positive number, 16 at most; 4 where it is unset or unusable"""
+    assert _lib.build_jobs({}) == 4
+    for text, jobs in (("1", 1), ("8", 8), ("16", 16), ("64", 16), ("0", 4), ("-2", 4), ("", 4), ("many", 4)):
+        assert _lib.build_jobs({"MAX_JOBS": text}) == jobs, text
+
+
 def test_options_defaults_and_opt_json(tmp_path):
     o = R.RenderOptions()
     assert (o.step_size, o.sigma_thresh, o.stop_thresh, o.background_brightness) == (

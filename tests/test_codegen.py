@@ -57,10 +57,29 @@ def kernel_resources(src, extra=(), min_kernels=21):
     return {n: {"vgprs": v, "scratch": s, "occupancy": o} for n, v, s, o in zip(names, vg, sc, oc)}
 
 
+RENDER_UNITS = ("render_kernels.hip", "frame_kernels.hip", "ray_kernels.hip", "shade_kernels.hip", "tree_image_kernels.hip")  # (the map in render_kernels.hip)
+
+
+def render_asm():
+    """gfx950 assembly of the render stage's units, joined (depth_kernels.hip, the depth-carrying forms, is asked for by its name)"""
+    return "\n".join(device_asm(src) for src in RENDER_UNITS)
+
+
+def render_resources():
+    """kernel_resources of the render stage's units, merged: the 636 kernels they held as one unit, each in exactly one of them"""
+    res = {}
+    for src in RENDER_UNITS:
+        unit = kernel_resources(src, min_kernels=1)
+        assert not set(unit) & set(res), (src, sorted(set(unit) & set(res)))
+        res.update(unit)
+    assert len(res) == 636, len(res)
+    return res
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 def test_the_two_gathers_of_a_node_visit_are_issued_back_to_back(tmp_path):
     """the ONE-level walk (trees without the two-level image): top-grid entry and slot word are issued back to back"""
-    text = device_asm("render_kernels.hip")
+    text = render_asm()
     for spp in (1, 6):  # the benchmark's instantiations (C5, C2 / C4)
         m = re.search(r"^_ZN3rto14render_persistILi%dELi32ELi8ELb0ELi0EEE[^\n]*\n(.*?)s_endpgm" % spp, text, re.S | re.M)
         assert m, "render_persist<%d,32,8,false> not found in the assembly" % spp
@@ -78,7 +97,7 @@ def test_the_two_gathers_of_a_node_visit_are_issued_back_to_back(tmp_path):
 def test_the_two_level_walk_has_one_gather_per_node_visit(tmp_path):
     """round 4: grid cells and wide nodes live in one array and a node visit is one uniform dword load -- no 8-byte grid
     entry, no second address computation anywhere in the kernel"""
-    text = device_asm("render_kernels.hip")
+    text = render_asm()
     for spp in (1, 6):
         for stack in (0, 1):  # ancestor stack in LDS rows / in two registers
             m = re.search(r"^_ZN3rto14render_persistILi%dELi32ELi8ELb1ELi%dEEE[^\n]*\n(.*?)s_endpgm" % (spp, stack), text, re.S | re.M)
@@ -99,7 +118,7 @@ def test_the_traversal_kernels_private_segments_are_what_is_recorded_here():
     instantiation and the single-frame kernel at 5 waves (88 VGPRs).  The two-level form
     with its ancestor stack in LDS rows (trees deeper than four levels below the top grid) keeps 16-24 bytes, in the ray set-up:
     sizes recorded here so that a change of them is a decision, not an accident."""
-    res = kernel_resources("render_kernels.hip")
+    res = render_resources()
     for spp in (1, 2, 3, 4, 6, 8, 16, 32):
         k = res["_ZN3rto14render_persistILi%dELi32ELi8ELb1ELi1EEEvNS_7TreeDevENS_6OptDevENS_10FrameBatchEPyPjj" % spp]
         assert k["occupancy"] == 8 and k["vgprs"] <= 64, (spp, k)
@@ -225,7 +244,7 @@ def test_no_kernel_holds_v_pk_fma_f32(tmp_path):
     this test builds every device source the way the Makefile does and looks for the instruction."""
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"filter_kernels\.o: HIPFLAGS \+= -fno-slp-vectorize", mk), "the Makefile no longer disables SLP for filter_kernels.hip"
-    for src, extra in (("filter_kernels.hip", ["-fno-slp-vectorize"]), ("guidance_kernels.hip", []), ("render_kernels.hip", [])):  # (probe_kernels.hip holds the instruction on purpose: the VALU calibration probe)
+    for src, extra in (("filter_kernels.hip", ["-fno-slp-vectorize"]), ("guidance_kernels.hip", [])) + tuple((u, []) for u in RENDER_UNITS):  # (probe_kernels.hip holds the instruction on purpose: the VALU calibration probe)
         text = device_asm(src, extra)
         assert "s_endpgm" in text
         assert "v_pk_fma_f32" not in text, "%s: %d v_pk_fma_f32" % (src, text.count("v_pk_fma_f32"))

@@ -93,8 +93,8 @@ def test_depth_kernels_codegen():
     import shutil
     if shutil.which("hipcc") is None:
         pytest.fail("hipcc is needed to cross-compile the kernels")
-    from test_codegen import kernel_resources
-    res = dict(kernel_resources("render_kernels.hip"))
+    from test_codegen import kernel_resources, render_resources
+    res = dict(render_resources())
     new = kernel_resources("depth_kernels.hip")
     assert not set(res) & set(new)
     res.update(new)

@@ -34,8 +34,8 @@ def test_depth_batch_codegen():
     build, no absolute number"""
     if shutil.which("hipcc") is None:
         pytest.fail("hipcc is needed to cross-compile the kernels")
-    from test_codegen import kernel_resources
-    old = kernel_resources("render_kernels.hip")
+    from test_codegen import kernel_resources, render_resources
+    old = render_resources()
     new = kernel_resources("depth_kernels.hip")
     assert not [n for n in old if "render_persist_depth" in n]
     forms = 0

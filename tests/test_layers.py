@@ -95,9 +95,9 @@ def test_layers_kernels_codegen():
     waves per SIMD it is built for (or its parent's, where that is fewer), and no kernel of the file holds v_pk_fma_f32"""
     if shutil.which("hipcc") is None:
         pytest.fail("hipcc is needed to cross-compile the kernels")
-    from test_codegen import device_asm, kernel_resources
-    res = kernel_resources("render_kernels.hip")
-    assert "v_pk_fma_f32" not in device_asm("render_kernels.hip")
+    from test_codegen import render_asm, render_resources
+    res = render_resources()
+    assert "v_pk_fma_f32" not in render_asm()
 
     def pair(parent_prefix, layered_prefix, target, slack=0):
         """target: the waves per SIMD the kernel is built for (its launch bounds); the layered form may hold a few VGPRs more

@@ -199,8 +199,8 @@ def test_rays_kernels_codegen():
     import shutil
     if shutil.which("hipcc") is None:
         pytest.fail("hipcc is needed to cross-compile the kernels")
-    from test_codegen import kernel_resources
-    res = kernel_resources("render_kernels.hip")
+    from test_codegen import render_resources
+    res = render_resources()
     for spp in (1, 2, 3, 4, 6, 8, 16, 32):
         fast = [v["occupancy"] for n, v in res.items() if n.startswith("_ZN3rto11render_fastILi%dELb0ELb1ELi" % spp)]
         assert len(fast) == 2, spp

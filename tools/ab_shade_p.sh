@@ -7,7 +7,7 @@ T=$(ls /dev/shm/rto_bench_tree_*.npz | head -1)
 python tools/make_quant_tree.py $T /dev/shm/q.npz --retain 1
 $B --tree /dev/shm/q.npz --quant-direct 2>/dev/null | pick
 for P in "$@"; do
-  touch rt-octree_amd/csrc/render_kernels.hip
+  touch rt-octree_amd/csrc/shade_kernels.hip
   make -C rt-octree_amd/csrc -j8 EXTRA=-DRTO_SHADE_P=$P >/dev/null 2>&1
   echo "P=$P"
   $B 2>/dev/null | pick
