@@ -35,10 +35,16 @@ float half_to_float(uint16_t h) {
 }
 
 bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3], const float offset[3], const uint16_t* sigma,
-                   size_t stride, std::vector<float>& out) {
+                   size_t stride, std::vector<float>& out, std::vector<float>* cubes) {
     auto density = [&](int64_t sl) { return half_to_float(sigma[(size_t)sl * stride]); };
     std::vector<uint8_t> lvl((size_t)capacity, 255), has((size_t)capacity, 0);
     std::vector<uint32_t> cx((size_t)capacity, 0), cy((size_t)capacity, 0), cz((size_t)capacity, 0);
+    // per node and axis: the bounds [lo, hi] of the subtree's dense leaves as fractions of the NODE'S OWN cube, in units of
+    // 2^-31 of its edge.  A slot is half the edge (2^30), a child's bounds are halved on the way up: every value is a multiple
+    // of 2^(30 - levels below) with at most 30 levels below, so the shifts drop no bit; and 0 <= lo < hi <= 2^31 whatever
+    // child[] holds -- relative bounds cannot leave their cell even where a damaged child[] gives a node two parents.
+    constexpr uint32_t kHalf = 1u << 30;
+    std::vector<uint32_t> blo((size_t)capacity * 3, 0), bhi((size_t)capacity * 3, 0);
     lvl[0] = 0;
     for (int64_t n = 0; n < capacity; ++n) {  // top-down: level and integer cell coordinates of every reachable node
         if (lvl[(size_t)n] == 255) continue;
@@ -53,17 +59,30 @@ bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3],
             cz[(size_t)t] = cz[(size_t)n] * 2 + (s & 1);
         }
     }
-    for (int64_t n = capacity - 1; n >= 0; --n) {  // bottom-up: does the subtree hold a leaf of positive density?
+    for (int64_t n = capacity - 1; n >= 0; --n) {  // bottom-up: does the subtree hold a leaf of positive density, and where?
         if (lvl[(size_t)n] == 255) continue;
         uint8_t h = 0;
-        for (int s = 0; s < 8 && !h; ++s) {
+        uint32_t lo[3] = {2 * kHalf, 2 * kHalf, 2 * kHalf}, hi[3] = {0, 0, 0};
+        for (int s = 0; s < 8; ++s) {
             const int32_t c = child[n * 8 + s];
-            h = c ? has[(size_t)(n + c)] : (uint8_t)(density(n * 8 + s) > 0.f);
+            if (!(c ? has[(size_t)(n + c)] : (uint8_t)(density(n * 8 + s) > 0.f))) continue;
+            h = 1;
+            const uint32_t bit[3] = {(uint32_t)(s >> 2) & 1u, (uint32_t)(s >> 1) & 1u, (uint32_t)s & 1u};
+            for (int i = 0; i < 3; ++i) {  // a dense leaf slot is its whole half of the edge, a child brings its own bounds
+                const uint32_t l = bit[i] * kHalf + (c ? blo[(size_t)(n + c) * 3 + i] >> 1 : 0u);
+                const uint32_t u = bit[i] * kHalf + (c ? bhi[(size_t)(n + c) * 3 + i] >> 1 : kHalf);
+                lo[i] = l < lo[i] ? l : lo[i];
+                hi[i] = u > hi[i] ? u : hi[i];
+            }
         }
         has[(size_t)n] = h;
+        for (int i = 0; i < 3 && h; ++i) blo[(size_t)n * 3 + i] = lo[i], bhi[(size_t)n * 3 + i] = hi[i];
     }
     out.clear();
+    if (cubes) cubes->clear();
     const float margin = 1e-4f;  // tree units: far above the float error of cen + t * dir (~1e-6), far below a cell
+    // (it pads the bounds as it pads a cube: they are a union of leaf cubes, and a sample point inside a dense leaf lies inside
+    //  that leaf's cube)
     for (int64_t n = 0; n < capacity; ++n) {
         if (lvl[(size_t)n] == 255 || !has[(size_t)n]) continue;
         const int ls = lvl[(size_t)n] + 1;  // the node's child slots are cubes of size 2^-ls
@@ -74,13 +93,20 @@ bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3],
             if (!emit) continue;
             const double size = std::ldexp(1.0, -ls);
             const uint32_t q[3] = {cx[(size_t)n] * 2 + ((s >> 2) & 1), cy[(size_t)n] * 2 + ((s >> 1) & 1), cz[(size_t)n] * 2 + (s & 1)};
+            // a record: {world centre, 0} {half-extents in TREE units, 0}.  The padded half-extents (a multiple of the finest
+            // leaf + the margin: exact to 1e-9 as floats); the kernel divides by |TreeDev::scale| per axis for the world
+            // half-widths of the box
+            float box[8] = {0.f}, cube[8] = {0.f};
             for (int i = 0; i < 3; ++i) {
-                const double ct = (q[i] + 0.5) * size;
-                out.push_back((float)((ct - offset[i]) / scale[i]));
-            }
-            // the padded half-edge in TREE units (a power of two + the margin: exact to 1e-10 as a float); the kernel divides
-            // by |TreeDev::scale| per axis for the world half-widths of the box
-            out.push_back((float)(0.5 * size + margin));
+                // a leaf slot is the cube; below a node of the culling level, the bounds of its subtree's dense leaves
+                const double l = c ? std::ldexp((double)blo[(size_t)(n + c) * 3 + i], -31) : 0.0;
+                const double u = c ? std::ldexp((double)bhi[(size_t)(n + c) * 3 + i], -31) : 1.0;
+                box[i] = (float)(((q[i] + 0.5 * (l + u)) * size - offset[i]) / scale[i]);
+                box[4 + i] = (float)(0.5 * (u - l) * size + margin);
+                cube[i] = (float)(((q[i] + 0.5) * size - offset[i]) / scale[i]);
+                cube[4 + i] = (float)(0.5 * size + margin);
+            }            out.insert(out.end(), box, box + 8);
+            if (cubes) cubes->insert(cubes->end(), cube, cube + 8);
         }
     }
     return true;

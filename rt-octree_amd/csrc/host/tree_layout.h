@@ -17,12 +17,15 @@ namespace rto {
 // IEEE binary16 -> binary32 (exact), for the host-side look at a leaf's density
 float half_to_float(uint16_t h);
 
-// The culling cells of a tree (TreeDev::occ_cells): cubes of size >= 2^-kOccLevel that together contain every leaf of positive
-// density, four floats each: the centre in WORLD coordinates and the half-edge, margin included, in TREE units (the box is
-// axis-aligned in both; its world half-widths are half-edge / |scale|).  Returns false when the node order does not allow
-// the single top-down pass (a child stored before its parent: cannot happen after the breadth-first relayout).
+// The culling cells of a tree (TreeDev::occ_cells): boxes that together contain every leaf of positive density.  A dense leaf
+// no finer than kOccLevel is its own cell, the cube; every node of level kOccLevel whose subtree holds a dense leaf is one cell,
+// the axis-aligned bounds of those leaves inside its cube.  Eight floats each: {centre in WORLD coordinates, 0} {half-extents
+// per axis, margin included, in TREE units, 0} (the box is axis-aligned in both; its world half-widths are half-extent / |scale|).
+// cubes, if not null: the same cells in the same order and format with every node's whole cube for its bounds (the cells before
+// the bounds: tuning "cull_cubes").  Returns false when the node order does not allow the single top-down pass (a child stored
+// before its parent: cannot happen after the breadth-first relayout).
 bool culling_cells(const int32_t* child, int64_t capacity, const float scale[3], const float offset[3], const uint16_t* sigma,
-                   size_t stride, std::vector<float>& out);
+                   size_t stride, std::vector<float>& out, std::vector<float>* cubes = nullptr);
 
 // Breadth-first node order of a tree: order[new] = old.  Children are visited in slot order, so after the
 // renumbering the internal children of every node are consecutive, in slot order, and every level is stored

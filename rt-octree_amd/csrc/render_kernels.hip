@@ -75,8 +75,9 @@ namespace rto {
 // A ray that never meets a leaf of positive density composites nothing: its pixel is the background, its hit list empty
 // (rt_core.cuh:252-262 only ever accumulates in leaves with sigma > sigma_thresh).  73 % of the bench scene's rays are such
 // rays and a third of all march steps are theirs.  mark_tiles_kernel decides it per 8x8-pixel tile, conservatively and
-// without marching: every culling cell of the tree (TreeDev::occ_cells: the cubes that hold the leaves of positive density,
-// as world-space boxes padded far above the float error of a sample point) is projected into every frame of the batch; the
+// without marching: every culling cell of the tree (TreeDev::occ_cells: boxes that hold the leaves of positive density -- per
+// node of level kOccLevel the bounds of its subtree's dense leaves, not its cube: a shell a few leaves thick fills a fraction
+// of most cubes -- as world-space boxes padded far above the float error of a sample point) is projected into every frame of the batch; the
 // tiles its projection can touch are marked.  An unmarked tile holds no ray that passes through a box, hence no ray that
 // visits a dense leaf: its rays are never queued, its pixels get no threshold draws.
 // The ball bound (rounds 3-6 applied it to the box's bounding sphere): with a ball's centre at camera coordinates (a, b, -d),
@@ -90,14 +91,21 @@ namespace rto {
 //     bound widens the rectangle by it.  The float error of p, of Cramer's sums and of the corner offsets is a few ulp of
 //     those magnitudes (~1e-6 of them for a camera matrix that is not close to singular); e is 10 times that.  The
 //     rectangle is used only while every corner's depth exceeds 100 e (the ball bound needs > 2 e; the rest keeps 1 / depth tame).
-//   * absolute, 1.5 pixels, as before: the ray of pixel x leaves through image-plane point (x - W / 2) / fx exactly, so the
-//     pad is pure slack for the float error of the pixel coordinates here (0.5 W + fx x: ~1e-4 pixel) and of the ray's own
-//     direction (ray_setup: the same size).
+//   * absolute, kMarkPad = 0.5 pixels (1.5 while the cells were cubes).  ray_setup sends the ray of pixel (x, y), x and y integers,
+//     through the camera-space point ((x - 0.5 W) / fx, -(y - 0.5 H) / fy, -1): the inverse of px = 0.5 W + fx a / d below AT
+//     the integer, with no half-pixel offset, and every sample of a pixel shares that ray.  So a ray can meet the box only if
+//     px0 <= x <= px1 up to float error, and the tiles floor(px0 / 8) .. floor(px1 / 8) would do.  The errors: of 0.5 W + fx x
+//     here two roundings at the magnitude of a pixel coordinate (~1e-4 pixel at W ~ 1000); of the ray's direction
+//     (a division, M xyz, normalize3) a few 1e-7 relative, ~1e-4 pixel at fx ~ 1000.  Both grow with the frame as fx does,
+//     and so does the relative pad above (1e-5 fx (1 + |x|) or more: 100 times either at any frame size); the absolute pad
+//     is 5000 times them at W ~ 1000 and never the one that is needed.  The sphere clamp keeps its 1.5.
 // A box with a corner nearer than that marks the whole frame; one with every corner behind the camera nothing.
 // The sphere rule stays as an upper clamp: where it yields a rectangle the tiles are the intersection of the two (each is a
 // bound by itself, and a box lies inside its bounding sphere: in exact arithmetic the box rectangle is the smaller one
 // already -- |M^-1|_F alone overstates an orthonormal camera's sphere by sqrt 3), where it marks nothing so does this, so
-// the marks are a subset of rounds 3-6's for every cell and camera whatever the rounding.  (Pixels are bit-identical with
+// the marks are a subset of the sphere rule's for every box and camera whatever the rounding.  (The sphere is the box's own:
+// a cell's bounds lie inside its cube, so their box rectangle lies inside the cube's and inside the cube's sphere rectangle
+// in exact arithmetic, and the sphere's 0.1 % and |M^-1|_F are far more than the rounding.)  (Pixels are bit-identical with
 // and without: tests/test_culling.py, tests/test_culling_cubes.py, and every parity test against the oracle, which marches
 // every ray, runs with it.)
 // One workgroup = kMarkCells cells of one frame, marked into a private copy of the frame's mask in LDS (LDS_MASK; a frame
@@ -105,8 +113,12 @@ namespace rto {
 // tens of thousands of cells land on a few hundred mask words, and device-scope atomics on one address serialise
 // (the first version, one global atomic per cell and tile, took 2.5 ms per 100 frames; this one 0.1).
 constexpr int kMarkCells = 2048, kMarkLdsWords = 8192;
+#ifndef RTO_MARK_PAD  // (A/B hook: the absolute pad in pixels; same pixels for every value >= 0.5)
+#define RTO_MARK_PAD 0.5f
+#endif
+constexpr float kMarkPad = RTO_MARK_PAD;
 template <class MarkFn>
-RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark);
+RTO_DEV void mark_cell(const float4 cell, const float4 half, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark);
 template <bool LDS_MASK>
 __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, const FrameBatch fb, uint32_t* __restrict__ mask) {
     extern __shared__ uint32_t s_mask[];
@@ -124,9 +136,9 @@ __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, con
         const int c = (int)blockIdx.x * kMarkCells + (int)threadIdx.x * (kMarkCells / 256) + i;
         if (c >= tree.n_occ_cells) break;
         if (LDS_MASK)
-            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });  // ds_or_b32
+            mark_cell(tree.occ_cells[2 * c], tree.occ_cells[2 * c + 1], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });  // ds_or_b32
         else
-            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(gm + w, bits); });
+            mark_cell(tree.occ_cells[2 * c], tree.occ_cells[2 * c + 1], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(gm + w, bits); });
     }
     if (LDS_MASK) {
         __syncthreads();
@@ -136,7 +148,7 @@ __global__ void __launch_bounds__(256) mark_tiles_kernel(const TreeDev tree, con
 }
 
 template <class MarkFn>
-RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark) {
+RTO_DEV void mark_cell(const float4 cell, const float4 half, const TreeDev& tree, const FrameDesc& fd, const FrameBatch& fb, MarkFn mark) {
     {
     const float* m = fd.transform;  // columns 0..2: camera axes, column 3: centre (common.cuh:29-44)
     const float p[3] = {cell.x - m[9], cell.y - m[10], cell.z - m[11]};
@@ -153,7 +165,7 @@ RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& 
     const float frob = sqrtf(c12[0] * c12[0] + c12[1] * c12[1] + c12[2] * c12[2] + c20[0] * c20[0] + c20[1] * c20[1] + c20[2] * c20[2] +
                              c01[0] * c01[0] + c01[1] * c01[1] + c01[2] * c01[2]) * fabsf(inv);
     // world half-widths of the box, and the radius of its bounding sphere (0.1 % above the half diagonal)
-    const float hw[3] = {cell.w / fabsf(tree.scale[0]), cell.w / fabsf(tree.scale[1]), cell.w / fabsf(tree.scale[2])};
+    const float hw[3] = {half.x / fabsf(tree.scale[0]), half.y / fabsf(tree.scale[1]), half.z / fabsf(tree.scale[2])};
     const float r = sqrtf(hw[0] * hw[0] + hw[1] * hw[1] + hw[2] * hw[2]) * 1.001f * frob * 1.0001f;
     if (d <= -r) return;    // wholly behind the camera (a NaN pose falls through to "keep everything")
     const float fx = fabsf(fd.fx), fy = fabsf(fd.fy);
@@ -198,8 +210,8 @@ RTO_DEV void mark_cell(const float4 cell, const TreeDev& tree, const FrameDesc& 
         return;
     }
     if (box) {
-        const float bx0 = floorf((fminf(px0, px1) - 1.5f) * 0.125f), bx1 = floorf((fmaxf(px0, px1) + 1.5f) * 0.125f);
-        const float by0 = floorf((fminf(py0, py1) - 1.5f) * 0.125f), by1 = floorf((fmaxf(py0, py1) + 1.5f) * 0.125f);
+        const float bx0 = floorf((fminf(px0, px1) - kMarkPad) * 0.125f), bx1 = floorf((fmaxf(px0, px1) + kMarkPad) * 0.125f);
+        const float by0 = floorf((fminf(py0, py1) - kMarkPad) * 0.125f), by1 = floorf((fmaxf(py0, py1) + kMarkPad) * 0.125f);
         // with both rules in hand the tiles are the intersection of the two rectangles (each alone is a valid bound)
         x0f = sphere ? fmaxf(x0f, bx0) : bx0, x1f = sphere ? fminf(x1f, bx1) : bx1;
         y0f = sphere ? fmaxf(y0f, by0) : by0, y1f = sphere ? fminf(y1f, by1) : by1;
@@ -237,9 +249,9 @@ __global__ void __launch_bounds__(256) mark_tiles_one_kernel(const TreeDev tree,
         const int c = (int)blockIdx.x * kMarkCells + (int)threadIdx.x * (kMarkCells / 256) + i;
         if (c >= tree.n_occ_cells) break;
         if (lds)
-            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });
+            mark_cell(tree.occ_cells[2 * c], tree.occ_cells[2 * c + 1], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(&s_mask[w], bits); });
         else
-            mark_cell(tree.occ_cells[c], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(mask + w, bits); });
+            mark_cell(tree.occ_cells[2 * c], tree.occ_cells[2 * c + 1], tree, fd, fb, [&](uint32_t w, uint32_t bits) { atomicOr(mask + w, bits); });
     }
     if (lds) {
         __syncthreads();

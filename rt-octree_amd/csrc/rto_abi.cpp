@@ -499,6 +499,8 @@ int rto_ctx_set_tuning(rto_ctx* c, const char* key, int value) {
         c->test_wide_bits = value;
     } else if (k == "cull") {  // empty-space culling of the batched path (1 = on; same pixels either way)
         c->cull_on = value != 0;
+    } else if (k == "cull_cubes") {  // A/B and test hook: culling cells as whole cubes, not the bounds of their dense leaves (more marks, same pixels)
+        c->cull_cubes = value != 0;
     } else if (k == "cull_single") {  // rto_launch_renderer's fast kernel skips the tiles no culling cell projects into (same pixels)
         c->cull_single = value != 0;
     } else if (k == "frame_via_batch") {  // rto_launch_renderer as a batch of one (culling + tile marks); same pixels

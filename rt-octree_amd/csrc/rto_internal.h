@@ -36,6 +36,7 @@ struct rto_tree {
     void* d_shrec = nullptr;  // aligned copy of the SH coefficients (shading)
     void* d_recidx = nullptr; // RTO_TREE_COMPACT_RECORDS: slot -> record of d_shrec
     void* d_occ = nullptr;    // culling cells (TreeDev::occ_cells)
+    void* d_occ_cubes = nullptr;  // the same cells as whole cubes (tuning "cull_cubes" renders with these for occ_cells)
     void* d_qrec = nullptr;
     void* d_qcolors = nullptr;
     void* d_qsigma = nullptr;
@@ -85,6 +86,7 @@ struct rto_ctx {
     uint32_t* qscratch = nullptr;         // chunk_count | chunk_base | qcount
     int mask_words = 0, q_chunks_cap = 0;
     bool cull_on = true;
+    bool cull_cubes = false;              // tuning "cull_cubes": mark from the cells' whole cubes (rto_tree::d_occ_cubes), the rule before the bounds
     bool frame_via_batch = false;
     int last_n_queues = 0;                // of the last batched launch (rto_ctx_queue_stats)
     int64_t last_slots = 0;

@@ -75,12 +75,13 @@ struct TreeDev {
     // and per quantised basis function a 65536-entry codebook of {r, g, b, 0} fp16 (8 B entries).
     // Same bytes as quant_map + data_retained of the file, slot-major so that one hit leaf touches
     // one or two cache lines instead of one per basis function.
-    // Empty-space culling (round 3): the cubes, no finer than kOccLevel, that together contain every leaf of positive
-    // density, as {x, y, z, h}: the centre in WORLD coordinates and the half-edge in TREE units (half the cube + a margin far
-    // above the float error of a ray's sample points); the box's world half-widths are h / |scale|.  mark_tiles_kernel projects
-    // them into each frame: an 8x8-pixel tile that no box touches holds only rays that can never meet density -- background
-    // pixels, known without marching.
-    const float4* occ_cells;
+    // Empty-space culling (round 3): boxes that together contain every leaf of positive density -- a dense leaf no finer than
+    // kOccLevel (its cube), or the bounds of the dense leaves below one node of that level -- as two float4 per cell,
+    // {x, y, z, -} {hx, hy, hz, -}: the centre in WORLD coordinates and the half-extents in TREE units (half the bounds + a
+    // margin far above the float error of a ray's sample points); the box's world half-widths are h / |scale|.
+    // mark_tiles_kernel projects them into each frame: an 8x8-pixel tile that no box touches holds only rays that can never
+    // meet density -- background pixels, known without marching.
+    const float4* occ_cells;  // [2 * n_occ_cells]
     int n_occ_cells;  // (0 with occ_cells != nullptr: a tree without density; occ_cells == nullptr: no culling)
     const uint16_t* qrec;
     // One field, two uses that never meet (quantised trees render directly only as SH): TreeDev travels as a kernel argument,

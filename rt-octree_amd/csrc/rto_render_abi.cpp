@@ -359,6 +359,7 @@ int launch_batch_at(const rto_tree* tree, const rto_camera* cams, const int64_t*
     // non-negative density threshold (a hit needs sigma > sigma_thresh, rt_core.cuh:252) and straight world-space rays
     // (the NDC warp of LLFF scenes bends them: maybe_world2ndc, volrend.cu:35-56)
     const bool cull = ctx->cull_on && tree->dev.occ_cells && o->sigma_thresh >= 0.f && !(tree->dev.ndc_width > 0.f);
+    if (ctx->cull_cubes && tree->d_occ_cubes) tdev.occ_cells = (const float4*)tree->d_occ_cubes;
     rto::FrameDesc frames[rto::kMaxBatch];
     fb.f = ctx->d_frames;
     fb.lean = o->denoise ? ctx->lean : 0;
@@ -463,6 +464,7 @@ int rto_launch_renderer(const rto_tree* tree, const rto_camera* cam, const rto_o
     if (cull_one) {
         rc = ensure_tile_buffers(ctx, mask_words_of(ctx), 0);
         if (rc != RTO_OK) return rc;
+        if (ctx->cull_cubes && tree->d_occ_cubes) tdev.occ_cells = (const float4*)tree->d_occ_cubes;
         HIP_TRY(rto::launch_mark_tiles_one(tdev, cd, ctx->tile_mask, ctx->mask_words, stream));
         fo.cull_marks = ctx->tile_mask;
         fo.cull_mask_words = ctx->mask_words;

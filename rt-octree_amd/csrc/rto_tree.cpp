@@ -164,14 +164,15 @@ int build_nodew(rto_tree* t, const HostArrays& h) {
 // culling cells for the batched path (see TreeDev::occ_cells)
 int upload_culling_cells(rto_tree* t, const HostArrays& h, const float scale[3], const float offset[3]) {
     if (!t->fast_ok || (t->flags & RTO_TREE_NO_CULLING)) return RTO_OK;
-    std::vector<float> cells;
-    if (!rto::culling_cells(h.child, h.capacity, scale, offset, h.sigma, h.sigma_stride, cells)) return RTO_OK;
-    const size_t bytes = cells.empty() ? 16 : cells.size() * sizeof(float);
-    if (!tree_alloc(t, &t->d_occ, bytes) ||
-        (!cells.empty() && hipMemcpy(t->d_occ, cells.data(), cells.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
-        return set_err(RTO_E_HIP, "hipMalloc(culling cells) failed");
+    std::vector<float> cells, cubes;  // (cubes: the same cells as whole cubes, for tuning "cull_cubes")
+    if (!rto::culling_cells(h.child, h.capacity, scale, offset, h.sigma, h.sigma_stride, cells, &cubes)) return RTO_OK;
+    const size_t bytes = cells.empty() ? 32 : cells.size() * sizeof(float);
+    auto up = [&](void** dst, const std::vector<float>& src) {
+        return tree_alloc(t, dst, bytes) && (src.empty() || hipMemcpy(*dst, src.data(), bytes, hipMemcpyHostToDevice) == hipSuccess);
+    };
+    if (!up(&t->d_occ, cells) || !up(&t->d_occ_cubes, cubes)) return set_err(RTO_E_HIP, "hipMalloc(culling cells) failed");
     t->dev.occ_cells = (const float4*)t->d_occ;
-    t->dev.n_occ_cells = (int)(cells.size() / 4);
+    t->dev.n_occ_cells = (int)(cells.size() / 8);
     return RTO_OK;
 }
 
@@ -592,7 +593,7 @@ void rto_tree_free(rto_tree* t) {
     if (!t) return;
     DeviceGuard guard(t->device);
     for (void* p : {t->d_data, t->d_child, t->d_nodew, t->d_topgrid, t->d_widew, t->d_worig, t->d_grid2, t->d_shrec, t->d_recidx, t->d_occ,
-                    t->d_qrec, t->d_qcolors, t->d_qsigma, t->d_extra})
+                    t->d_occ_cubes, t->d_qrec, t->d_qcolors, t->d_qsigma, t->d_extra})
         if (p) (void)hipFree(p);
     delete t;
 }

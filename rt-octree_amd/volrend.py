@@ -461,7 +461,7 @@ class RenderContext:
         return self._timer
 
     def set_tuning(self, key, value):
-        """performance knobs ("strip_rows", "refill", "tile_order", "xcd_queues", "tile_major", "tile_block", "blocks_per_cu", "cull", "cull_single");
+        """performance knobs ("strip_rows", "refill", "tile_order", "xcd_queues", "tile_major", "tile_block", "blocks_per_cu", "cull", "cull_cubes", "cull_single");
         results never change"""
         check(lib().rto_ctx_set_tuning(self._h, key.encode("ascii"), int(value)))
 
