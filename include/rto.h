@@ -896,6 +896,56 @@ int rto_tree_simplify_host(const int32_t* child, const uint16_t* data, int64_t c
                            int32_t* child_out, uint16_t* data_out, int64_t* out_capacity, int64_t* node_map,
                            rto_simplify_stats* stats);
 
+/* ---- leaf weights (the pruning criterion of PlenOctree extraction: render every training view, record for every leaf the largest
+ * compositing weight any ray gives it, drop the leaves that stay under a threshold; the reference holds no counterpart) ----
+ * A dense leaf buried behind an opaque surface has a large sigma and weight 0: no density threshold finds it, this does.
+ *   weights  one word per slot of child[]: indexed like child[capacity][N][N][N], flattened, in the numbering of the arrays the
+ *            tree was uploaded from (the slot query_single_from_root names) -- whichever traversal image is resident, and also
+ *            when child[] has been released.  A word is the bit pattern of a float in [0, 1].  The call ACCUMULATES into what
+ *            weights holds (max); the caller zeroes it.
+ *   rays     For every camera k of the call and every pixel 0 <= x < width, 0 <= y < height the renderer's own ray: set up as
+ *            the frame kernels set it up (volrend.cu:23-56,138-144, the NDC warp of an NDC tree included), entered as they enter
+ *            the volume with tmax_bg = 1e9f (rt_core.cuh:206-222: double sub-expressions, render_bbox +- 1e-6, delta_scale).  A
+ *            ray is not marched when a component of dir or cen is not finite after the set-up, or when it misses the box.
+ *   march    float32, every operation rounded once, no contraction:
+ *                T = 1.f;  t = tmin
+ *                while (t < tmax):
+ *                    pos   = cen + t * dir
+ *                    leaf, cube_sz, local = query_single_from_root(pos)          (its clamp to [0, 1 - 1e-6f] included)
+ *                    dt    = _dda_unit(local, invdir) / cube_sz + step_size
+ *                    sigma = (float)(the density half of leaf)
+ *                    if (sigma > sigma_thresh):                                   (a NaN density is skipped)
+ *                        att = fminf(expf(-((dt * delta_scale) * sigma)), 1.f)    (expf: the library's deterministic one, full range)
+ *                        w   = T * (1.f - att)
+ *                        weights[leaf] = max(weights[leaf], w)
+ *                        T   = T * att
+ *                        if (T < stop_thresh) break
+ *                    tn = t + dt
+ *                    if (!(tn > t)) break         (a step that does not advance ends the ray: no input makes the loop endless)
+ *                    t = tn
+ *            -- the bookkeeping of the shader backend's trace (rt.frag:244-321) without its colour, on the CUDA backend's ray.
+ *            Of rto_options only step_size, sigma_thresh, stop_thresh and render_bbox are read (spp is not validated);
+ *            stop_thresh = 0 never stops a ray.
+ *   max      w is never NaN and never negative (att lies in [0, 1], T >= 0; an infinite sigma gives att = 0), so the words are
+ *            compared as unsigned integers: the result does not depend on the order of the rays, on how the cameras are split
+ *            over calls, or on the thread count.  The device entry, the host twin and the numpy restatement of the tests give
+ *            the same bits.
+ * rto_tree_leaf_weights: asynchronous on `stream`; no allocation, no host synchronisation, no host-to-device copy (the cameras
+ * travel in the kernel arguments, 32 per launch; a launch takes a run of consecutive cameras of one size, so mixed sizes are
+ * accepted); n == 0 launches nothing.  Only sigma is read: quantised-direct and compact-records trees work.  The kernel walks what
+ * the tree has resident (the two-level image, the one-level image, or child[] with the float descent); a tree that has neither an
+ * image nor child[] / data[] resident is RTO_E_UNSUPPORTED.
+ * RTO_E_INVALID, decided before anything is enqueued: a null pointer; n < 0; a camera with width or height < 1 (height at most
+ * 1048560), fx or fy not finite or zero; weights not 4-byte aligned; on the device entry weights not memory of the tree's device.
+ * rto_leaf_weights_host is the host twin: host pointers, no device; the root-restart float descent over child[] (links are checked
+ * first: RTO_E_FORMAT for an offset outside [1, capacity) or a node reached twice); threads <= 0 means one thread, and the result
+ * does not depend on threads. */
+int rto_tree_leaf_weights(const rto_tree* tree, const rto_camera* cams /* host [n] */, int n, const rto_options* opt,
+                          uint32_t* weights /* device [capacity * N^3] */, void* stream);
+int rto_leaf_weights_host(const int32_t* child, const uint16_t* data, int64_t capacity, int N, int data_dim,
+                          const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
+                          const rto_camera* cams, int n, const rto_options* opt, int threads, uint32_t* weights);
+
 /* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
  * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
  * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that

@@ -14,6 +14,7 @@ from .meshes import Mesh, MeshSet, MeshParams, draw_mesh_layers, trace_mesh_rays
 from .metrics import FrameMetrics, ImageMetrics, read_png  # noqa: F401
 from .quantize import Quantizer, quantize_median_cut  # noqa: F401
 from .simplify import Simplifier, simplify_tree  # noqa: F401
+from .visibility import leaf_weights, leaf_weights_host, kill_unseen  # noqa: F401
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
@@ -23,4 +24,5 @@ __all__ = [
     "Mesh", "MeshSet", "MeshParams", "draw_mesh_layers", "trace_mesh_rays", "MESH_MERGE",
     "FrameMetrics", "ImageMetrics", "read_png",
     "Quantizer", "quantize_median_cut", "Simplifier", "simplify_tree",
+    "leaf_weights", "leaf_weights_host", "kill_unseen",
 ]

@@ -230,6 +230,9 @@ SYMBOLS = {
                                     C.POINTER(CSimplifyStats)]),
     "rto_tree_simplify_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P, C.POINTER(C.c_int64), _P,
                                          C.POINTER(CSimplifyStats)]),
+    "rto_tree_leaf_weights": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(COptions), _P, _P]),
+    "rto_leaf_weights_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float), C.POINTER(CCamera), C.c_int, C.POINTER(COptions), C.c_int, _P]),
     "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_guidance_train_free": (None, [_P]),
     "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

@@ -41,6 +41,9 @@ struct rto_tree {
     void* d_qcolors = nullptr;
     void* d_qsigma = nullptr;
     void* d_extra = nullptr;  // SG / ASG lobes (TreeDev::extra)
+    // the upload re-laid the nodes breadth-first: node_old[n] (uint32) = the index node n has in the arrays the tree was uploaded
+    // from, which per-slot outputs of the caller's numbering go by (rto_tree_leaf_weights); nullptr: the order is the same
+    void* d_node_old = nullptr;
     bool quant = false;  // rendered from the codebooks; only the batched path can shade it
     int flags = 0;       // the RTO_TREE_* flags of the upload
     bool fast_ok = false;

@@ -73,12 +73,13 @@ int validate_upload(const int32_t* child, const uint16_t* data, int64_t capacity
 
 // Re-lay the tree breadth-first unless the file already is (derived layout: every query returns the same
 // leaf values, so no pixel can change -- tests/test_render_parity.py::test_node_order_never_changes_pixels)
-void relay_breadth_first(HostArrays& h, rto::Relaid& relaid, rto::HostTree& quant_relaid) {
+// -> order[new] = old, empty when the file's order stays
+std::vector<int64_t> relay_breadth_first(HostArrays& h, rto::Relaid& relaid, rto::HostTree& quant_relaid) {
     const int64_t N3 = h.n_slots / h.capacity;
     const std::vector<int64_t> order = rto::bfs_order(h.child, h.capacity, N3);
     bool identity = true;
     for (int64_t n = 0; n < h.capacity && identity; ++n) identity = order[(size_t)n] == n;
-    if (identity) return;
+    if (identity) return {};
     rto::relay_tree(order, h.child, h.data, h.capacity, N3, h.data_dim, h.quant, relaid);
     h.child = relaid.child.data();
     if (h.data) h.data = relaid.data.data();
@@ -89,6 +90,7 @@ void relay_breadth_first(HostArrays& h, rto::Relaid& relaid, rto::HostTree& quan
         quant_relaid.q_retained = relaid.q_retained.empty() ? nullptr : relaid.q_retained.data();
         h.quant = &quant_relaid;
     }
+    return order;
 }
 
 // child[] first, for either kind of tree
@@ -356,7 +358,7 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
     HostArrays h = {child, data, quant, nullptr, 0, capacity, capacity * N * N * N, N, data_dim, max_depth};
     rto::Relaid relaid;
     rto::HostTree quant_relaid;
-    relay_breadth_first(h, relaid, quant_relaid);
+    const std::vector<int64_t> node_old = relay_breadth_first(h, relaid, quant_relaid);
     h.sigma = h.quant ? h.quant->q_sigma : h.data + data_dim - 1;
     h.sigma_stride = h.quant ? 1 : (size_t)data_dim;
 
@@ -371,6 +373,12 @@ int upload_tree(const int32_t* child, const uint16_t* data, int64_t capacity, in
     if (rc == RTO_OK) rc = upload_lobes(t, extra, extra_floats);
     if (rc == RTO_OK) rc = build_records(t, h, fmt);
     if (rc == RTO_OK) release_upload_only_arrays(t, h);
+    if (rc == RTO_OK && !node_old.empty()) {  // the caller's node numbering, for per-slot outputs (rto_tree_leaf_weights)
+        const std::vector<uint32_t> old32(node_old.begin(), node_old.end());
+        if (!tree_alloc(t, &t->d_node_old, old32.size() * sizeof(uint32_t)) ||
+            hipMemcpy(t->d_node_old, old32.data(), old32.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+            rc = set_err(RTO_E_HIP, "tree upload failed");
+    }
     if (rc == RTO_OK && h.quant && !t->fast_ok)
         rc = set_err(RTO_E_UNSUPPORTED, "direct rendering of quantised trees needs the N == 2 traversal image");
     if (rc != RTO_OK) {
@@ -593,7 +601,7 @@ void rto_tree_free(rto_tree* t) {
     if (!t) return;
     DeviceGuard guard(t->device);
     for (void* p : {t->d_data, t->d_child, t->d_nodew, t->d_topgrid, t->d_widew, t->d_worig, t->d_grid2, t->d_shrec, t->d_recidx, t->d_occ,
-                    t->d_occ_cubes, t->d_qrec, t->d_qcolors, t->d_qsigma, t->d_extra})
+                    t->d_occ_cubes, t->d_qrec, t->d_qcolors, t->d_qsigma, t->d_extra, t->d_node_old})
         if (p) (void)hipFree(p);
     delete t;
 }
