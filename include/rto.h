@@ -946,6 +946,58 @@ int rto_leaf_weights_host(const int32_t* child, const uint16_t* data, int64_t ca
                           const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
                           const rto_camera* cams, int n, const rto_options* opt, int threads, uint32_t* weights);
 
+/* ---- grid builder (the first step of PlenOctree extraction: a field evaluated on a regular grid becomes an octree; svox does
+ * it on the CPU, the reference holds no counterpart) ----
+ * Builds child[] / data[] (N = 2) from a dense grid of records.  The result is the tree the simplifier leaves of the grid's full
+ * octree: grid -> tree -> rto_tree_query at the voxel centres returns the grid's bits (+0 in all D halves where a voxel was
+ * killed).
+ *   input    grid[R][R][R][D], fp16 bit patterns, R = 2^L with 1 <= L <= 10, D >= 1; the density is the last of the D halves, as
+ *            in data[].  grid[i][j][k] is the voxel that covers the tree coordinates [i/R,(i+1)/R) x [j/R,(j+1)/R) x
+ *            [k/R,(k+1)/R): the first index is x, the axis order of child[n][i][j][k] (slot 4 i + 2 j + k).  kill_thresh: a
+ *            float, NaN = no kill.  Every index into the grid is 64-bit.
+ *   kill     The simplifier's rule: th = kill_thresh rounded to fp16 (to nearest even, beyond 65504 an infinity); a voxel whose
+ *            density half d is not IEEE d > th is DEAD (a NaN density is dead; -0 == +0) and its record counts as D halves +0.
+ *   cells    The cell of level l (0 <= l <= L) with Morton code m covers 2^(L-l) voxels per side; m holds three bits per level, x
+ *            the most significant of each triple, so the children of cell m are the cells 8 m + slot of level l + 1.  A cell of
+ *            level L (a voxel) is UNIFORM.  A cell of level 1 <= l < L is uniform when its eight children are uniform and
+ *            their records (after the kill) are equal bit for bit: +0 and -0 differ, two NaNs with the same bits are equal.  A
+ *            uniform cell's record is the record of its min-corner voxel.
+ *   tree     The root (level 0) is always node 0, even over a uniform grid.  Nodes are numbered breadth-first: all nodes of
+ *            level l before any of level l + 1, within a level by Morton code.  Slot s of the node of cell m at level l looks at
+ *            cell 8 m + s of level l + 1: uniform -> child = 0 and the slot holds that cell's record; not uniform -> child is
+ *            the relative offset to that cell's node and the slot holds D halves +0 (no averaged level-of-detail records).
+ *   stats    nodes; killed: dead voxels, whatever they held; levels: 1 + the deepest level of a node.
+ * Nothing is left to the implementation: the device entries, the host twin and the numpy model of the tests give the same
+ * bytes, and they are the bytes rto_tree_simplify gives for the grid's full octree (every cell subdivided to level L,
+ * breadth-first in Morton order, interior slots zero) with the same kill_thresh.
+ * Two passes, because the outputs cannot be sized before the grid has been read.  rto_tree_build_plan reads the grid once,
+ * leaves the flags of all cells and the node lists of all levels in the handle, synchronises `stream` once to read the counts back
+ * and sets *out_capacity = nodes (also when it refuses the result as too large).  rto_tree_build_write enqueues the kernels that
+ * write child_out[nodes][2][2][2] and data_out[nodes][2][2][2][D] of the handle's last successful plan and returns without
+ * waiting; the grid must be unchanged and stay alive until they have run.  A TOOL path like rto_tree_simplify: kernel
+ * boundaries are the only grid-wide synchronisation, integer counts the only atomics, the scans are reduce-then-scan: two runs
+ * give the same bytes.  The handle owns all scratch -- one flag byte per cell of levels 0 .. L - 1, one 32-bit Morton code per
+ * possible node of those levels and a word per 256 of them: 5/7 of a byte per VOXEL (0.72), independent of D and of the node
+ * count; pass 2 needs none per node -- which grows on demand and is reused; growing synchronises the device once.
+ * One handle serves one stream at a time.  A data_out aligned to 16 bytes is written in 16-byte words, another half by half.
+ * RTO_E_INVALID, decided before anything is enqueued: a null pointer (stats may be NULL), L outside 1 .. 10, D < 1, a pointer
+ * not aligned to its element, an output that overlaps the grid or the other output, grid / child_out / data_out not memory of
+ * the handle's device (out_capacity and stats are host memory), rto_tree_build_write without a preceding successful plan on the
+ * handle.  A result with nodes * 8 >= 2^31 (the simplifier's bound on a tree) is refused by the plan, with a text.
+ * rto_tree_build_host is the host twin: host pointers, no handle, no device.  child_out == data_out == NULL counts only; `room` =
+ * the nodes the outputs can hold -- too small is RTO_E_INVALID with *out_capacity and *stats set all the same. */
+typedef struct rto_grid_build_stats {
+    int64_t nodes, killed, levels;
+} rto_grid_build_stats;
+typedef struct rto_tree_builder rto_tree_builder;
+int rto_tree_builder_create(int device, rto_tree_builder** out);
+void rto_tree_builder_free(rto_tree_builder* b);
+int rto_tree_build_plan(rto_tree_builder* b, void* stream, const uint16_t* grid /* device */, int L, int D, float kill_thresh,
+                        int64_t* out_capacity /* host */, rto_grid_build_stats* stats /* host, or NULL */);
+int rto_tree_build_write(rto_tree_builder* b, void* stream, int32_t* child_out, uint16_t* data_out);
+int rto_tree_build_host(const uint16_t* grid, int L, int D, float kill_thresh, int32_t* child_out, uint16_t* data_out,
+                        int64_t room, int64_t* out_capacity, rto_grid_build_stats* stats);
+
 /* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
  * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
  * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that

@@ -15,6 +15,7 @@ from .metrics import FrameMetrics, ImageMetrics, read_png  # noqa: F401
 from .quantize import Quantizer, quantize_median_cut  # noqa: F401
 from .simplify import Simplifier, simplify_tree  # noqa: F401
 from .visibility import leaf_weights, leaf_weights_host, kill_unseen  # noqa: F401
+from .grid_build import TreeBuilder, build_tree, tree_to_grid  # noqa: F401
 
 __all__ = [
     "LIB_PATH", "RtoError", "build_library", "lib", "Camera", "N3Tree", "RenderContext",
@@ -25,4 +26,5 @@ __all__ = [
     "FrameMetrics", "ImageMetrics", "read_png",
     "Quantizer", "quantize_median_cut", "Simplifier", "simplify_tree",
     "leaf_weights", "leaf_weights_host", "kill_unseen",
+    "TreeBuilder", "build_tree", "tree_to_grid",
 ]

@@ -113,6 +113,11 @@ class CSimplifyStats(C.Structure):
                 ("levels", C.c_int64)]
 
 
+class CGridBuildStats(C.Structure):
+    """rto_grid_build_stats (include/rto.h)"""
+    _fields_ = [("nodes", C.c_int64), ("killed", C.c_int64), ("levels", C.c_int64)]
+
+
 # every symbol include/rto.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -233,6 +238,12 @@ SYMBOLS = {
     "rto_tree_leaf_weights": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(COptions), _P, _P]),
     "rto_leaf_weights_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.POINTER(CCamera), C.c_int, C.POINTER(COptions), C.c_int, _P]),
+    "rto_tree_builder_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_tree_builder_free": (None, [_P]),
+    "rto_tree_build_plan": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(CGridBuildStats)]),
+    "rto_tree_build_write": (C.c_int, [_P, _P, _P, _P]),
+    "rto_tree_build_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int64, C.POINTER(C.c_int64),
+                                      C.POINTER(CGridBuildStats)]),
     "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_guidance_train_free": (None, [_P]),
     "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
