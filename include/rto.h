@@ -946,6 +946,84 @@ int rto_leaf_weights_host(const int32_t* child, const uint16_t* data, int64_t ca
                           const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
                           const rto_camera* cams, int n, const rto_options* opt, int threads, uint32_t* weights);
 
+/* ---- tree fit (the last step of PlenOctree extraction: the leaf values are optimised against the training images by gradient
+ * descent on a fixed structure, PlenOctrees' octree/optimization.py; the reference renderer holds no counterpart) ----
+ * The images are rendered by deterministic compositing (a transmittance T, no RNG), the loss is 1/2 sum over rays |out - target|^2,
+ * and its gradient with respect to the leaf values is accumulated in 64-bit FIXED POINT, so that no order can change a bit.
+ *   params   float32 [capacity][N][N][N][D], D = data_dim, in the numbering of the arrays the tree was uploaded from: indexed like
+ *            weights[] of the leaf weights, times D.  The tree handle gives the TOPOLOGY and the SUPPORT, params the field.
+ *   support  A leaf is DENSE when its uploaded density half is > sigma_thresh AND params[slot][D-1] > sigma_thresh (a NaN fails
+ *            either test).  A leaf that is not dense is stepped over and never receives a gradient: the support can shrink and
+ *            never grows.  The first test is free on the image walks (the walk returns the half), so only a dense leaf pays for
+ *            its address.
+ *   formats  RGBA (D = 4) and SH with basis_dim B in {1, 4, 9, 16, 25} (D = 3 B + 1).  RTO_E_UNSUPPORTED: SG / ASG trees, trees
+ *            loaded with RTO_TREE_QUANT_DIRECT or RTO_TREE_COMPACT_RECORDS, a tree with neither an image nor child[] / data[]
+ *            resident.
+ *   ray      that of the leaf weights, word for word: the set-up (NDC warp included), the entry with tmax_bg = 1e9f, the loop and
+ *            the three ways it ends (t >= tmax, T < stop_thresh, a step that does not advance).  A ray whose set-up is not finite
+ *            or that misses the box is not marched: out = bg.  Of rto_options step_size, sigma_thresh, stop_thresh, render_bbox
+ *            and background_brightness (bg) are read; rot_dirs and basis_minmax are NOT, and a call with non-default values of
+ *            either is RTO_E_INVALID.
+ *   colour   c[ch] of a dense leaf, p = params[slot]:  RGBA: p[ch].  SH: Y = the tree's SH basis (lumisphere.hpp:38-80: double
+ *            literals, one rounding per assignment) at vdir, the unit direction of the set-up before the NDC warp and before the
+ *            entry scales it;  z = Y[0] * p[ch*B];  z = z + Y[k] * p[ch*B + k] for k = 1 .. B-1;  c[ch] = 1.f / (1.f + expf(-z)),
+ *            expf the library's deterministic one (the probe's colour, above).
+ *   forward  float32, every operation rounded once, no contraction:
+ *                T = 1.f;  acc[ch] = 0.f;  t = tmin
+ *                while (t < tmax):
+ *                    pos, leaf, cube_sz, local, dt       as the leaf weights
+ *                    if (dense):   sigma = p[D-1]
+ *                        delta = dt * delta_scale
+ *                        att   = fminf(expf(-(delta * sigma)), 1.f)
+ *                        w     = T * (1.f - att)
+ *                        acc[ch] = acc[ch] + w * c[ch]
+ *                        T = T * att;  if (T < stop_thresh) break
+ *                    tn = t + dt;  if (!(tn > t)) break;  t = tn
+ *                out[ch] = acc[ch] + T * bg
+ *                r[ch] = out[ch] - target[ch];   loss_ray = (r[0]*r[0] + r[1]*r[1]) + r[2]*r[2]
+ *            A pixel whose target holds a NaN in any channel is MASKED: not marched, not counted, no loss, no gradient, and its
+ *            image pixel is not written.
+ *   backward the ray is marched a second time by the same operations, so T, att, w, c and acc repeat bit for bit.  At a dense
+ *            sample, with acc the accumulator AFTER the sample and T the transmittance BEFORE it:
+ *                g[D-1] = delta * s,   s = r[0] * x[0];  s = s + r[1] * x[1];  s = s + r[2] * x[2],
+ *                                      x[ch] = (T * att) * c[ch] - (out[ch] - acc[ch])
+ *                gc = r[ch] * w;   RGBA: g[ch] = gc;   SH: gz = gc * (c[ch] * (1.f - c[ch])),  g[ch*B + k] = gz * Y[k]
+ *            The clamp in att and the early stop are treated as constants.
+ *   sums     grad is int64 with the shape of params.  A contribution g enters as q = (int64_t)rint((double)g' * 2^36) (to nearest
+ *            even), g' = 0 for a NaN g, else g clamped to +-2^16 -- so |q| <= 2^52 and the product, the rounding and the
+ *            conversion are exact -- added with a wrapping 64-bit integer add.  stats[0] += q(loss_ray) in the same way;
+ *            stats[1] += 1 per unmasked ray (the rays that are not marched included).  Integer adds commute and associate: the
+ *            words do not depend on the order of the rays, on how the cameras are split over calls, on thread counts or on any
+ *            pre-reduction.  The device entry, the host twin and the numpy restatement of the tests give the same bytes.
+ *            Headroom (a choice, not a measurement): 2^-36 = 1.5e-11 per contribution, against SH gradients bounded by about
+ *            |r| w / 4 |Y| < 1; a word takes 2^27 contributions of magnitude 1 before it wraps.
+ *   step     p = p - lr * g,  g = (float)((double)q * 2^-36): two float roundings, no FMA; then the grad word is zeroed.
+ *            Elementwise over the whole array.  The entry takes no normaliser: fold 2 / (3 rays) of a mean squared error into lr.
+ * rto_tree_fit_grad: asynchronous on `stream`; no allocation, no host synchronisation, no host-to-device copy (cameras, targets
+ * and images travel in the kernel arguments, 32 per launch; runs of one size become launches); n == 0 launches nothing.  images:
+ * NULL, or per camera NULL or where out is written.  grad == NULL: only the forward march runs -- the deterministic render of the
+ * field.  targets may be NULL only with grad == NULL and stats == NULL (nothing is masked then).  The call ACCUMULATES into grad
+ * and stats; the caller zeroes them.
+ * RTO_E_INVALID, decided before anything is enqueued, with a text naming the argument and the camera: a null tree, params,
+ * options, cams with n > 0, or targets[k]; n < 0; the camera checks of the leaf weights; params, targets[k] or images[k] not
+ * 4-byte aligned, grad or stats not 8-byte aligned; params or grad overlapping a target or an image; on the device entry any of
+ * them not memory of the tree's device.
+ * rto_fit_sgd_step: asynchronous; params and grad (count elements each) memory of one device.
+ * rto_fit_grad_host / rto_fit_sgd_step_host are the host twins: host pointers, no device; `data` (fp16 bits) gives the support,
+ * data_format is "RGBA" or "SH<B>"; links are checked as rto_leaf_weights_host checks them; the result does not depend on
+ * threads. */
+int rto_tree_fit_grad(const rto_tree* tree, const float* params, const rto_camera* cams /* host [n] */,
+                      const float* const* targets /* host [n] of device [H][W][3] f32 */,
+                      float* const* images /* host [n] of device [H][W][3] f32, or NULL; entries may be NULL */, int n,
+                      const rto_options* opt, int64_t* grad /* or NULL: forward only */, uint64_t* stats /* device [2] or NULL */,
+                      void* stream);
+int rto_fit_sgd_step(float* params, int64_t* grad, int64_t count, float lr, void* stream);
+int rto_fit_grad_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int data_dim,
+                      const char* data_format, const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
+                      const rto_camera* cams, const float* const* targets, float* const* images, int n, const rto_options* opt,
+                      int threads, int64_t* grad, uint64_t* stats);
+int rto_fit_sgd_step_host(float* params, int64_t* grad, int64_t count, float lr);
+
 /* ---- grid builder (the first step of PlenOctree extraction: a field evaluated on a regular grid becomes an octree; svox does
  * it on the CPU, the reference holds no counterpart) ----
  * Builds child[] / data[] (N = 2) from a dense grid of records.  The result is the tree the simplifier leaves of the grid's full

@@ -238,6 +238,12 @@ SYMBOLS = {
     "rto_tree_leaf_weights": (C.c_int, [_P, C.POINTER(CCamera), C.c_int, C.POINTER(COptions), _P, _P]),
     "rto_leaf_weights_host": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.POINTER(CCamera), C.c_int, C.POINTER(COptions), C.c_int, _P]),
+    "rto_tree_fit_grad": (C.c_int, [_P, _P, C.POINTER(CCamera), C.POINTER(_P), C.POINTER(_P), C.c_int, C.POINTER(COptions), _P, _P, _P]),
+    "rto_fit_sgd_step": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
+    "rto_fit_grad_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.POINTER(CCamera), C.POINTER(_P), C.POINTER(_P), C.c_int,
+                                    C.POINTER(COptions), C.c_int, _P, _P]),
+    "rto_fit_sgd_step_host": (C.c_int, [_P, _P, C.c_int64, C.c_float]),
     "rto_tree_builder_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_tree_builder_free": (None, [_P]),
     "rto_tree_build_plan": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(CGridBuildStats)]),

@@ -24,10 +24,8 @@ std::string leaf_weights_check_cams(const rto_camera* cams, int n, const void* w
     return "";
 }
 
-namespace {
-
 // every link of the walk from the root stays inside [1, capacity) and no node is reached twice
-std::string check_links(const int32_t* child, int64_t capacity, int64_t N3) {
+std::string leaf_weights_check_links(const int32_t* child, int64_t capacity, int64_t N3) {
     std::vector<uint8_t> seen((size_t)capacity, 0);
     std::vector<int64_t> stack{0};
     seen[0] = 1;
@@ -48,6 +46,8 @@ std::string check_links(const int32_t* child, int64_t capacity, int64_t N3) {
     }
     return "";
 }
+
+namespace {
 
 void atomic_max_u32(uint32_t* p, uint32_t v) {
     uint32_t cur = __atomic_load_n(p, __ATOMIC_RELAXED);
@@ -70,7 +70,7 @@ int leaf_weights_host(const int32_t* child, const uint16_t* data, int64_t capaci
     if (capacity > (((int64_t)1 << 31) - 1) / N3) return fail(RTO_E_INVALID, "capacity * N^3 must stay below 2^31");
     const std::string bad = leaf_weights_check_cams(cams, n, weights);
     if (!bad.empty()) return fail(RTO_E_INVALID, bad);
-    const std::string links = check_links(child, capacity, N3);
+    const std::string links = leaf_weights_check_links(child, capacity, N3);
     if (!links.empty()) return fail(RTO_E_FORMAT, links);
     if (n == 0) return RTO_OK;
 

@@ -12,6 +12,9 @@ namespace rto {
 // "" or what is wrong with the cameras / the weights pointer of a call (checked before anything is enqueued or marched)
 std::string leaf_weights_check_cams(const rto_camera* cams, int n, const void* weights);
 
+// "" or what is wrong with child[]: a link of the walk from the root outside [1, capacity), or a node reached twice
+std::string leaf_weights_check_links(const int32_t* child, int64_t capacity, int64_t N3);
+
 // The march over child[] / data[] with the root-restart float descent, `threads` threads (<= 0: one) over the rows of each
 // camera; weights (capacity * N^3 words) is accumulated into with an atomic unsigned max: the result does not depend on
 // `threads`.  ndc: {width, height, focal} or nullptr.  RTO_OK, or RTO_E_INVALID / RTO_E_FORMAT with *err set; child[] is

@@ -1,0 +1,102 @@
+// rto_fit_abi.cpp -- C ABI of the tree fit (include/rto.h "tree fit"): the device entries (fit_kernels.hip) and the host twins
+// (host/fit_grad.cpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "host/fit_grad.h"
+#include "rto_fit_launch.h"
+#include "rto_internal.h"
+
+extern "C" {
+
+int rto_tree_fit_grad(const rto_tree* tree, const float* params, const rto_camera* cams, const float* const* targets, float* const* images,
+                      int n, const rto_options* opt, int64_t* grad, uint64_t* stats, void* stream) {
+    const std::string w = "rto_tree_fit_grad: ";
+    if (!tree) return set_err(RTO_E_INVALID, w + "null tree");
+    const rto_tree_info& ti = tree->info;
+    const int basis = rto::fit_basis_of_tree(ti.format, ti.basis_dim, ti.data_dim);
+    if (basis < 0) return set_err(RTO_E_UNSUPPORTED, w + "the fit takes RGBA and SH trees of basis_dim 1, 4, 9, 16 or 25");
+    if (tree->quant) return set_err(RTO_E_UNSUPPORTED, w + "a tree loaded with RTO_TREE_QUANT_DIRECT has no leaf values to fit");
+    if (tree->d_recidx) return set_err(RTO_E_UNSUPPORTED, w + "a tree loaded with RTO_TREE_COMPACT_RECORDS is not taken");
+    int walk;
+    rto::ValuesSrc vs;
+    (void)query_plan(tree, false, &walk, &vs);
+    if (walk == rto::kWalkChild && !(tree->dev.child && tree->dev.data))
+        return set_err(RTO_E_UNSUPPORTED, w + "the tree has neither a traversal image nor child[] / data[] resident");
+    const int64_t count = ti.capacity * tree->dev.N3 * ti.data_dim;
+    const std::string bad = rto::fit_check_call(params, cams, targets, images, n, opt, grad, stats, count);
+    if (!bad.empty()) return set_err(RTO_E_INVALID, w + bad);
+    if (pointer_device(params) != tree->device) return set_err(RTO_E_INVALID, w + "params is not memory of the tree's device");
+    if (grad && pointer_device(grad) != tree->device) return set_err(RTO_E_INVALID, w + "grad is not memory of the tree's device");
+    if (stats && pointer_device(stats) != tree->device) return set_err(RTO_E_INVALID, w + "stats is not memory of the tree's device");
+    for (int f = 0; f < n; ++f) {
+        if (targets && pointer_device(targets[f]) != tree->device)
+            return set_err(RTO_E_INVALID, w + "camera " + std::to_string(f) + ": target is not memory of the tree's device");
+        if (images && images[f] && pointer_device(images[f]) != tree->device)
+            return set_err(RTO_E_INVALID, w + "camera " + std::to_string(f) + ": image is not memory of the tree's device");
+    }
+    if (n == 0) return RTO_OK;
+    DeviceGuard guard(tree->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    rto::fm::Opt o;
+    o.m.step_size = opt->step_size;
+    o.m.sigma_thresh = opt->sigma_thresh;
+    o.m.stop_thresh = opt->stop_thresh;
+    for (int i = 0; i < 6; ++i) o.m.render_bbox[i] = opt->render_bbox[i];
+    o.bg = opt->background_brightness;
+    // a launch takes a run of consecutive cameras of one size, at most kLayerCamChunk of them (the unused slots hold the first)
+    for (int f0 = 0; f0 < n;) {
+        int k = 1;
+        while (k < rto::kLayerCamChunk && f0 + k < n && cams[f0 + k].width == cams[f0].width && cams[f0 + k].height == cams[f0].height) ++k;
+        rto::LayerCams lc;
+        rto::FitPlanes pl;
+        for (int f = 0; f < rto::kLayerCamChunk; ++f) {
+            const int g = f0 + (f < k ? f : 0);
+            lc.c[f] = cam_dev(cams[g]);
+            pl.target[f] = targets ? targets[g] : nullptr;
+            pl.image[f] = images ? images[g] : nullptr;
+        }
+        const hipError_t e = rto::launch_fit_grad(tree->dev, walk, basis, o, lc, pl, k, (const uint32_t*)tree->d_node_old, params, grad, stats,
+                                                  (hipStream_t)stream);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, w + "launch failed: " + hipGetErrorString(e));
+        f0 += k;
+    }
+    return RTO_OK;
+}
+
+int rto_fit_sgd_step(float* params, int64_t* grad, int64_t count, float lr, void* stream) {
+    const std::string w = "rto_fit_sgd_step: ";
+    if (!params || !grad) return set_err(RTO_E_INVALID, w + "null params or grad");
+    if (count < 0) return set_err(RTO_E_INVALID, w + "count must be >= 0");
+    if ((uintptr_t)params % 4 != 0 || (uintptr_t)grad % 8 != 0) return set_err(RTO_E_INVALID, w + "params must be 4-byte and grad 8-byte aligned");
+    const int dev = pointer_device(params);
+    if (dev < 0 || pointer_device(grad) != dev) return set_err(RTO_E_INVALID, w + "params and grad must be memory of one device");
+    if (count == 0) return RTO_OK;
+    DeviceGuard guard(dev);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    const hipError_t e = rto::launch_fit_sgd_step(params, grad, count, lr, (hipStream_t)stream);
+    if (e != hipSuccess) return set_err(RTO_E_HIP, w + "launch failed: " + hipGetErrorString(e));
+    return RTO_OK;
+}
+
+int rto_fit_grad_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int data_dim,
+                      const char* data_format, const float scale[3], const float offset[3], const float* ndc, const rto_camera* cams,
+                      const float* const* targets, float* const* images, int n, const rto_options* opt, int threads, int64_t* grad,
+                      uint64_t* stats) {
+    std::string err;
+    const int rc = rto::fit_grad_host(child, data, params, capacity, N, data_dim, data_format, scale, offset, ndc, cams, targets, images, n, opt,
+                                      threads, grad, stats, &err);
+    if (rc != RTO_OK) return set_err(rc, "rto_fit_grad_host: " + err);
+    return RTO_OK;
+}
+
+int rto_fit_sgd_step_host(float* params, int64_t* grad, int64_t count, float lr) {
+    std::string err;
+    const int rc = rto::fit_sgd_step_host(params, grad, count, lr, &err);
+    if (rc != RTO_OK) return set_err(rc, "rto_fit_sgd_step_host: " + err);
+    return RTO_OK;
+}
+
+}  // extern "C"

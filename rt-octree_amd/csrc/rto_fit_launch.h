@@ -1,0 +1,27 @@
+// rto_fit_launch.h -- launchers of fit_kernels.hip (rto_tree_fit_grad / rto_fit_sgd_step, include/rto.h "tree fit").
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rto_fit_march.h"
+#include "rto_kernel_types.h"
+#include "rto_layer_pass.h"
+
+namespace rto {
+
+// the per-camera planes of one launch, by value beside the cameras: [H][W][3] float32 each, or nullptr
+struct FitPlanes {
+    const float* target[kLayerCamChunk];
+    float* image[kLayerCamChunk];
+};
+
+// `frames` (1 .. kLayerCamChunk) consecutive cameras of ONE size; one lane per pixel's ray, a wave per 8x8 tile, blockIdx.z =
+// camera.  walk: kWalkChild / kWalkNodew / kWalkWide of rto_launch.h.  basis: the tree's basis_dim (1, 4, 9, 16, 25), 0 for RGBA.
+// params: float32 in the numbering node_old translates to (nullptr: the resident numbering); grad: nullptr = forward only;
+// stats: two words or nullptr.
+hipError_t launch_fit_grad(const TreeDev& tree, int walk, int basis, const fm::Opt& opt, const LayerCams& cams, const FitPlanes& planes,
+                           int frames, const uint32_t* node_old, const float* params, int64_t* grad, uint64_t* stats, hipStream_t stream);
+
+// params[i] -= lr * g(grad[i]); grad[i] = 0 for i < count
+hipError_t launch_fit_sgd_step(float* params, int64_t* grad, int64_t count, float lr, hipStream_t stream);
+
+}  // namespace rto

@@ -1,0 +1,232 @@
+"""Fine-tuning a tree's leaf values against training images (include/rto.h "tree fit"; csrc/fit_kernels.hip,
+csrc/host/fit_grad.cpp): the deterministic composited render of the field `params` over a fixed tree, its squared error against
+target images, and the gradient with respect to params accumulated in 64-bit fixed point -- so that the kernel, the host twin
+and any split of the cameras over calls give the same bytes.  optimize_octree.py is the tool built on them."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import RtoError, check, lib
+from .visibility import _cam_array, _options
+from .volrend import _stream_ptr
+
+FIX_SCALE = 2.0 ** 36  # a grad / loss word counts units of 2^-36
+
+
+def _ptr_array(ptrs, n):
+    arr = (C.c_void_p * max(n, 1))()
+    for i, p in enumerate(ptrs):
+        arr[i] = p
+    return arr
+
+
+def _planes(cams, planes, n, what, is_ok, ptr_of, optional_entries):
+    """the per-camera [H][W][3] float32 planes of a call -> a ctypes pointer array or None"""
+    if planes is None:
+        return None
+    planes = list(planes)
+    if len(planes) != n:
+        raise RtoError(-1, "%s: %d planes for %d cameras" % (what, len(planes), n))
+    ptrs = []
+    for f, (c, p) in enumerate(zip(cams, planes)):
+        if p is None and optional_entries:
+            ptrs.append(None)
+            continue
+        if not is_ok(p) or tuple(p.shape) != (int(c.height), int(c.width), 3):
+            raise RtoError(-1, "%s %d must be a contiguous float32 [%d, %d, 3]" % (what, f, c.height, c.width))
+        ptrs.append(ptr_of(p))
+    return _ptr_array(ptrs, n)
+
+
+def _cam_list(cams):
+    from .volrend import Camera
+    return [cams] if isinstance(cams, Camera) else list(cams)
+
+
+def fit_grad(tree, params, cams, targets=None, options=None, grad=None, stats=None, images=None, stream=None):
+    """rto_tree_fit_grad on the N3Tree `tree`: params float32 [capacity,N,N,N,D], targets / images per camera float32 [H,W,3]
+    (an entry of images may be None), grad int64 like params or None (forward only), stats int64 [2] or None -- torch tensors on
+    the tree's device.  Accumulates into grad and stats.  Asynchronous on `stream` (default: torch's current stream); no sync."""
+    import torch
+    device = torch.device("cuda", tree.device)
+    shape = (int(tree.capacity), int(tree.N), int(tree.N), int(tree.N), int(tree.data_dim))
+
+    def on_device(t, dtype, shp=None):
+        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.device == device
+                and (shp is None or tuple(t.shape) == shp))
+
+    if not on_device(params, torch.float32, shape):
+        raise RtoError(-1, "params must be a contiguous float32 tensor of shape %s on %s" % (list(shape), device))
+    if grad is not None and not on_device(grad, torch.int64, shape):
+        raise RtoError(-1, "grad must be a contiguous int64 tensor of shape %s on %s" % (list(shape), device))
+    if stats is not None and not on_device(stats, torch.int64, (2,)):
+        raise RtoError(-1, "stats must be a contiguous int64 tensor of shape [2] on %s" % device)
+    cams = _cam_list(cams)
+    arr, n = _cam_array(cams)
+    ok = lambda t: on_device(t, torch.float32)  # noqa: E731
+    tg = _planes(cams, targets, n, "target", ok, lambda t: t.data_ptr(), False)
+    im = _planes(cams, images, n, "image", ok, lambda t: t.data_ptr(), True)
+    co = _options(options)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    check(lib().rto_tree_fit_grad(tree._h, C.c_void_p(params.data_ptr()), arr, tg, im, n, C.byref(co),
+                                  C.c_void_p(grad.data_ptr()) if grad is not None else None,
+                                  C.c_void_p(stats.data_ptr()) if stats is not None else None, _stream_ptr(stream)))
+    return grad
+
+
+def sgd_step(params, grad, lr, stream=None):
+    """rto_fit_sgd_step: params -= lr * grad (fixed point -> float), grad = 0; torch tensors of one device and one shape"""
+    import torch
+    if not (isinstance(params, torch.Tensor) and isinstance(grad, torch.Tensor) and params.dtype == torch.float32 and grad.dtype == torch.int64
+            and params.is_contiguous() and grad.is_contiguous() and params.shape == grad.shape and params.device == grad.device):
+        raise RtoError(-1, "params (float32) and grad (int64) must be contiguous tensors of one shape and device")
+    if stream is None:
+        stream = torch.cuda.current_stream(params.device)
+    check(lib().rto_fit_sgd_step(C.c_void_p(params.data_ptr()), C.c_void_p(grad.data_ptr()), params.numel(), float(lr), _stream_ptr(stream)))
+    return params
+
+
+def fit_grad_host(child, data, params, scale, offset, data_format, cams, targets=None, options=None, ndc=None, threads=0, grad=None,
+                  stats=None, images=None):
+    """rto_fit_grad_host: the same from numpy arrays (child int32 [capacity,N,N,N], data float16 -- the support --, params
+    float32 [capacity,N,N,N,D], targets / images float32 [H,W,3] per camera, grad int64 like params or None, stats int64 [2] or
+    None); no device is touched.  threads <= 0: one thread; the result does not depend on it."""
+    child = np.ascontiguousarray(child)
+    data = np.ascontiguousarray(data)
+    if data.dtype == np.float16:
+        data = data.view(np.uint16)
+    if child.dtype != np.int32 or data.dtype != np.uint16:
+        raise RtoError(-1, "child must be int32 and data float16")
+    if child.ndim != 4 or data.ndim != 5 or data.shape[:4] != child.shape or not (child.shape[1] == child.shape[2] == child.shape[3]):
+        raise RtoError(-1, "child must be [capacity,N,N,N] and data [capacity,N,N,N,D], not %s and %s" % (list(child.shape), list(data.shape)))
+
+    def on_host(a, dtype, shp=None):
+        return isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous and (shp is None or a.shape == shp)
+
+    if not on_host(params, np.float32, data.shape):
+        raise RtoError(-1, "params must be a contiguous float32 array of shape %s" % (list(data.shape),))
+    if grad is not None and not (on_host(grad, np.int64, data.shape) and grad.flags.writeable):
+        raise RtoError(-1, "grad must be a contiguous int64 array of shape %s" % (list(data.shape),))
+    if stats is not None and not on_host(stats, np.int64, (2,)):
+        raise RtoError(-1, "stats must be a contiguous int64 array of shape [2]")
+    sc = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(scale, np.float32), (3,))])
+    of = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(offset, np.float32), (3,))])
+    nd = None if ndc is None else (C.c_float * 3)(*[float(x) for x in ndc])
+    cams = _cam_list(cams)
+    arr, n = _cam_array(cams)
+    ok = lambda a: on_host(a, np.float32)  # noqa: E731
+    tg = _planes(cams, targets, n, "target", ok, lambda a: a.ctypes.data, False)
+    im = _planes(cams, images, n, "image", lambda a: ok(a) and a.flags.writeable, lambda a: a.ctypes.data, True)
+    co = _options(options)
+    check(lib().rto_fit_grad_host(C.c_void_p(child.ctypes.data), C.c_void_p(data.ctypes.data), C.c_void_p(params.ctypes.data), child.shape[0],
+                                  child.shape[1], data.shape[4], str(data_format).encode(), sc, of, nd, arr, tg, im, n, C.byref(co),
+                                  int(threads), C.c_void_p(grad.ctypes.data) if grad is not None else None,
+                                  C.c_void_p(stats.ctypes.data) if stats is not None else None))
+    return grad
+
+
+def sgd_step_host(params, grad, lr):
+    """rto_fit_sgd_step_host on numpy arrays (float32 / int64, one shape)"""
+    if not (isinstance(params, np.ndarray) and isinstance(grad, np.ndarray) and params.dtype == np.float32 and grad.dtype == np.int64
+            and params.flags.c_contiguous and grad.flags.c_contiguous and params.shape == grad.shape):
+        raise RtoError(-1, "params (float32) and grad (int64) must be contiguous arrays of one shape")
+    check(lib().rto_fit_sgd_step_host(C.c_void_p(params.ctypes.data), C.c_void_p(grad.ctypes.data), params.size, float(lr)))
+    return params
+
+
+def _loss_of(words):
+    """(sum of the rays' squared errors, rays) from the two stats words"""
+    return float(int(words[0])) / FIX_SCALE, int(words[1])
+
+
+class TreeFit:
+    """The state of a fit on the device: the N3Tree (topology and support), params (float32, made from the float16 `data` the tree
+    was uploaded from), grad and stats.  accumulate() adds a batch's gradient and loss, step() takes the SGD step and clears the
+    gradient, loss() reads and clears the loss (it synchronises), render() is the deterministic render of params."""
+
+    def __init__(self, tree, data, options=None):
+        import torch
+        self.tree = tree
+        self.options = options
+        device = torch.device("cuda", tree.device)
+        data = np.ascontiguousarray(data)
+        shape = (int(tree.capacity), int(tree.N), int(tree.N), int(tree.N), int(tree.data_dim))
+        if data.dtype != np.float16 or data.shape != shape:
+            raise RtoError(-1, "data must be the float16 array %s the tree was uploaded from" % (list(shape),))
+        self.params = torch.from_numpy(data.astype(np.float32)).to(device)
+        self.grad = torch.zeros(shape, dtype=torch.int64, device=device)
+        self.stats = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def accumulate(self, cams, targets, stream=None):
+        fit_grad(self.tree, self.params, cams, targets, self.options, grad=self.grad, stats=self.stats, stream=stream)
+
+    def step(self, lr, stream=None):
+        sgd_step(self.params, self.grad, lr, stream=stream)
+
+    def evaluate(self, cams, targets, stream=None):
+        """(loss, rays) of params over a set of views: forward only, through stats (which it clears)"""
+        fit_grad(self.tree, self.params, cams, targets, self.options, stats=self.stats, stream=stream)
+        return self.loss()
+
+    def loss(self, reset=True):
+        """(sum over the rays since the last reset of |out - target|^2, their number)"""
+        words = self.stats.cpu().numpy()
+        if reset:
+            self.stats.zero_()
+        return _loss_of(words)
+
+    def render(self, cams, stream=None):
+        """the composited images of params: a list of float32 [H,W,3] tensors"""
+        import torch
+        cams = _cam_list(cams)
+        images = [torch.empty((int(c.height), int(c.width), 3), dtype=torch.float32, device=self.params.device) for c in cams]
+        fit_grad(self.tree, self.params, cams, None, self.options, images=images, stream=stream)
+        return images
+
+    def data_half(self):
+        """params rounded to float16 (to nearest even) as a numpy array: what a tree file stores"""
+        return self.params.cpu().numpy().astype(np.float16)
+
+
+class HostTreeFit:
+    """TreeFit on the host twin (no device): the same methods, the same bytes.  targets are numpy arrays."""
+
+    def __init__(self, child, data, scale, offset, data_format, options=None, ndc=None, threads=0):
+        self.child = np.ascontiguousarray(child)
+        self.data = np.ascontiguousarray(data)
+        if self.data.dtype != np.float16:
+            raise RtoError(-1, "data must be float16")
+        self.scale, self.offset, self.data_format, self.options, self.ndc, self.threads = scale, offset, data_format, options, ndc, threads
+        self.params = self.data.astype(np.float32)
+        self.grad = np.zeros(self.data.shape, np.int64)
+        self.stats = np.zeros(2, np.int64)
+
+    def _call(self, cams, targets, **kw):
+        fit_grad_host(self.child, self.data, self.params, self.scale, self.offset, self.data_format, cams, targets, self.options, ndc=self.ndc,
+                      threads=self.threads, **kw)
+
+    def accumulate(self, cams, targets):
+        self._call(cams, targets, grad=self.grad, stats=self.stats)
+
+    def step(self, lr):
+        sgd_step_host(self.params, self.grad, lr)
+
+    def evaluate(self, cams, targets):
+        self._call(cams, targets, stats=self.stats)
+        return self.loss()
+
+    def loss(self, reset=True):
+        words = self.stats.copy()
+        if reset:
+            self.stats[:] = 0
+        return _loss_of(words)
+
+    def render(self, cams):
+        cams = _cam_list(cams)
+        images = [np.empty((int(c.height), int(c.width), 3), np.float32) for c in cams]
+        self._call(cams, None, images=images)
+        return images
+
+    def data_half(self):
+        return self.params.astype(np.float16)

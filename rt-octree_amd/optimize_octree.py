@@ -1,0 +1,183 @@
+"""Octree optimisation against the training images -- the last step of PlenOctree extraction (PlenOctrees'
+octree/optimization.py): the structure stays fixed, the leaf values descend the squared error of the deterministic composited
+render (include/rto.h "tree fit") by SGD.
+
+    python -m rt_octree_amd.optimize_octree tree.npz --poses transforms_train.json
+        [--dataset blender|tt] [--scale S] [--lr L] [--epochs E] [--batch_imgs K] [--max_imgs N]
+        [--val_poses transforms_val.json] [--stop_thresh 1e-2] [--sigma_thresh 1e-2] [--step_size 1e-4]
+        [--background 1.0] [--out_dir optimized] [--overwrite] [--backend hip|cpu]
+
+One SGD step per batch of K images, in file order (no shuffling: a run is reproducible), E epochs.  --lr is the rate of a mean
+squared error: a step uses lr * 2 / (3 * rays of the batch) on the summed gradient.  Per epoch the PSNR of the training images
+as they were rendered during the epoch (-10 log10(loss / (3 rays))) is printed, and with --val_poses that of the validation
+images after it.  Poses are read as prune_octree reads them; the images are the PNGs the pose file names (blender: file_path +
+".png" beside the json; tt: the sorted files of ../rgb), 8-bit RGB or RGBA, alpha composited over --background, and must have the
+cameras' size (with --scale: the scaled size).  The output holds `data` rounded to float16 and every other key unchanged: the
+schema simplify_octree writes.  Refused: --dataset llff, a quantised file, an SG / ASG tree.  Skipped when the output exists
+(without --overwrite).  --backend cpu uses the host twin and never touches a GPU; both backends write the same bytes."""
+import argparse
+import json
+import os
+import os.path as osp
+import sys
+
+import numpy as np
+
+from .prune_octree import load_poses, make_cameras, scaled_size
+from .simplify_octree import QUANT_KEYS
+
+
+def image_paths(dataset, poses_path):
+    """the PNG of every pose, in the order load_poses returns the poses"""
+    if dataset == "blender":
+        with open(poses_path) as f:
+            j = json.load(f)
+        root = osp.dirname(osp.abspath(poses_path))
+        return [osp.normpath(osp.join(root, fr["file_path"] + ".png")) for fr in j["frames"]]
+    rgb = osp.join(poses_path, "..", "rgb")
+    return [osp.join(rgb, n) for n in sorted(os.listdir(rgb))]
+
+
+def load_target(path, width, height, background):
+    """-> float32 [H,W,3]: rgb * a + background * (1 - a), every value / 255 in float32"""
+    from .metrics import read_png
+    u8 = read_png(path)
+    if u8.shape[:2] != (height, width):
+        raise ValueError("'%s' is %d x %d, the cameras %d x %d" % (path, u8.shape[1], u8.shape[0], width, height))
+    f = u8.astype(np.float32) / np.float32(255)
+    a = f[..., 3:]
+    return np.ascontiguousarray(f[..., :3] * a + np.float32(background) * (np.float32(1) - a), np.float32)
+
+
+def load_views(dataset, poses_path, scale, max_imgs, background):
+    """-> (cameras, targets) of a pose file"""
+    if dataset not in ("blender", "tt"):
+        load_poses(dataset, poses_path)  # (raises: llff and unknown types, in prune_octree's words)
+    paths = image_paths(dataset, poses_path)
+    if not paths:
+        raise ValueError("no images for '%s'" % poses_path)
+    from .metrics import read_png
+    first = read_png(paths[0])
+    s = np.float32(scale)
+    # the cameras' size before --scale: that of the images, undone
+    w0, h0 = (first.shape[1], first.shape[0]) if s == np.float32(1) else (int(round(first.shape[1] / float(s))), int(round(first.shape[0] / float(s))))
+    trans, width, height, fx, fy = load_poses(dataset, poses_path, w0, h0)
+    if len(trans) != len(paths):
+        raise ValueError("%d poses and %d images" % (len(trans), len(paths)))
+    width, height, fx, fy = scaled_size(width, height, fx, fy, scale)
+    if max_imgs > 0:
+        trans, paths = trans[:max_imgs], paths[:max_imgs]
+    return make_cameras(trans, width, height, fx, fy), [load_target(p, width, height, background) for p in paths]
+
+
+def psnr_of(loss, rays):
+    return float("nan") if rays == 0 else (float("inf") if loss <= 0 else -10.0 * np.log10(loss / (3.0 * rays)))
+
+
+def make_fit(z, options, backend):
+    """z: the dict of a dense tree.npz -> (a TreeFit or HostTreeFit, to_device: targets -> what its accumulate takes)"""
+    from .fit import HostTreeFit, TreeFit
+    child = np.ascontiguousarray(z["child"], dtype=np.int32)
+    data = np.ascontiguousarray(z["data"], dtype=np.float16)
+    if data.ndim != 5 or child.ndim != 4 or data.shape[:4] != child.shape:
+        raise ValueError("child must be [capacity,N,N,N] and data [capacity,N,N,N,D], not %s and %s" % (list(child.shape), list(data.shape)))
+    scale = np.asarray(z["invradius3"] if "invradius3" in z else np.full(3, z["invradius"]), np.float32).reshape(-1)[:3]
+    offset = np.asarray(z["offset"], np.float32).reshape(-1)[:3]
+    fmt = str(z["data_format"]) if "data_format" in z else ""
+    if not (fmt == "RGBA" or (fmt.startswith("SH") and fmt[2:].isdigit())):
+        raise ValueError("the fit takes RGBA and SH trees, not data_format '%s'" % fmt)
+    if backend == "cpu":
+        return HostTreeFit(child, data, scale, offset, fmt, options, threads=min(16, os.cpu_count() or 1)), lambda ts: ts
+    if backend != "hip":
+        raise ValueError("backend must be 'hip' or 'cpu', not %r" % (backend,))
+    import torch
+    from .volrend import N3Tree
+    tree = N3Tree.from_arrays(child, data, scale, offset, fmt)
+    fit = TreeFit(tree, data, options)
+    return fit, lambda ts: [torch.from_numpy(t).to(fit.params.device) for t in ts]
+
+
+def optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val=None, say=print):
+    """the SGD loop -> the PSNR per epoch"""
+    targets = to_device(targets)
+    val = None if val is None else (val[0], to_device(val[1]))
+    k = max(1, int(batch_imgs))
+    out = []
+    for epoch in range(epochs):
+        for b in range(0, len(cams), k):
+            bc, bt = cams[b:b + k], targets[b:b + k]
+            fit.accumulate(bc, bt)
+            rays = sum(int(c.width) * int(c.height) for c in bc)
+            fit.step(lr * 2.0 / (3.0 * rays))
+        line = "epoch %d: train psnr %.4f" % (epoch, psnr_of(*fit.loss()))
+        if val is not None:
+            line += ", val psnr %.4f" % psnr_of(*fit.evaluate(*val))
+        say(line)
+        out.append(line)
+    return out
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="python -m rt_octree_amd.optimize_octree", description=__doc__.split("\n\n")[0])
+    parser.add_argument("input", type=str, nargs="+", help="Input npz(s)")
+    parser.add_argument("--poses", type=str, required=True, help="transforms_train.json (blender) or the pose directory (tt)")
+    parser.add_argument("--dataset", type=str, default="blender", help="blender|tt")
+    parser.add_argument("--scale", type=float, default=1.0, help="The images are this fraction of the dataset's size")
+    parser.add_argument("--lr", type=float, default=1000.0, help="SGD rate on the mean squared error")
+    parser.add_argument("--epochs", type=int, default=1)
+    parser.add_argument("--batch_imgs", type=int, default=4, help="Images per SGD step")
+    parser.add_argument("--max_imgs", type=int, default=0, help="Use the first N poses only")
+    parser.add_argument("--val_poses", type=str, default="", help="Pose file of a validation set, scored after every epoch")
+    parser.add_argument("--stop_thresh", type=float, default=1e-2)
+    parser.add_argument("--sigma_thresh", type=float, default=1e-2)
+    parser.add_argument("--step_size", type=float, default=1e-4)
+    parser.add_argument("--background", type=float, default=1.0, help="background_brightness: behind the rays and the PNGs' alpha")
+    parser.add_argument("--out_dir", type=str, default="optimized", help="Where to write the optimised npz")
+    parser.add_argument("--overwrite", action="store_true", help="Overwrite an existing output")
+    parser.add_argument("--backend", choices=("hip", "cpu"), default="hip", help="The HIP kernels or the host twins")
+    args = parser.parse_args(argv)
+    if not (args.lr >= 0 and args.epochs >= 0):
+        print("optimize_octree: --lr and --epochs must be numbers >= 0", file=sys.stderr)
+        return 2
+    from ._lib import RtoError
+    from .volrend import RenderOptions
+    try:
+        cams, targets = load_views(args.dataset, args.poses, args.scale, args.max_imgs, args.background)
+        val = load_views(args.dataset, args.val_poses, args.scale, 0, args.background) if args.val_poses else None
+    except (ValueError, OSError, KeyError, RtoError) as e:
+        print("optimize_octree: %s" % e, file=sys.stderr)
+        return 2
+    options = RenderOptions(step_size=args.step_size, sigma_thresh=args.sigma_thresh, stop_thresh=args.stop_thresh,
+                            background_brightness=args.background)
+    print("Images %d, %d x %d, fx %.9g fy %.9g" % (len(cams), cams[0].width, cams[0].height, cams[0].fx, cams[0].fy))
+    os.makedirs(args.out_dir, exist_ok=True)
+    for fname in args.input:
+        fname_s = osp.join(args.out_dir, osp.basename(fname))
+        print("Optimizing", fname, "to", fname_s)
+        if not args.overwrite and osp.exists(fname_s):
+            print(" > skip")
+            continue
+        fit = None
+        try:
+            with np.load(fname) as f:
+                if any(k in f.files for k in QUANT_KEYS[:2]):
+                    raise ValueError("the file is quantised (quant_colors / quant_map): optimise the dense tree first, then run compress_octree")
+                if "child" not in f.files or "data" not in f.files:
+                    raise ValueError("no child / data arrays: not a dense tree.npz")
+                z = {k: f[k] for k in f.files}
+            fit, to_device = make_fit(z, options, args.backend)
+            optimize(fit, to_device, cams, targets, args.lr, args.epochs, args.batch_imgs, val, say=lambda s: print(" > " + s))
+            z["data"] = fit.data_half()
+        except (ValueError, RtoError) as e:
+            print("optimize_octree: %s: %s" % (fname, e), file=sys.stderr)
+            return 2
+        finally:
+            if fit is not None and hasattr(fit, "tree"):
+                fit.tree.free()
+        np.savez_compressed(fname_s, **z)
+        print(" > Size %.2f MB -> %.2f MB" % (osp.getsize(fname) / 2.0 ** 20, osp.getsize(fname_s) / 2.0 ** 20))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
