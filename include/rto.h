@@ -1076,6 +1076,62 @@ int rto_tree_build_write(rto_tree_builder* b, void* stream, int32_t* child_out, 
 int rto_tree_build_host(const uint16_t* grid, int L, int D, float kill_thresh, int32_t* child_out, uint16_t* data_out,
                         int64_t room, int64_t* out_capacity, rto_grid_build_stats* stats);
 
+/* ---- refiner (svox's N3Tree.refine(sel=...): the one structural step that makes a tree FINER; PlenOctree extraction refines where
+ * the weights are high; the reference holds no counterpart) ----
+ * Splits the K most important leaves: each becomes a node of N^3 leaves that all hold the leaf's record, so every point query of
+ * the result returns the bits the input returns, and rto_tree_simplify of the result is rto_tree_simplify of the input.
+ *   input    child[cap][N^3] (int32, relative offsets, 0 = leaf) and data[cap][N^3][D] (fp16 bit patterns), as the simplifier
+ *            takes them; key[cap * N^3] (uint32, one word per slot, indexed like child; NULL = every key is 1); key_thresh
+ *            (uint32); max_new (int64, negative = unbounded); max_level (1 .. 31).
+ *   links    The simplifier's rules and refusals, word for word: RTO_E_FORMAT for an n + c outside [1, cap), for a node referred
+ *            to by more than one slot, for a node at level 32; every read is bounds-checked before the dereference it guards.
+ *            Unreachable nodes are copied unchanged and their slots are never candidates.
+ *   candidate  Slot i of a reachable node of level l is a CANDIDATE when child[i] == 0, l + 1 <= max_level and
+ *            key[i] >= key_thresh, compared as unsigned integers.  There is no density test: the caller folds it into the key.
+ *   selection  C = the number of candidates; K = C when max_new < 0, else min(C, max_new).  SELECTED are the first K candidates
+ *            in the order (key descending, slot index ascending) -- a complete order, so nothing depends on the run.
+ *   output   cap_out = cap + K.  Nodes 0 .. cap - 1 are the input's bytes except the selected slots' child words: with the
+ *            selected slots numbered j = 0 .. K - 1 in ASCENDING SLOT ORDER, selected slot i of node n gets
+ *            child_out[i] = (cap + j) - n and keeps its record; node cap + j has child all 0 and each of its N^3 slots holds the
+ *            D halves of data[i].  New nodes are appended, as svox appends them.
+ *   slot_src (optional, int32 [cap_out * N^3]) slot_src[s] = s for s < cap * N^3 and = i for the slots of node cap + j, so
+ *            data_out.reshape(-1, D) == data.reshape(-1, D)[slot_src]; the same gather carries the fit's float32 params and leaf
+ *            weights across a refinement.
+ *   stats    reachable; candidates = C; selected = K; levels: 1 + the deepest level of a reachable node of the RESULT; cut_key:
+ *            the smallest selected key, 0 when K == 0.
+ * Nothing is left to the implementation: the device entries, the host twin and the numpy model of the tests give the same bytes.
+ * Two passes, like the grid builder, because the outputs cannot be sized before the selection.  rto_tree_refine_plan reads child
+ * and key, leaves the per-slot selection and the ranks j in the handle, synchronises `stream` once to read the counts and the link
+ * flags back and sets *out_capacity = cap_out and *stats (also when it refuses the result as too large).  rto_tree_refine_write
+ * enqueues the kernels that write the outputs of the handle's last successful plan and returns without waiting; child must be
+ * unchanged since the plan.  A TOOL path like rto_tree_simplify: kernel boundaries are the only grid-wide synchronisation; integer
+ * counts, maxima, minima and one compare-and-swap per link the only atomics; no float arithmetic; the top K come from a radix
+ * select over the keys (four 8-bit passes of a 256-bin histogram, the digit picked on the device) and the ranks from a
+ * reduce-then-scan over tiles of slots: two runs give the same bytes.  The handle owns all scratch (8 bytes per slot and 8 per
+ * node), which grows on demand and is reused; growing synchronises the device once.  One handle serves one stream at a time.
+ * data and data_out aligned to 16 bytes with N^3 * D a multiple of 8 are written in 16-byte words, anything else half by half.
+ * RTO_E_INVALID, decided before anything is enqueued: a null pointer (key, slot_src and stats may be NULL), cap < 1, N < 2, D < 1,
+ * cap * N^3 >= 2^31, max_level outside 1 .. 31, a pointer not aligned to its element, an output that overlaps an input or another
+ * output; on the device entries any array that is not memory of the handle's device (out_capacity and stats are host memory);
+ * rto_tree_refine_write without a preceding successful plan on the handle.  A result with cap_out * N^3 >= 2^31 is refused by the
+ * plan, with a text.
+ * rto_tree_refine_host is the host twin: host pointers, no handle, no device.  child_out == data_out == NULL counts only; `room` =
+ * the nodes the outputs can hold -- too small is RTO_E_INVALID with *out_capacity and *stats set all the same. */
+typedef struct rto_refine_stats {
+    int64_t reachable, candidates, selected, levels, cut_key;
+} rto_refine_stats;
+typedef struct rto_refiner rto_refiner;
+int rto_refiner_create(int device, rto_refiner** out);
+void rto_refiner_free(rto_refiner* r);
+int rto_tree_refine_plan(rto_refiner* r, void* stream, const int32_t* child, const uint32_t* key /* or NULL */, int64_t cap, int N,
+                         uint32_t key_thresh, int64_t max_new, int max_level, int64_t* out_capacity /* host */,
+                         rto_refine_stats* stats /* host, or NULL */);
+int rto_tree_refine_write(rto_refiner* r, void* stream, const int32_t* child, const uint16_t* data, int D, int32_t* child_out,
+                          uint16_t* data_out, int32_t* slot_src /* or NULL */);
+int rto_tree_refine_host(const int32_t* child, const uint16_t* data, const uint32_t* key, int64_t cap, int N, int D,
+                         uint32_t key_thresh, int64_t max_new, int max_level, int32_t* child_out, uint16_t* data_out, int64_t room,
+                         int64_t* out_capacity, int32_t* slot_src, rto_refine_stats* stats);
+
 /* ---- GuidanceNet under training (denoiser/network.py:49-118; denoiser/runner.py:71-84; denoiser/metrics.py:7-9) ----
  * A RepVGG block (network.py:49-75) has no normalisation layer: before its ReLU6 it is linear in its input, so the sum of its
  * branches is ONE 3x3 convolution with the summed weights, and the gradient of every branch is a slice of the gradient of that

@@ -118,6 +118,12 @@ class CGridBuildStats(C.Structure):
     _fields_ = [("nodes", C.c_int64), ("killed", C.c_int64), ("levels", C.c_int64)]
 
 
+class CRefineStats(C.Structure):
+    """rto_refine_stats (include/rto.h)"""
+    _fields_ = [("reachable", C.c_int64), ("candidates", C.c_int64), ("selected", C.c_int64), ("levels", C.c_int64),
+                ("cut_key", C.c_int64)]
+
+
 # every symbol include/rto.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -250,6 +256,13 @@ SYMBOLS = {
     "rto_tree_build_write": (C.c_int, [_P, _P, _P, _P]),
     "rto_tree_build_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, _P, _P, C.c_int64, C.POINTER(C.c_int64),
                                       C.POINTER(CGridBuildStats)]),
+    "rto_refiner_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
+    "rto_refiner_free": (None, [_P]),
+    "rto_tree_refine_plan": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_uint32, C.c_int64, C.c_int, C.POINTER(C.c_int64),
+                                       C.POINTER(CRefineStats)]),
+    "rto_tree_refine_write": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "rto_tree_refine_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_int64, C.c_int, _P, _P, C.c_int64,
+                                       C.POINTER(C.c_int64), _P, C.POINTER(CRefineStats)]),
     "rto_guidance_train_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_guidance_train_free": (None, [_P]),
     "rto_guidance_train_acts_bytes": (C.c_int, [C.POINTER(CGuidanceTrainLayer), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),

@@ -6,6 +6,7 @@ render (include/rto.h "tree fit") by SGD.
         [--dataset blender|tt] [--scale S] [--lr L] [--epochs E] [--batch_imgs K] [--max_imgs N]
         [--val_poses transforms_val.json] [--stop_thresh 1e-2] [--sigma_thresh 1e-2] [--step_size 1e-4]
         [--background 1.0] [--out_dir optimized] [--overwrite] [--backend hip|cpu]
+        [--refine_rounds R] [--refine_nodes K] [--refine_weight_thresh 0.01] [--refine_max_level L]
 
 One SGD step per batch of K images, in file order (no shuffling: a run is reproducible), E epochs.  --lr is the rate of a mean
 squared error: a step uses lr * 2 / (3 * rays of the batch) on the summed gradient.  Per epoch the PSNR of the training images
@@ -14,7 +15,13 @@ images after it.  Poses are read as prune_octree reads them; the images are the 
 ".png" beside the json; tt: the sorted files of ../rgb), 8-bit RGB or RGBA, alpha composited over --background, and must have the
 cameras' size (with --scale: the scaled size).  The output holds `data` rounded to float16 and every other key unchanged: the
 schema simplify_octree writes.  Refused: --dataset llff, a quantised file, an SG / ASG tree.  Skipped when the output exists
-(without --overwrite).  --backend cpu uses the host twin and never touches a GPU; both backends write the same bytes."""
+(without --overwrite).  --backend cpu uses the host twin and never touches a GPU; both backends write the same bytes.
+
+--refine_rounds R (default 0: the structure stays fixed) makes the fit coarse to fine: after the E epochs of each of the first R
+rounds the leaves that the training cameras see with a weight of at least --refine_weight_thresh are split, heaviest first, at
+most --refine_nodes of them (include/rto.h "refiner"), never below level --refine_max_level; the float32 state of the fit is
+carried into the new leaves unrounded, and E more epochs follow: (R + 1) * E in all.  The node count is printed per round; the
+output's `child` is the refined one (parent_depth, n_free and n_internal are dropped then, as simplify_octree drops them)."""
 import argparse
 import json
 import os
@@ -97,8 +104,47 @@ def make_fit(z, options, backend):
     return fit, lambda ts: [torch.from_numpy(t).to(fit.params.device) for t in ts]
 
 
-def optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val=None, say=print):
-    """the SGD loop -> the PSNR per epoch"""
+def refine_fit(fit, z, cams, options, backend, max_nodes=-1, weight_thresh=0.01, max_level=31, refiner=None):
+    """One refinement between two rounds of epochs: the leaves of the fitted tree that the training cameras see with a weight of
+    at least weight_thresh are split, heaviest first, at most max_nodes of them (negative: all).  z: the dict the fit was made
+    from -> (the dict of the refined tree, the new fit, its to_device, the refiner's stats).  The new fit's params are the old
+    float32 params gathered by slot_src: the fit's state does not pass through fp16."""
+    from .refine import keys_from_weights, refine_tree
+    from .refine_octree import weight_thresh_key
+    from .simplify_octree import STALE_KEYS
+    from .visibility import leaf_weights, leaf_weights_host
+    child = np.ascontiguousarray(z["child"], dtype=np.int32)
+    halves = fit.data_half()
+    D = halves.shape[-1]
+    if backend == "cpu":
+        w = leaf_weights_host(child, halves, fit.scale, fit.offset, cams, options, threads=fit.threads)
+    else:
+        from .volrend import N3Tree
+        old = fit.tree
+        seen = N3Tree.from_arrays(child, halves, np.asarray(old.scale, np.float32), np.asarray(old.offset, np.float32), str(z["data_format"]))
+        try:
+            w = leaf_weights(seen, cams, options).cpu().numpy()
+        finally:
+            seen.free()
+    c, d, slot_src, stats = refine_tree(child, halves, keys_from_weights(w), weight_thresh_key(weight_thresh), max_nodes, max_level,
+                                        backend=backend, refiner=refiner)
+    z = dict(z)
+    for k in STALE_KEYS:
+        z.pop(k, None)
+    z["child"], z["data"] = c, d
+    new_fit, to_device = make_fit(z, options, backend)
+    if backend == "cpu":
+        new_fit.params[...] = fit.params.reshape(-1, D)[slot_src.reshape(-1)].reshape(new_fit.params.shape)
+    else:
+        import torch
+        idx = torch.from_numpy(slot_src.reshape(-1).astype(np.int64)).to(fit.params.device)
+        new_fit.params.copy_(fit.params.reshape(-1, D)[idx].reshape(new_fit.params.shape))
+        fit.tree.free()
+    return z, new_fit, to_device, stats
+
+
+def optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val=None, say=print, losses=None):
+    """the SGD loop -> the PSNR per epoch (losses: a list that takes every epoch's (loss, rays))"""
     targets = to_device(targets)
     val = None if val is None else (val[0], to_device(val[1]))
     k = max(1, int(batch_imgs))
@@ -109,12 +155,37 @@ def optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val=None, sa
             fit.accumulate(bc, bt)
             rays = sum(int(c.width) * int(c.height) for c in bc)
             fit.step(lr * 2.0 / (3.0 * rays))
-        line = "epoch %d: train psnr %.4f" % (epoch, psnr_of(*fit.loss()))
+        loss = fit.loss()
+        if losses is not None:
+            losses.append(loss)
+        line = "epoch %d: train psnr %.4f" % (epoch, psnr_of(*loss))
         if val is not None:
             line += ", val psnr %.4f" % psnr_of(*fit.evaluate(*val))
         say(line)
         out.append(line)
     return out
+
+
+def optimize_rounds(z, fit, to_device, cams, targets, options, backend, lr, epochs, batch_imgs, rounds, max_nodes=-1, weight_thresh=0.01,
+                    max_level=31, val=None, say=print, losses=None):
+    """Coarse to fine: `epochs` epochs, then -- after each of the first `rounds` rounds -- refine_fit and `epochs` more.
+    -> (the dict of the tree the last round ran on, its fit).  rounds == 0 is optimize()."""
+    refiner = None
+    try:
+        for rnd in range(rounds + 1):
+            optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val, say=say, losses=losses)
+            if rnd == rounds:
+                break
+            if backend == "hip" and refiner is None:
+                from .refine import Refiner
+                refiner = Refiner(0)
+            z, fit, to_device, st = refine_fit(fit, z, cams, options, backend, max_nodes, weight_thresh, max_level, refiner)
+            say("round %d: nodes %d -> %d (%d candidates, %d selected), %d levels"
+                % (rnd, st["capacity_in"], st["capacity"], st["candidates"], st["selected"], st["levels"]))
+    finally:
+        if refiner is not None:
+            refiner.free()
+    return z, fit
 
 
 def main(argv=None):
@@ -135,9 +206,16 @@ def main(argv=None):
     parser.add_argument("--out_dir", type=str, default="optimized", help="Where to write the optimised npz")
     parser.add_argument("--overwrite", action="store_true", help="Overwrite an existing output")
     parser.add_argument("--backend", choices=("hip", "cpu"), default="hip", help="The HIP kernels or the host twins")
+    parser.add_argument("--refine_rounds", type=int, default=0, help="Refine the tree after each of the first R rounds of --epochs epochs")
+    parser.add_argument("--refine_nodes", type=int, default=-1, help="Nodes a refinement adds at most (default: no bound)")
+    parser.add_argument("--refine_weight_thresh", type=float, default=0.01, help="A refinement splits leaves seen with at least this weight")
+    parser.add_argument("--refine_max_level", type=int, default=31, help="A refinement never makes a node below this level")
     args = parser.parse_args(argv)
     if not (args.lr >= 0 and args.epochs >= 0):
         print("optimize_octree: --lr and --epochs must be numbers >= 0", file=sys.stderr)
+        return 2
+    if not (args.refine_rounds >= 0 and args.refine_weight_thresh >= 0 and 1 <= args.refine_max_level <= 31):
+        print("optimize_octree: --refine_rounds and --refine_weight_thresh must be >= 0, --refine_max_level in 1 .. 31", file=sys.stderr)
         return 2
     from ._lib import RtoError
     from .volrend import RenderOptions
@@ -166,7 +244,12 @@ def main(argv=None):
                     raise ValueError("no child / data arrays: not a dense tree.npz")
                 z = {k: f[k] for k in f.files}
             fit, to_device = make_fit(z, options, args.backend)
-            optimize(fit, to_device, cams, targets, args.lr, args.epochs, args.batch_imgs, val, say=lambda s: print(" > " + s))
+            if args.refine_rounds > 0:
+                z, fit = optimize_rounds(z, fit, to_device, cams, targets, options, args.backend, args.lr, args.epochs, args.batch_imgs,
+                                         args.refine_rounds, args.refine_nodes, args.refine_weight_thresh, args.refine_max_level, val,
+                                         say=lambda s: print(" > " + s))
+            else:
+                optimize(fit, to_device, cams, targets, args.lr, args.epochs, args.batch_imgs, val, say=lambda s: print(" > " + s))
             z["data"] = fit.data_half()
         except (ValueError, RtoError) as e:
             print("optimize_octree: %s: %s" % (fname, e), file=sys.stderr)
