@@ -1023,6 +1023,38 @@ int rto_fit_grad_host(const int32_t* child, const uint16_t* data, const float* p
                       const rto_camera* cams, const float* const* targets, float* const* images, int n, const rto_options* opt,
                       int threads, int64_t* grad, uint64_t* stats);
 int rto_fit_sgd_step_host(float* params, int64_t* grad, int64_t count, float lr);
+/* The fit on rays the CALLER supplies -- the counterpart of rto_launch_rays: shuffled ray batches across all images, rays of
+ * non-pinhole cameras, rays kept after a mask or picked by a sampler.  origins, dirs, targets, out: [n][3] float32.
+ *   set-up   Ray i is a pixel whose set-up produced  dir = vdir = normalize3(dirs[i])  (invnorm = 1.f / sqrtf(x*x + y*y + z*z),
+ *            three products: the operations of the camera set-up; dirs[i] may have any length)  and  cen = origins[i];  then the
+ *            NDC warp of an NDC tree and offset + scale * cen, exactly the tail of the camera set-up.  The SH basis is taken at
+ *            vdir.  EVERYTHING AFTER THE SET-UP is rto_tree_fit_grad's, word for word: the entry with tmax_bg = 1e9f, both
+ *            marches, the fixed point, the sums.  A NaN in targets[i] MASKS ray i: not marched, not counted, out[i] not
+ *            written.  A component of dir or cen that is not finite after the set-up, or a miss of the box: not marched,
+ *            out[i] = bg, and the ray is counted; a zero or non-finite direction and a non-finite origin fall under this by
+ *            arithmetic (0 * inf), there is no separate test.  No per-ray t_max and no per-ray backdrop: every ray ends at the
+ *            box or at tmax_bg, and background_brightness is the backdrop.
+ *   identity Integer adds commute: on the rays of a camera (dirs[i] = M xyz(x, y) before normalising, origins[i] = the camera's
+ *            position), in any order and any split over calls, the entry gives the grad, stats and image bytes that
+ *            rto_tree_fit_grad gives on the camera.
+ * Formats, the support, the RTO_E_UNSUPPORTED cases and the walks are rto_tree_fit_grad's.  grad == NULL: only the forward
+ * march runs; targets == NULL only with grad == NULL and stats == NULL; out may be NULL.  The call ACCUMULATES into grad and
+ * stats; the caller zeroes them.  The device entry is asynchronous on `stream`: no allocation, no host synchronisation, no copy;
+ * n == 0 launches nothing; a call becomes launches of at most 2^30 rays, every ray index is 64-bit.
+ * RTO_E_INVALID, decided before anything is enqueued, with a text naming the argument: a null tree, params or options; null
+ * origins or dirs with n > 0; n < 0; params, origins, dirs, targets or out not 4-byte aligned, grad or stats not 8-byte aligned;
+ * null targets with grad or stats set; params or grad overlapping origins, dirs, targets or out; out overlapping origins, dirs or
+ * targets; non-default rot_dirs or basis_minmax; on the device entry any of them not memory of the tree's device.
+ * rto_fit_grad_rays_host is the host twin (host pointers, no device; the tree's arrays as rto_fit_grad_host takes them): threads
+ * run over contiguous ranges of rays, and the result does not depend on threads. */
+int rto_tree_fit_grad_rays(const rto_tree* tree, const float* params, const float* origins /* device [n][3] */,
+                           const float* dirs /* device [n][3] */, const float* targets /* device [n][3] or NULL */,
+                           float* out /* device [n][3] or NULL */, int64_t n, const rto_options* opt, int64_t* grad /* or NULL */,
+                           uint64_t* stats /* device [2] or NULL */, void* stream);
+int rto_fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int data_dim,
+                           const char* data_format, const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
+                           const float* origins, const float* dirs, const float* targets, float* out, int64_t n, const rto_options* opt,
+                           int threads, int64_t* grad, uint64_t* stats);
 
 /* ---- grid builder (the first step of PlenOctree extraction: a field evaluated on a regular grid becomes an octree; svox does
  * it on the CPU, the reference holds no counterpart) ----

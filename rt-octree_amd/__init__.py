@@ -16,7 +16,7 @@ from .quantize import Quantizer, quantize_median_cut  # noqa: F401
 from .simplify import Simplifier, simplify_tree  # noqa: F401
 from .visibility import leaf_weights, leaf_weights_host, kill_unseen  # noqa: F401
 from .grid_build import TreeBuilder, build_tree, tree_to_grid  # noqa: F401
-from .fit import TreeFit, HostTreeFit, fit_grad, fit_grad_host, sgd_step, sgd_step_host  # noqa: F401
+from .fit import TreeFit, HostTreeFit, fit_grad, fit_grad_host, fit_grad_rays, fit_grad_rays_host, sgd_step, sgd_step_host  # noqa: F401
 from .refine import Refiner, refine_tree, refine_tree_host, keys_from_weights, keys_from_density  # noqa: F401
 
 __all__ = [
@@ -29,6 +29,6 @@ __all__ = [
     "Quantizer", "quantize_median_cut", "Simplifier", "simplify_tree",
     "leaf_weights", "leaf_weights_host", "kill_unseen",
     "TreeBuilder", "build_tree", "tree_to_grid",
-    "TreeFit", "HostTreeFit", "fit_grad", "fit_grad_host", "sgd_step", "sgd_step_host",
+    "TreeFit", "HostTreeFit", "fit_grad", "fit_grad_host", "fit_grad_rays", "fit_grad_rays_host", "sgd_step", "sgd_step_host",
     "Refiner", "refine_tree", "refine_tree_host", "keys_from_weights", "keys_from_density",
 ]

@@ -250,6 +250,9 @@ SYMBOLS = {
                                     C.POINTER(C.c_float), C.POINTER(CCamera), C.POINTER(_P), C.POINTER(_P), C.c_int,
                                     C.POINTER(COptions), C.c_int, _P, _P]),
     "rto_fit_sgd_step_host": (C.c_int, [_P, _P, C.c_int64, C.c_float]),
+    "rto_tree_fit_grad_rays": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(COptions), _P, _P, _P]),
+    "rto_fit_grad_rays_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, C.POINTER(COptions), C.c_int, _P, _P]),
     "rto_tree_builder_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_tree_builder_free": (None, [_P]),
     "rto_tree_build_plan": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(CGridBuildStats)]),

@@ -1,8 +1,10 @@
-// host/fit_grad.cpp -- the host twin of rto_tree_fit_grad and rto_fit_sgd_step: the marches of rto_fit_march.h over child[] /
-// data[] with the root-restart float descent, det_expf restated in plain C++.  Same bits as the kernels
-// (tests/test_fit_gpu.py) and as the numpy restatement (tests/fit_ref.py).  No HIP header.
+// host/fit_grad.cpp -- the host twin of rto_tree_fit_grad, rto_tree_fit_grad_rays and rto_fit_sgd_step: the marches of
+// rto_fit_march.h over child[] / data[] with the root-restart float descent, det_expf restated in plain C++.  Same bits as the
+// kernels (tests/test_fit_gpu.py, tests/test_fit_rays_gpu.py) and as the numpy restatements (tests/fit_ref.py,
+// tests/fit_rays_ref.py).  No HIP header.
 #include "fit_grad.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +75,38 @@ std::string fit_check_call(const float* params, const rto_camera* cams, const fl
     return "";
 }
 
+std::string fit_check_rays_call(const float* params, const float* origins, const float* dirs, const float* targets, const float* out, int64_t n,
+                                const rto_options* opt, const int64_t* grad, const uint64_t* stats, int64_t param_count) {
+    if (!params) return "null params";
+    if (!opt) return "null options";
+    if (n < 0) return "n must be >= 0";
+    if (!origins && n > 0) return "null origins with n > 0";
+    if (!dirs && n > 0) return "null dirs with n > 0";
+    if ((uintptr_t)params % 4 != 0) return "params must be 4-byte aligned";
+    if ((uintptr_t)grad % 8 != 0) return "grad must be 8-byte aligned";
+    if ((uintptr_t)stats % 8 != 0) return "stats must be 8-byte aligned";
+    if (!targets && (grad || stats)) return "null targets with grad or stats set";
+    if (opt->basis_minmax[0] != 0 || opt->basis_minmax[1] != RTO_BASIS_MAX - 1)
+        return "options: basis_minmax is not read by the fit and must keep its default {0, 24}";
+    if (opt->rot_dirs[0] != 0.f || opt->rot_dirs[1] != 0.f || opt->rot_dirs[2] != 0.f)
+        return "options: rot_dirs is not read by the fit and must keep its default {0, 0, 0}";
+    const struct {
+        const float* p;
+        const char* name;
+    } arrays[4] = {{origins, "origins"}, {dirs, "dirs"}, {targets, "targets"}, {out, "out"}};
+    const int64_t bytes = n * 12;
+    for (const auto& a : arrays) {
+        if (!a.p) continue;
+        if ((uintptr_t)a.p % 4 != 0) return std::string(a.name) + " must be 4-byte aligned";
+        if (overlap(params, param_count * 4, a.p, bytes)) return std::string("params overlaps ") + a.name;
+        if (grad && overlap(grad, param_count * 8, a.p, bytes)) return std::string("grad overlaps ") + a.name;
+    }
+    if (out)
+        for (int k = 0; k < 3; ++k)
+            if (arrays[k].p && overlap(out, bytes, arrays[k].p, bytes)) return std::string("out overlaps ") + arrays[k].name;
+    return "";
+}
+
 namespace {
 
 template <int B>
@@ -128,6 +162,64 @@ void fit_cameras(const int32_t* child, const uint16_t* data, const float* params
     }
 }
 
+// the rays [i0, i1) of thread k of nt; integer sums, so the split changes no bit
+template <int B>
+void fit_rays(const int32_t* child, const uint16_t* data, const float* params, int N, const lm::Frame& fr, const fm::Opt& o, const float* origins,
+              const float* dirs, const float* targets, float* out, int64_t n, int nt, int64_t* grad, uint64_t* stats) {
+    constexpr int D = fm::data_dim_of<B>();
+    const auto locate = [&](const float* pos, lm::Leaf& leaf) -> bool {
+        for (int i = 0; i < 3; ++i) leaf.local[i] = pos[i];
+        const int64_t slot = lm::descend_child(child, N, leaf.local, leaf.cube_sz);
+        leaf.index = (uint32_t)slot;
+        leaf.sigma_bits = data[slot * D + D - 1];
+        return true;
+    };
+    const auto exp_ = [](float v) -> float { return lm::det_expf(v); };
+    const auto slot_of = [](uint32_t index) -> uint32_t { return index; };
+    const auto add = [&](int64_t index, float g) {
+        const int64_t q = fm::to_fixed(g);
+        if (q != 0) __atomic_fetch_add((uint64_t*)grad + index, (uint64_t)q, __ATOMIC_RELAXED);
+    };
+    const auto range = [&](int k) {
+        const int64_t i0 = n / nt * k + (k < n % nt ? k : n % nt), i1 = i0 + n / nt + (k < n % nt ? 1 : 0);
+        uint64_t loss = 0, rays = 0;
+        for (int64_t i = i0; i < i1; ++i) {
+            int64_t q;
+            if (fm::fit_ray<B>(fr, o, origins + i * 3, dirs + i * 3, params, targets ? targets + i * 3 : nullptr, out ? out + i * 3 : nullptr,
+                               grad != nullptr, locate, exp_, slot_of, add, q)) {
+                loss += (uint64_t)q;
+                ++rays;
+            }
+        }
+        if (stats && targets) {
+            __atomic_fetch_add(stats, loss, __ATOMIC_RELAXED);
+            __atomic_fetch_add(stats + 1, rays, __ATOMIC_RELAXED);
+        }
+    };
+    if (nt == 1) {
+        range(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (int k = 0; k < nt; ++k) pool.emplace_back(range, k);
+        for (auto& t : pool) t.join();
+    }
+}
+
+void host_frame_and_opt(const float scale[3], const float offset[3], const float* ndc, const rto_options* opt, lm::Frame& fr, fm::Opt& o) {
+    for (int i = 0; i < 3; ++i) {
+        fr.offset[i] = offset[i];
+        fr.scale[i] = scale[i];
+    }
+    fr.ndc_width = ndc && ndc[0] > 0 ? ndc[0] : -1.f;
+    fr.ndc_height = ndc ? ndc[1] : 0.f;
+    fr.ndc_focal = ndc ? ndc[2] : 0.f;
+    o.m.step_size = opt->step_size;
+    o.m.sigma_thresh = opt->sigma_thresh;
+    o.m.stop_thresh = opt->stop_thresh;
+    for (int i = 0; i < 6; ++i) o.m.render_bbox[i] = opt->render_bbox[i];
+    o.bg = opt->background_brightness;
+}
+
 }  // namespace
 
 int fit_grad_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int D, const char* data_format,
@@ -152,22 +244,51 @@ int fit_grad_host(const int32_t* child, const uint16_t* data, const float* param
     if (n == 0) return RTO_OK;
 
     lm::Frame fr;
-    for (int i = 0; i < 3; ++i) {
-        fr.offset[i] = offset[i];
-        fr.scale[i] = scale[i];
-    }
-    fr.ndc_width = ndc && ndc[0] > 0 ? ndc[0] : -1.f;
-    fr.ndc_height = ndc ? ndc[1] : 0.f;
-    fr.ndc_focal = ndc ? ndc[2] : 0.f;
     fm::Opt o;
-    o.m.step_size = opt->step_size;
-    o.m.sigma_thresh = opt->sigma_thresh;
-    o.m.stop_thresh = opt->stop_thresh;
-    for (int i = 0; i < 6; ++i) o.m.render_bbox[i] = opt->render_bbox[i];
-    o.bg = opt->background_brightness;
+    host_frame_and_opt(scale, offset, ndc, opt, fr, o);
     const int nt = threads <= 0 ? 1 : threads;
 #define RTO_FIT_CASE(B_) \
     case B_: fit_cameras<B_>(child, data, params, N, fr, o, cams, targets, images, n, nt, grad, stats); break
+    switch (B) {
+        RTO_FIT_CASE(0);
+        RTO_FIT_CASE(1);
+        RTO_FIT_CASE(4);
+        RTO_FIT_CASE(9);
+        RTO_FIT_CASE(16);
+        RTO_FIT_CASE(25);
+    }
+#undef RTO_FIT_CASE
+    return RTO_OK;
+}
+
+int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int D, const char* data_format,
+                       const float scale[3], const float offset[3], const float* ndc, const float* origins, const float* dirs,
+                       const float* targets, float* out, int64_t n, const rto_options* opt, int threads, int64_t* grad, uint64_t* stats,
+                       std::string* err) {
+    const auto fail = [&](int code, const std::string& msg) {
+        if (err) *err = msg;
+        return code;
+    };
+    if (!child || !data || !scale || !offset || !data_format) return fail(RTO_E_INVALID, "null argument");
+    if (capacity < 1 || N < 2 || D < 1) return fail(RTO_E_INVALID, "capacity >= 1, N >= 2 and data_dim >= 1 are required");
+    const int64_t N3 = (int64_t)N * N * N;
+    if (capacity > (((int64_t)1 << 31) - 1) / N3) return fail(RTO_E_INVALID, "capacity * N^3 must stay below 2^31");
+    const int B = fit_basis_of_format(data_format, D);
+    if (B < 0)
+        return fail(RTO_E_UNSUPPORTED, std::string("the fit takes RGBA and SH trees of basis_dim 1, 4, 9, 16 or 25, not ") + data_format +
+                                           " with data_dim " + std::to_string(D));
+    const std::string bad = fit_check_rays_call(params, origins, dirs, targets, out, n, opt, grad, stats, capacity * N3 * D);
+    if (!bad.empty()) return fail(RTO_E_INVALID, bad);
+    const std::string links = leaf_weights_check_links(child, capacity, N3);
+    if (!links.empty()) return fail(RTO_E_FORMAT, links);
+    if (n == 0) return RTO_OK;
+
+    lm::Frame fr;
+    fm::Opt o;
+    host_frame_and_opt(scale, offset, ndc, opt, fr, o);
+    const int nt = (int)std::min<int64_t>(threads <= 0 ? 1 : threads, n);
+#define RTO_FIT_CASE(B_) \
+    case B_: fit_rays<B_>(child, data, params, N, fr, o, origins, dirs, targets, out, n, nt, grad, stats); break
     switch (B) {
         RTO_FIT_CASE(0);
         RTO_FIT_CASE(1);

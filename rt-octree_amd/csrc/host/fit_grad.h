@@ -27,6 +27,17 @@ int fit_grad_host(const int32_t* child, const uint16_t* data, const float* param
                   const float scale[3], const float offset[3], const float* ndc, const rto_camera* cams, const float* const* targets,
                   float* const* images, int n, const rto_options* opt, int threads, int64_t* grad, uint64_t* stats, std::string* err);
 
+// the same for a call on rays (rto_tree_fit_grad_rays / rto_fit_grad_rays_host): origins, dirs, targets, out are [n][3] floats
+std::string fit_check_rays_call(const float* params, const float* origins, const float* dirs, const float* targets, const float* out, int64_t n,
+                                const rto_options* opt, const int64_t* grad, const uint64_t* stats, int64_t param_count);
+
+// fit_grad_host on n rays of the caller's (rto_fit_grad_rays_host): `threads` threads (<= 0: one) over contiguous ranges of rays;
+// the result does not depend on `threads`.
+int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int D, const char* data_format,
+                       const float scale[3], const float offset[3], const float* ndc, const float* origins, const float* dirs,
+                       const float* targets, float* out, int64_t n, const rto_options* opt, int threads, int64_t* grad, uint64_t* stats,
+                       std::string* err);
+
 // p = p - lr * g over count parameters, g from the fixed-point word, which is zeroed
 int fit_sgd_step_host(float* params, int64_t* grad, int64_t count, float lr, std::string* err);
 

@@ -1,13 +1,26 @@
-// rto_fit_abi.cpp -- C ABI of the tree fit (include/rto.h "tree fit"): the device entries (fit_kernels.hip) and the host twins
+// rto_fit_abi.cpp -- C ABI of the tree fit (include/rto.h "tree fit"): the device entries (fit_kernels.hip, fit_rays_kernels.hip) and the host twins
 // (host/fit_grad.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "host/fit_grad.h"
 #include "rto_fit_launch.h"
 #include "rto_internal.h"
+
+namespace {
+
+// threads per workgroup of the ray kernel: kFitRaysBlock; RTO_FIT_RAYS_BLOCK=128|256 is the measuring hook of
+// tools/fit_rays_bench.py (the bytes do not depend on it)
+int fit_rays_block() {
+    const char* e = std::getenv("RTO_FIT_RAYS_BLOCK");
+    const int b = e ? std::atoi(e) : 0;
+    return b == 128 || b == 256 ? b : rto::kFitRaysBlock;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -66,6 +79,49 @@ int rto_tree_fit_grad(const rto_tree* tree, const float* params, const rto_camer
     return RTO_OK;
 }
 
+int rto_tree_fit_grad_rays(const rto_tree* tree, const float* params, const float* origins, const float* dirs, const float* targets, float* out,
+                           int64_t n, const rto_options* opt, int64_t* grad, uint64_t* stats, void* stream) {
+    const std::string w = "rto_tree_fit_grad_rays: ";
+    if (!tree) return set_err(RTO_E_INVALID, w + "null tree");
+    const rto_tree_info& ti = tree->info;
+    const int basis = rto::fit_basis_of_tree(ti.format, ti.basis_dim, ti.data_dim);
+    if (basis < 0) return set_err(RTO_E_UNSUPPORTED, w + "the fit takes RGBA and SH trees of basis_dim 1, 4, 9, 16 or 25");
+    if (tree->quant) return set_err(RTO_E_UNSUPPORTED, w + "a tree loaded with RTO_TREE_QUANT_DIRECT has no leaf values to fit");
+    if (tree->d_recidx) return set_err(RTO_E_UNSUPPORTED, w + "a tree loaded with RTO_TREE_COMPACT_RECORDS is not taken");
+    int walk;
+    rto::ValuesSrc vs;
+    (void)query_plan(tree, false, &walk, &vs);
+    if (walk == rto::kWalkChild && !(tree->dev.child && tree->dev.data))
+        return set_err(RTO_E_UNSUPPORTED, w + "the tree has neither a traversal image nor child[] / data[] resident");
+    const int64_t count = ti.capacity * tree->dev.N3 * ti.data_dim;
+    const std::string bad = rto::fit_check_rays_call(params, origins, dirs, targets, out, n, opt, grad, stats, count);
+    if (!bad.empty()) return set_err(RTO_E_INVALID, w + bad);
+    const struct {
+        const void* p;
+        const char* name;
+    } mem[7] = {{params, "params"}, {grad, "grad"}, {stats, "stats"}, {origins, "origins"}, {dirs, "dirs"}, {targets, "targets"}, {out, "out"}};
+    for (const auto& m : mem)
+        if (m.p && pointer_device(m.p) != tree->device) return set_err(RTO_E_INVALID, w + m.name + " is not memory of the tree's device");
+    if (n == 0) return RTO_OK;
+    DeviceGuard guard(tree->device);
+    if (!guard.ok) return set_err(RTO_E_HIP, "hipSetDevice failed");
+    rto::fm::Opt o;
+    o.m.step_size = opt->step_size;
+    o.m.sigma_thresh = opt->sigma_thresh;
+    o.m.stop_thresh = opt->stop_thresh;
+    for (int i = 0; i < 6; ++i) o.m.render_bbox[i] = opt->render_bbox[i];
+    o.bg = opt->background_brightness;
+    // a launch takes at most kFitRaysPerLaunch rays: the pointers advance, so every index inside a launch stays small
+    for (int64_t i0 = 0; i0 < n; i0 += rto::kFitRaysPerLaunch) {
+        const int64_t k = std::min(n - i0, rto::kFitRaysPerLaunch);
+        const hipError_t e = rto::launch_fit_grad_rays(tree->dev, walk, basis, o, (const uint32_t*)tree->d_node_old, params, origins + i0 * 3,
+                                                       dirs + i0 * 3, targets ? targets + i0 * 3 : nullptr, out ? out + i0 * 3 : nullptr, k,
+                                                       fit_rays_block(), grad, stats, (hipStream_t)stream);
+        if (e != hipSuccess) return set_err(RTO_E_HIP, w + "launch failed: " + hipGetErrorString(e));
+    }
+    return RTO_OK;
+}
+
 int rto_fit_sgd_step(float* params, int64_t* grad, int64_t count, float lr, void* stream) {
     const std::string w = "rto_fit_sgd_step: ";
     if (!params || !grad) return set_err(RTO_E_INVALID, w + "null params or grad");
@@ -89,6 +145,17 @@ int rto_fit_grad_host(const int32_t* child, const uint16_t* data, const float* p
     const int rc = rto::fit_grad_host(child, data, params, capacity, N, data_dim, data_format, scale, offset, ndc, cams, targets, images, n, opt,
                                       threads, grad, stats, &err);
     if (rc != RTO_OK) return set_err(rc, "rto_fit_grad_host: " + err);
+    return RTO_OK;
+}
+
+int rto_fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int data_dim,
+                           const char* data_format, const float scale[3], const float offset[3], const float* ndc, const float* origins,
+                           const float* dirs, const float* targets, float* out, int64_t n, const rto_options* opt, int threads, int64_t* grad,
+                           uint64_t* stats) {
+    std::string err;
+    const int rc = rto::fit_grad_rays_host(child, data, params, capacity, N, data_dim, data_format, scale, offset, ndc, origins, dirs, targets, out,
+                                           n, opt, threads, grad, stats, &err);
+    if (rc != RTO_OK) return set_err(rc, "rto_fit_grad_rays_host: " + err);
     return RTO_OK;
 }
 

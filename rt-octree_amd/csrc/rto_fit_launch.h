@@ -1,4 +1,5 @@
-// rto_fit_launch.h -- launchers of fit_kernels.hip (rto_tree_fit_grad / rto_fit_sgd_step, include/rto.h "tree fit").
+// rto_fit_launch.h -- launchers of fit_kernels.hip and fit_rays_kernels.hip (rto_tree_fit_grad / rto_tree_fit_grad_rays /
+// rto_fit_sgd_step, include/rto.h "tree fit").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,14 @@ struct FitPlanes {
 // stats: two words or nullptr.
 hipError_t launch_fit_grad(const TreeDev& tree, int walk, int basis, const fm::Opt& opt, const LayerCams& cams, const FitPlanes& planes,
                            int frames, const uint32_t* node_old, const float* params, int64_t* grad, uint64_t* stats, hipStream_t stream);
+
+// fit_rays_kernels.hip: n (<= kFitRaysPerLaunch) rays of the caller's, one lane per ray, workgroups of `block` threads (64, 128
+// or 256; kFitRaysBlock is the library's choice).  origins / dirs [n][3]; targets / out [n][3] or nullptr; the rest as above.
+constexpr int64_t kFitRaysPerLaunch = (int64_t)1 << 30;
+constexpr int kFitRaysBlock = 64;
+hipError_t launch_fit_grad_rays(const TreeDev& tree, int walk, int basis, const fm::Opt& opt, const uint32_t* node_old, const float* params,
+                                const float* origins, const float* dirs, const float* targets, float* out, int64_t n, int block,
+                                int64_t* grad, uint64_t* stats, hipStream_t stream);
 
 // params[i] -= lr * g(grad[i]); grad[i] = 0 for i < count
 hipError_t launch_fit_sgd_step(float* params, int64_t* grad, int64_t count, float lr, hipStream_t stream);

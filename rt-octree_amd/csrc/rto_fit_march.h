@@ -3,6 +3,7 @@
 // colour per dense leaf (the forward march), and marched a second time with the same operations for the gradient of
 // 1/2 |out - target|^2 with respect to the leaf values (the backward march).  Gradients leave through add(index, g): the caller
 // converts them to fixed point (to_fixed) and adds integers, so no order of rays, threads or calls can change a bit.
+// rto_tree_fit_grad_rays (fit_rays_kernels.hip) marches the same ray from a caller's origin and direction: ray_begin_ray, fit_ray.
 //
 // Built on lm::ray_setup / ray_enter / dda_unit / half_to_float; the locate / exp functors are those of lm::march_pixel.  It
 // carries its own RTO_HD copy of the SH basis (sh_basis of rto_tree_device.h, the same operations) so that a plain C++ compiler
@@ -115,6 +116,41 @@ RTO_HD inline void ray_begin(const lm::Frame& fr, const Opt& o, const lm::Cam& c
     if (r.hit) r.hit = lm::ray_enter(fr, o.m, r.dir, r.cen, r.invdir, r.delta_scale, r.tmin, r.tmax);
 }
 
+// ray_begin's sibling for a ray the caller supplies (rto_tree_fit_grad_rays): the ray of a pixel whose set-up produced
+// dir = vdir = normalize3(direction) and cen = origin.  From there on lm::ray_setup's tail -- the NDC warp, then
+// offset + scale * cen -- by ray_setup's operations in ray_setup's order, and ray_begin's own.  A zero or non-finite direction
+// and a non-finite origin leave a non-finite dir or cen: the ray is not marched (hit = false), by arithmetic alone.
+template <int B>
+RTO_HD inline void ray_begin_ray(const lm::Frame& fr, const Opt& o, const float* origin, const float* direction, Ray& r, float* Y) {
+    float vdir[3] = {direction[0], direction[1], direction[2]};
+    lm::normalize3(vdir);
+    float* dir = r.dir;
+    float* cen = r.cen;
+    for (int i = 0; i < 3; ++i) {
+        dir[i] = vdir[i];
+        cen[i] = origin[i];
+    }
+    if (fr.ndc_width > 0) {
+        const float t = -(1.f + cen[2]) / dir[2];
+        for (int i = 0; i < 3; ++i) cen[i] = cen[i] + t * dir[i];
+        dir[0] = -((2 * fr.ndc_focal) / fr.ndc_width) * (dir[0] / dir[2] - cen[0] / cen[2]);
+        dir[1] = -((2 * fr.ndc_focal) / fr.ndc_height) * (dir[1] / dir[2] - cen[1] / cen[2]);
+        dir[2] = -2 / cen[2];
+        cen[0] = -((2 * fr.ndc_focal) / fr.ndc_width) * (cen[0] / cen[2]);
+        cen[1] = -((2 * fr.ndc_focal) / fr.ndc_height) * (cen[1] / cen[2]);
+        cen[2] = 1 + 2 / cen[2];
+        lm::normalize3(dir);
+    }
+    for (int i = 0; i < 3; ++i) cen[i] = fr.offset[i] + fr.scale[i] * cen[i];
+    r.hit = true;
+    for (int i = 0; i < 3; ++i)
+        if (!lm::finite_f(r.dir[i]) || !lm::finite_f(r.cen[i])) r.hit = false;
+    if constexpr (B > 0) sh_basis<B>(vdir, Y);
+    r.delta_scale = r.tmin = r.tmax = 0.f;
+    r.invdir[0] = r.invdir[1] = r.invdir[2] = 0.f;
+    if (r.hit) r.hit = lm::ray_enter(fr, o.m, r.dir, r.cen, r.invdir, r.delta_scale, r.tmin, r.tmax);
+}
+
 // colour of a dense leaf from its values p[0 .. D-2]
 template <int B, class Exp>
 RTO_HD inline void leaf_colour(const float* p, const float* Y, Exp exp_, float* c) {
@@ -206,6 +242,32 @@ RTO_HD inline bool fit_pixel(const lm::Frame& fr, const Opt& o, const lm::Cam& c
     march<B, false>(r, o, Y, params, locate, exp_, slot_of, out, res, add);
     if (image)
         for (int ch = 0; ch < 3; ++ch) image[ch] = out[ch];
+    if (!target) return true;
+    for (int ch = 0; ch < 3; ++ch) res[ch] = out[ch] - tg[ch];
+    loss_q = to_fixed((res[0] * res[0] + res[1] * res[1]) + res[2] * res[2]);
+    if (backward) march<B, true>(r, o, Y, params, locate, exp_, slot_of, out, res, add);
+    return true;
+}
+
+// One ray of the caller's (rto_tree_fit_grad_rays): fit_pixel with ray_begin_ray in place of ray_begin, the same text after it.
+// origin, direction: three floats each; target: three floats or nullptr; out: where the colour goes, or nullptr
+template <int B, class Locate, class Exp, class SlotOf, class Add>
+RTO_HD inline bool fit_ray(const lm::Frame& fr, const Opt& o, const float* origin, const float* direction, const float* params,
+                           const float* target, float* out_px, bool backward, Locate locate, Exp exp_, SlotOf slot_of, Add add,
+                           int64_t& loss_q) {
+    loss_q = 0;
+    float tg[3] = {0.f, 0.f, 0.f};
+    if (target) {
+        for (int ch = 0; ch < 3; ++ch) tg[ch] = target[ch];
+        if (tg[0] != tg[0] || tg[1] != tg[1] || tg[2] != tg[2]) return false;
+    }
+    Ray r;
+    float Y[B > 0 ? B : 1];
+    ray_begin_ray<B>(fr, o, origin, direction, r, Y);
+    float out[3], res[3];
+    march<B, false>(r, o, Y, params, locate, exp_, slot_of, out, res, add);
+    if (out_px)
+        for (int ch = 0; ch < 3; ++ch) out_px[ch] = out[ch];
     if (!target) return true;
     for (int ch = 0; ch < 3; ++ch) res[ch] = out[ch] - tg[ch];
     loss_q = to_fixed((res[0] * res[0] + res[1] * res[1]) + res[2] * res[2]);

@@ -75,6 +75,44 @@ def fit_grad(tree, params, cams, targets=None, options=None, grad=None, stats=No
     return grad
 
 
+def fit_grad_rays(tree, params, origins, dirs, targets=None, options=None, grad=None, stats=None, out=None, stream=None):
+    """rto_tree_fit_grad_rays: fit_grad on n rays of the caller's.  origins / dirs [n,3] (dirs of any length), targets [n,3] or
+    None (a NaN masks its ray), out [n,3] or None (where the composited colours go): contiguous float32 torch tensors on the
+    tree's device, or numpy arrays (copied over; pass a tensor for `out`) -- volrend._ray_tensor's rules.  volrend.camera_rays(cam)
+    gives the rays on which this is fit_grad on the camera, bit for bit.  params, grad, stats as fit_grad takes them.
+    Accumulates into grad and stats.  Asynchronous on `stream` (default: torch's current stream); no sync."""
+    import torch
+    from .volrend import _ray_tensor
+    device = torch.device("cuda", tree.device)
+    shape = (int(tree.capacity), int(tree.N), int(tree.N), int(tree.N), int(tree.data_dim))
+
+    def on_device(t, dtype, shp):
+        return isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.device == device and tuple(t.shape) == shp
+
+    if not on_device(params, torch.float32, shape):
+        raise RtoError(-1, "params must be a contiguous float32 tensor of shape %s on %s" % (list(shape), device))
+    if grad is not None and not on_device(grad, torch.int64, shape):
+        raise RtoError(-1, "grad must be a contiguous int64 tensor of shape %s on %s" % (list(shape), device))
+    if stats is not None and not on_device(stats, torch.int64, (2,)):
+        raise RtoError(-1, "stats must be a contiguous int64 tensor of shape [2] on %s" % device)
+    n = int(origins.shape[0])
+    o = _ray_tensor(origins, "origins", 3, n, device)
+    d = _ray_tensor(dirs, "dirs", 3, n, device)
+    tg = None if targets is None else _ray_tensor(targets, "targets", 3, n, device)
+    if out is not None and not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a torch tensor: it is written")
+    ou = None if out is None else _ray_tensor(out, "out", 3, n, device)
+    if n == 0:  # (an empty tensor has no address to pass; the entry launches nothing)
+        return grad
+    co = _options(options)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib().rto_tree_fit_grad_rays(tree._h, ptr(params), ptr(o), ptr(d), ptr(tg), ptr(ou), n, C.byref(co), ptr(grad), ptr(stats),
+                                       _stream_ptr(stream)))
+    return grad
+
+
 def sgd_step(params, grad, lr, stream=None):
     """rto_fit_sgd_step: params -= lr * grad (fixed point -> float), grad = 0; torch tensors of one device and one shape"""
     import torch
@@ -123,6 +161,53 @@ def fit_grad_host(child, data, params, scale, offset, data_format, cams, targets
                                   child.shape[1], data.shape[4], str(data_format).encode(), sc, of, nd, arr, tg, im, n, C.byref(co),
                                   int(threads), C.c_void_p(grad.ctypes.data) if grad is not None else None,
                                   C.c_void_p(stats.ctypes.data) if stats is not None else None))
+    return grad
+
+
+def _host_rays(a, name, n, written=False):
+    """a contiguous float32 numpy array [n, 3]: volrend._ray_tensor's rules on the host"""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("%s must be a numpy array" % name)
+    if a.dtype != np.float32 or not a.flags.c_contiguous or a.shape != (n, 3) or (written and not a.flags.writeable):
+        raise RtoError(-1, "%s must be a contiguous float32 array of shape %s" % (name, [n, 3]))
+    return a
+
+
+def fit_grad_rays_host(child, data, params, scale, offset, data_format, origins, dirs, targets=None, options=None, ndc=None, threads=0,
+                       grad=None, stats=None, out=None):
+    """rto_fit_grad_rays_host: fit_grad_rays from numpy arrays (the tree's as fit_grad_host takes them; origins, dirs, targets, out
+    float32 [n,3]); no device is touched.  threads <= 0: one thread; the result does not depend on it."""
+    child = np.ascontiguousarray(child)
+    data = np.ascontiguousarray(data)
+    if data.dtype == np.float16:
+        data = data.view(np.uint16)
+    if child.dtype != np.int32 or data.dtype != np.uint16:
+        raise RtoError(-1, "child must be int32 and data float16")
+    if child.ndim != 4 or data.ndim != 5 or data.shape[:4] != child.shape or not (child.shape[1] == child.shape[2] == child.shape[3]):
+        raise RtoError(-1, "child must be [capacity,N,N,N] and data [capacity,N,N,N,D], not %s and %s" % (list(child.shape), list(data.shape)))
+
+    def on_host(a, dtype, shp):
+        return isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.c_contiguous and a.shape == shp
+
+    if not on_host(params, np.float32, data.shape):
+        raise RtoError(-1, "params must be a contiguous float32 array of shape %s" % (list(data.shape),))
+    if grad is not None and not (on_host(grad, np.int64, data.shape) and grad.flags.writeable):
+        raise RtoError(-1, "grad must be a contiguous int64 array of shape %s" % (list(data.shape),))
+    if stats is not None and not on_host(stats, np.int64, (2,)):
+        raise RtoError(-1, "stats must be a contiguous int64 array of shape [2]")
+    n = int(np.shape(origins)[0]) if np.ndim(origins) else 0
+    o = _host_rays(origins, "origins", n)
+    d = _host_rays(dirs, "dirs", n)
+    tg = None if targets is None else _host_rays(targets, "targets", n)
+    ou = None if out is None else _host_rays(out, "out", n, written=True)
+    sc = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(scale, np.float32), (3,))])
+    of = (C.c_float * 3)(*[float(x) for x in np.broadcast_to(np.asarray(offset, np.float32), (3,))])
+    nd = None if ndc is None else (C.c_float * 3)(*[float(x) for x in ndc])
+    co = _options(options)
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(lib().rto_fit_grad_rays_host(ptr(child), ptr(data), ptr(params), child.shape[0], child.shape[1], data.shape[4],
+                                       str(data_format).encode(), sc, of, nd, ptr(o), ptr(d), ptr(tg), ptr(ou), n, C.byref(co), int(threads),
+                                       ptr(grad), ptr(stats)))
     return grad
 
 
@@ -184,6 +269,22 @@ class TreeFit:
         fit_grad(self.tree, self.params, cams, None, self.options, images=images, stream=stream)
         return images
 
+    def accumulate_rays(self, origins, dirs, targets, stream=None):
+        """accumulate() on rays of the caller's (fit_grad_rays): [n,3] tensors on the device, or numpy arrays"""
+        fit_grad_rays(self.tree, self.params, origins, dirs, targets, self.options, grad=self.grad, stats=self.stats, stream=stream)
+
+    def evaluate_rays(self, origins, dirs, targets, stream=None):
+        """(loss, rays) of params over the rays: forward only, through stats (which it clears)"""
+        fit_grad_rays(self.tree, self.params, origins, dirs, targets, self.options, stats=self.stats, stream=stream)
+        return self.loss()
+
+    def render_rays(self, origins, dirs, stream=None):
+        """the composited colours of params along the rays: a float32 [n,3] tensor"""
+        import torch
+        out = torch.empty((int(origins.shape[0]), 3), dtype=torch.float32, device=self.params.device)
+        fit_grad_rays(self.tree, self.params, origins, dirs, None, self.options, out=out, stream=stream)
+        return out
+
     def data_half(self):
         """params rounded to float16 (to nearest even) as a numpy array: what a tree file stores"""
         return self.params.cpu().numpy().astype(np.float16)
@@ -227,6 +328,22 @@ class HostTreeFit:
         images = [np.empty((int(c.height), int(c.width), 3), np.float32) for c in cams]
         self._call(cams, None, images=images)
         return images
+
+    def _call_rays(self, origins, dirs, targets, **kw):
+        fit_grad_rays_host(self.child, self.data, self.params, self.scale, self.offset, self.data_format, origins, dirs, targets, self.options,
+                           ndc=self.ndc, threads=self.threads, **kw)
+
+    def accumulate_rays(self, origins, dirs, targets):
+        self._call_rays(origins, dirs, targets, grad=self.grad, stats=self.stats)
+
+    def evaluate_rays(self, origins, dirs, targets):
+        self._call_rays(origins, dirs, targets, stats=self.stats)
+        return self.loss()
+
+    def render_rays(self, origins, dirs):
+        out = np.empty((int(origins.shape[0]), 3), np.float32)
+        self._call_rays(origins, dirs, None, out=out)
+        return out
 
     def data_half(self):
         return self.params.astype(np.float16)
