@@ -1055,6 +1055,72 @@ int rto_fit_grad_rays_host(const int32_t* child, const uint16_t* data, const flo
                            const char* data_format, const float scale[3], const float offset[3], const float* ndc /* {w,h,focal} or NULL */,
                            const float* origins, const float* dirs, const float* targets, float* out, int64_t n, const rto_options* opt,
                            int threads, int64_t* grad, uint64_t* stats);
+/* The SPARSE step: remember which leaves a batch reached, and step those rows only -- so that a small batch does not stream the
+ * whole of params and grad, and so that an optimiser with moments (RMSProp, Adam) touches its state only there.
+ *   touched  a bitmap uint32_t[(slots + 31) / 32], slots = capacity * N^3: slot s is bit s & 31 of word s >> 5, in the numbering
+ *            of params.  A call sets the bit of every slot that the backward march of an unmasked ray visits as a DENSE sample:
+ *            exactly the slots for which the backward march adds a contribution, whether or not its fixed-point value is zero.
+ *            The call ACCUMULATES into the bitmap as it does into grad; the caller zeroes it.  The set does not depend on the
+ *            order of the rays, on splits over calls or on threads, and every slot with a non-zero grad word has its bit set.
+ *            A masked ray, a miss and a ray that is not marched mark nothing.
+ * rto_tree_fit_grad_rays_touched: rto_tree_fit_grad_rays plus the bitmap.  grad and touched are both REQUIRED (a forward-only
+ * call uses rto_tree_fit_grad_rays); the out, grad and stats bytes are those of rto_tree_fit_grad_rays.  RTO_E_INVALID, decided
+ * before anything is enqueued, with a text naming the argument: everything rto_tree_fit_grad_rays refuses; a null grad or
+ * touched; touched not 4-byte aligned; touched overlapping params, grad, stats, origins, dirs, targets or out; touched not
+ * memory of the tree's device.  Cameras need no entry of their own: on the rays of a camera the ray entry gives the camera
+ * entry's bytes (the identity above).  rto_fit_grad_rays_touched_host is the host twin.
+ *   list     rto_fit_touched_list writes the set slots in ASCENDING order to list[] and their total number to count[0]; only
+ *            the first min(count, list_capacity) are written.  clear != 0 zeroes the bitmap in the same pass.  Bits at or beyond
+ *            `slots` in the last word are ignored, and cleared under clear.  Asynchronous on `stream`: no allocation, no host
+ *            synchronisation, no copy; three launches (a popcount sum per block of RTO_FIT_TOUCHED_BLOCK_WORDS words, one
+ *            workgroup that scans the block sums, the scatter), no workgroup waits for another.  scratch: device memory of
+ *            rto_fit_touched_scratch_bytes(slots) bytes, 4-byte aligned.  0 <= slots < 2^31.  RTO_E_INVALID: a null touched,
+ *            count or scratch, a null list with list_capacity > 0, slots or list_capacity out of range, scratch_bytes too
+ *            small, touched / list / scratch not 4-byte or count not 8-byte aligned, memory of different devices.
+ *            rto_fit_touched_list_host is the host twin, without scratch.
+ *   step     rto_fit_step_sparse: for every list position j < min(count[0], list_capacity), s = list[j] (an entry >= slots is
+ *            skipped) and every k < row, on element i = s * row + k, all in float32, every operation rounded once, no FMA,
+ *            IEEE division and sqrtf (csrc/rto_fit_optim.h states it once for the kernel and the host twin):
+ *                g = from_fixed(grad[i]) * grad_scale;   grad[i] = 0
+ *                RTO_FIT_SGD      p = p - lr * g
+ *                RTO_FIT_RMSPROP  v = beta2 * v + ((1.f - beta2) * g) * g
+ *                                 p = p - lr * (g / (sqrtf(v) + eps))
+ *                RTO_FIT_ADAM     m = beta1 * m + (1.f - beta1) * g
+ *                                 v = beta2 * v + ((1.f - beta2) * g) * g
+ *                                 p = p - lr * ((m / bias1) / (sqrtf(v / bias2) + eps))
+ *            bias1 and bias2 are the CALLER's floats, 1 - beta^t for step t: the entry counts no steps.  The moments of a leaf
+ *            that was not listed do NOT decay: the lazy rule of torch.optim.SparseAdam and of Plenoxels.  With grad_scale == 1.f
+ *            and a finite lr >= 0, RTO_FIT_SGD over a list that covers every non-zero grad row leaves the bytes of
+ *            rto_fit_sgd_step in params and an all-zero grad.  m and v are float32 arrays like params (m: ADAM only; v: RMSPROP
+ *            and ADAM; else ignored).  count is read ON THE DEVICE: a step needs no host round trip; count[0] == 0 does nothing.
+ *            Asynchronous; a grid of fixed size, no atomics.  RTO_E_INVALID: a null params, grad, list, count or options; a
+ *            pointer not aligned (4 bytes, grad and count 8); row < 1; slots or list_capacity out of range; an unknown kind; a
+ *            null m for ADAM or v for RMSPROP / ADAM; memory of different devices.  rto_fit_step_sparse_host is the host twin. */
+#define RTO_FIT_SGD 0
+#define RTO_FIT_RMSPROP 1
+#define RTO_FIT_ADAM 2
+#define RTO_FIT_TOUCHED_BLOCK_WORDS 2048 /* bitmap words per workgroup of the list's sum and scatter launches */
+typedef struct rto_fit_optim {
+    int kind; /* RTO_FIT_SGD, RTO_FIT_RMSPROP, RTO_FIT_ADAM */
+    float lr, grad_scale, beta1, beta2, eps, bias1, bias2;
+} rto_fit_optim;
+int rto_tree_fit_grad_rays_touched(const rto_tree* tree, const float* params, const float* origins, const float* dirs,
+                                   const float* targets, float* out, int64_t n, const rto_options* opt, int64_t* grad,
+                                   uint64_t* stats, uint32_t* touched /* device [(slots + 31) / 32] */, void* stream);
+int rto_fit_grad_rays_touched_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int data_dim,
+                                   const char* data_format, const float scale[3], const float offset[3], const float* ndc,
+                                   const float* origins, const float* dirs, const float* targets, float* out, int64_t n,
+                                   const rto_options* opt, int threads, int64_t* grad, uint64_t* stats, uint32_t* touched);
+int rto_fit_touched_block_words(void); /* RTO_FIT_TOUCHED_BLOCK_WORDS of the library */
+int64_t rto_fit_touched_scratch_bytes(int64_t slots); /* -1: slots out of range */
+int rto_fit_touched_list(uint32_t* touched, int64_t slots, int clear, uint32_t* list, int64_t list_capacity,
+                         uint64_t* count /* device [1] */, void* scratch, int64_t scratch_bytes, void* stream);
+int rto_fit_touched_list_host(uint32_t* touched, int64_t slots, int clear, uint32_t* list, int64_t list_capacity, uint64_t* count);
+int rto_fit_step_sparse(float* params, int64_t* grad, float* m /* ADAM only */, float* v /* RMSPROP, ADAM */, int64_t slots,
+                        int row /* D */, const uint32_t* list, const uint64_t* count /* device [1] */, int64_t list_capacity,
+                        const rto_fit_optim* o, void* stream);
+int rto_fit_step_sparse_host(float* params, int64_t* grad, float* m, float* v, int64_t slots, int row, const uint32_t* list,
+                             const uint64_t* count, int64_t list_capacity, const rto_fit_optim* o);
 
 /* ---- grid builder (the first step of PlenOctree extraction: a field evaluated on a regular grid becomes an octree; svox does
  * it on the CPU, the reference holds no counterpart) ----

@@ -17,6 +17,7 @@ from .simplify import Simplifier, simplify_tree  # noqa: F401
 from .visibility import leaf_weights, leaf_weights_host, kill_unseen  # noqa: F401
 from .grid_build import TreeBuilder, build_tree, tree_to_grid  # noqa: F401
 from .fit import TreeFit, HostTreeFit, fit_grad, fit_grad_host, fit_grad_rays, fit_grad_rays_host, sgd_step, sgd_step_host  # noqa: F401
+from .fit import fit_optim, step_sparse, step_sparse_host, touched_list, touched_list_host, touched_words  # noqa: F401
 from .refine import Refiner, refine_tree, refine_tree_host, keys_from_weights, keys_from_density  # noqa: F401
 
 __all__ = [
@@ -30,5 +31,6 @@ __all__ = [
     "leaf_weights", "leaf_weights_host", "kill_unseen",
     "TreeBuilder", "build_tree", "tree_to_grid",
     "TreeFit", "HostTreeFit", "fit_grad", "fit_grad_host", "fit_grad_rays", "fit_grad_rays_host", "sgd_step", "sgd_step_host",
+    "fit_optim", "step_sparse", "step_sparse_host", "touched_list", "touched_list_host", "touched_words",
     "Refiner", "refine_tree", "refine_tree_host", "keys_from_weights", "keys_from_density",
 ]

@@ -124,6 +124,12 @@ class CRefineStats(C.Structure):
                 ("cut_key", C.c_int64)]
 
 
+class CFitOptim(C.Structure):
+    """rto_fit_optim (include/rto.h)"""
+    _fields_ = [("kind", C.c_int), ("lr", C.c_float), ("grad_scale", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("bias1", C.c_float), ("bias2", C.c_float)]
+
+
 # every symbol include/rto.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -253,6 +259,16 @@ SYMBOLS = {
     "rto_tree_fit_grad_rays": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(COptions), _P, _P, _P]),
     "rto_fit_grad_rays_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, C.POINTER(COptions), C.c_int, _P, _P]),
+    "rto_tree_fit_grad_rays_touched": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(COptions), _P, _P, _P, _P]),
+    "rto_fit_grad_rays_touched_host": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64,
+                                                 C.POINTER(COptions), C.c_int, _P, _P, _P]),
+    "rto_fit_touched_block_words": (C.c_int, []),
+    "rto_fit_touched_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "rto_fit_touched_list": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "rto_fit_touched_list_host": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int64, _P]),
+    "rto_fit_step_sparse": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(CFitOptim), _P]),
+    "rto_fit_step_sparse_host": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.POINTER(CFitOptim)]),
     "rto_tree_builder_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "rto_tree_builder_free": (None, [_P]),
     "rto_tree_build_plan": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(CGridBuildStats)]),

@@ -1,4 +1,4 @@
-// host/fit_grad.cpp -- the host twin of rto_tree_fit_grad, rto_tree_fit_grad_rays and rto_fit_sgd_step: the marches of
+// host/fit_grad.cpp -- the host twin of rto_tree_fit_grad, rto_tree_fit_grad_rays (with or without the touched bitmap) and rto_fit_sgd_step: the marches of
 // rto_fit_march.h over child[] / data[] with the root-restart float descent, det_expf restated in plain C++.  Same bits as the
 // kernels (tests/test_fit_gpu.py, tests/test_fit_rays_gpu.py) and as the numpy restatements (tests/fit_ref.py,
 // tests/fit_rays_ref.py).  No HIP header.
@@ -107,6 +107,23 @@ std::string fit_check_rays_call(const float* params, const float* origins, const
     return "";
 }
 
+std::string fit_check_touched(const float* params, const float* origins, const float* dirs, const float* targets, const float* out, int64_t n,
+                              const int64_t* grad, const uint64_t* stats, const uint32_t* touched, int64_t slots, int D) {
+    if (!grad) return "null grad: a forward-only call uses the entry without the bitmap";
+    if (!touched) return "null touched";
+    if ((uintptr_t)touched % 4 != 0) return "touched must be 4-byte aligned";
+    const int64_t t_bytes = ((slots + 31) >> 5) * 4;
+    const struct {
+        const void* p;
+        int64_t bytes;
+        const char* name;
+    } arrays[7] = {{params, slots * D * 4, "params"}, {grad, slots * D * 8, "grad"}, {stats, 16, "stats"},   {origins, n * 12, "origins"},
+                   {dirs, n * 12, "dirs"},            {targets, n * 12, "targets"},  {out, n * 12, "out"}};
+    for (const auto& a : arrays)
+        if (a.p && overlap(touched, t_bytes, a.p, a.bytes)) return std::string("touched overlaps ") + a.name;
+    return "";
+}
+
 namespace {
 
 template <int B>
@@ -165,7 +182,7 @@ void fit_cameras(const int32_t* child, const uint16_t* data, const float* params
 // the rays [i0, i1) of thread k of nt; integer sums, so the split changes no bit
 template <int B>
 void fit_rays(const int32_t* child, const uint16_t* data, const float* params, int N, const lm::Frame& fr, const fm::Opt& o, const float* origins,
-              const float* dirs, const float* targets, float* out, int64_t n, int nt, int64_t* grad, uint64_t* stats) {
+              const float* dirs, const float* targets, float* out, int64_t n, int nt, int64_t* grad, uint64_t* stats, uint32_t* touched) {
     constexpr int D = fm::data_dim_of<B>();
     const auto locate = [&](const float* pos, lm::Leaf& leaf) -> bool {
         for (int i = 0; i < 3; ++i) leaf.local[i] = pos[i];
@@ -177,6 +194,10 @@ void fit_rays(const int32_t* child, const uint16_t* data, const float* params, i
     const auto exp_ = [](float v) -> float { return lm::det_expf(v); };
     const auto slot_of = [](uint32_t index) -> uint32_t { return index; };
     const auto add = [&](int64_t index, float g) {
+        if (touched && index % D == D - 1) {  // the density's contribution, the first of a dense sample: mark the slot
+            const int64_t slot = index / D;
+            __atomic_fetch_or(touched + (slot >> 5), 1u << (slot & 31), __ATOMIC_RELAXED);
+        }
         const int64_t q = fm::to_fixed(g);
         if (q != 0) __atomic_fetch_add((uint64_t*)grad + index, (uint64_t)q, __ATOMIC_RELAXED);
     };
@@ -265,6 +286,14 @@ int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* 
                        const float scale[3], const float offset[3], const float* ndc, const float* origins, const float* dirs,
                        const float* targets, float* out, int64_t n, const rto_options* opt, int threads, int64_t* grad, uint64_t* stats,
                        std::string* err) {
+    return fit_grad_rays_touched_host(child, data, params, capacity, N, D, data_format, scale, offset, ndc, origins, dirs, targets, out, n, opt,
+                                      threads, grad, stats, nullptr, false, err);
+}
+
+int fit_grad_rays_touched_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int D,
+                               const char* data_format, const float scale[3], const float offset[3], const float* ndc, const float* origins,
+                               const float* dirs, const float* targets, float* out, int64_t n, const rto_options* opt, int threads,
+                               int64_t* grad, uint64_t* stats, uint32_t* touched, bool marking, std::string* err) {
     const auto fail = [&](int code, const std::string& msg) {
         if (err) *err = msg;
         return code;
@@ -279,6 +308,10 @@ int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* 
                                            " with data_dim " + std::to_string(D));
     const std::string bad = fit_check_rays_call(params, origins, dirs, targets, out, n, opt, grad, stats, capacity * N3 * D);
     if (!bad.empty()) return fail(RTO_E_INVALID, bad);
+    if (marking) {
+        const std::string bad_t = fit_check_touched(params, origins, dirs, targets, out, n, grad, stats, touched, capacity * N3, D);
+        if (!bad_t.empty()) return fail(RTO_E_INVALID, bad_t);
+    }
     const std::string links = leaf_weights_check_links(child, capacity, N3);
     if (!links.empty()) return fail(RTO_E_FORMAT, links);
     if (n == 0) return RTO_OK;
@@ -288,7 +321,7 @@ int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* 
     host_frame_and_opt(scale, offset, ndc, opt, fr, o);
     const int nt = (int)std::min<int64_t>(threads <= 0 ? 1 : threads, n);
 #define RTO_FIT_CASE(B_) \
-    case B_: fit_rays<B_>(child, data, params, N, fr, o, origins, dirs, targets, out, n, nt, grad, stats); break
+    case B_: fit_rays<B_>(child, data, params, N, fr, o, origins, dirs, targets, out, n, nt, grad, stats, marking ? touched : nullptr); break
     switch (B) {
         RTO_FIT_CASE(0);
         RTO_FIT_CASE(1);

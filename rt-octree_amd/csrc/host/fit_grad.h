@@ -38,6 +38,16 @@ int fit_grad_rays_host(const int32_t* child, const uint16_t* data, const float* 
                        const float* targets, float* out, int64_t n, const rto_options* opt, int threads, int64_t* grad, uint64_t* stats,
                        std::string* err);
 
+// fit_grad_rays_host that also marks the touched bitmap (rto_fit_grad_rays_touched_host, marking = true: grad and touched are
+// required; marking = false is fit_grad_rays_host).  fit_check_touched: "" or what is wrong with the bitmap of a marking call
+// (slots = capacity * N^3), shared with the device entry
+std::string fit_check_touched(const float* params, const float* origins, const float* dirs, const float* targets, const float* out, int64_t n,
+                              const int64_t* grad, const uint64_t* stats, const uint32_t* touched, int64_t slots, int D);
+int fit_grad_rays_touched_host(const int32_t* child, const uint16_t* data, const float* params, int64_t capacity, int N, int D,
+                               const char* data_format, const float scale[3], const float offset[3], const float* ndc, const float* origins,
+                               const float* dirs, const float* targets, float* out, int64_t n, const rto_options* opt, int threads,
+                               int64_t* grad, uint64_t* stats, uint32_t* touched, bool marking, std::string* err);
+
 // p = p - lr * g over count parameters, g from the fixed-point word, which is zeroed
 int fit_sgd_step_host(float* params, int64_t* grad, int64_t count, float lr, std::string* err);
 

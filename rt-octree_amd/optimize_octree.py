@@ -8,6 +8,7 @@ render (include/rto.h "tree fit") by SGD.
         [--background 1.0] [--out_dir optimized] [--overwrite] [--backend hip|cpu]
         [--refine_rounds R] [--refine_nodes K] [--refine_weight_thresh 0.01] [--refine_max_level L]
         [--batch_rays R] [--seed S]
+        [--optimizer sgd|rmsprop|adam] [--sparse_step] [--beta1 0.9] [--beta2 0.999] [--eps 1e-8]
 
 One SGD step per batch of K images, in file order (no shuffling: a run is reproducible), E epochs.  --lr is the rate of a mean
 squared error: a step uses lr * 2 / (3 * rays of the batch) on the summed gradient.  Per epoch the PSNR of the training images
@@ -30,7 +31,16 @@ printed before it is made; on the device for hip, on the host for cpu -- walked 
 PCG64(--seed + epoch index), one SGD step per R rays at lr * 2 / (3 * rays of the batch).  Both backends see the same batches and
 write the same bytes; --val_poses and --refine_rounds (whose leaf weights still come from the cameras) work as before.  Measured
 on a tree of 2.1 M nodes: the full-array SGD step is 35 % of a step's time at R = 2^18, 14 % at 2^20 and 4 % at
-2^22, and shuffling costs 5 % of the gradient's rate; batches are not re-sorted by image (that won back 2.4 %)."""
+2^22, and shuffling costs 5 % of the gradient's rate; batches are not re-sorted by image (that won back 2.4 %).
+
+--sparse_step steps only the leaves the batch reached (include/rto.h "tree fit", rto_fit_step_sparse): the ray
+kernel marks them in a bitmap, the bitmap becomes a list, the step runs over the listed rows.  With --optimizer sgd it writes the
+bytes of the run without the flag.  --optimizer rmsprop|adam (which imply --sparse_step) keep their moments per leaf value and
+update them only where a batch reached (the lazy rule of torch.optim.SparseAdam and of Plenoxels); --lr is then the rate per
+parameter, the gradient of the mean squared error enters as grad_scale = 2 / (3 * rays of the batch), and --lr must be given:
+the default of 1000 is a rate for SGD on a mean squared error, a thousand units per step for an optimiser whose step has the
+size of lr.  Image batches go through the ray entry on the cameras' rays then (the same bytes).  A refinement round starts the
+moments and the step count afresh."""
 import argparse
 import json
 import os
@@ -90,8 +100,15 @@ def psnr_of(loss, rays):
     return float("nan") if rays == 0 else (float("inf") if loss <= 0 else -10.0 * np.log10(loss / (3.0 * rays)))
 
 
-def make_fit(z, options, backend):
-    """z: the dict of a dense tree.npz -> (a TreeFit or HostTreeFit, to_device: targets -> what its accumulate takes)"""
+def fit_kw_of(fit):
+    """the optimiser keywords a fit was made with: what a refinement hands to the next one"""
+    return {"optimizer": fit.optimizer, "sparse": fit.sparse, "beta1": fit.beta1, "beta2": fit.beta2, "eps": fit.eps}
+
+
+def make_fit(z, options, backend, fit_kw=None):
+    """z: the dict of a dense tree.npz -> (a TreeFit or HostTreeFit, to_device: targets -> what its accumulate takes).  fit_kw:
+    the optimiser keywords of TreeFit (optimizer, sparse, beta1, beta2, eps)"""
+    fit_kw = fit_kw or {}
     from .fit import HostTreeFit, TreeFit
     child = np.ascontiguousarray(z["child"], dtype=np.int32)
     data = np.ascontiguousarray(z["data"], dtype=np.float16)
@@ -103,13 +120,13 @@ def make_fit(z, options, backend):
     if not (fmt == "RGBA" or (fmt.startswith("SH") and fmt[2:].isdigit())):
         raise ValueError("the fit takes RGBA and SH trees, not data_format '%s'" % fmt)
     if backend == "cpu":
-        return HostTreeFit(child, data, scale, offset, fmt, options, threads=min(16, os.cpu_count() or 1)), lambda ts: ts
+        return HostTreeFit(child, data, scale, offset, fmt, options, threads=min(16, os.cpu_count() or 1), **fit_kw), lambda ts: ts
     if backend != "hip":
         raise ValueError("backend must be 'hip' or 'cpu', not %r" % (backend,))
     import torch
     from .volrend import N3Tree
     tree = N3Tree.from_arrays(child, data, scale, offset, fmt)
-    fit = TreeFit(tree, data, options)
+    fit = TreeFit(tree, data, options, **fit_kw)
     return fit, lambda ts: [torch.from_numpy(t).to(fit.params.device) for t in ts]
 
 
@@ -117,7 +134,8 @@ def refine_fit(fit, z, cams, options, backend, max_nodes=-1, weight_thresh=0.01,
     """One refinement between two rounds of epochs: the leaves of the fitted tree that the training cameras see with a weight of
     at least weight_thresh are split, heaviest first, at most max_nodes of them (negative: all).  z: the dict the fit was made
     from -> (the dict of the refined tree, the new fit, its to_device, the refiner's stats).  The new fit's params are the old
-    float32 params gathered by slot_src: the fit's state does not pass through fp16."""
+    float32 params gathered by slot_src: the fit's state does not pass through fp16.  The new fit is a new TreeFit with the old
+    one's optimiser: its moments are zero and its step count restarts (they are not carried across a refinement)."""
     from .refine import keys_from_weights, refine_tree
     from .refine_octree import weight_thresh_key
     from .simplify_octree import STALE_KEYS
@@ -141,7 +159,7 @@ def refine_fit(fit, z, cams, options, backend, max_nodes=-1, weight_thresh=0.01,
     for k in STALE_KEYS:
         z.pop(k, None)
     z["child"], z["data"] = c, d
-    new_fit, to_device = make_fit(z, options, backend)
+    new_fit, to_device = make_fit(z, options, backend, fit_kw_of(fit))
     if backend == "cpu":
         new_fit.params[...] = fit.params.reshape(-1, D)[slot_src.reshape(-1)].reshape(new_fit.params.shape)
     else:
@@ -200,17 +218,25 @@ def optimize(fit, to_device, cams, targets, lr, epochs, batch_imgs, val=None, sa
     val = None if val is None else (val[0], to_device(val[1]))
     k = max(1, int(batch_imgs))
     out = []
+    adaptive = getattr(fit, "optimizer", "sgd") != "sgd"  # lr per parameter, the mean's 2 / (3 rays) as grad_scale; else folded into lr as before
+
+    def step(rays):
+        if adaptive:
+            fit.step(lr, grad_scale=2.0 / (3.0 * rays))
+        else:
+            fit.step(lr * 2.0 / (3.0 * rays))
+
     for epoch in range(epochs):
         if batch_rays > 0:
             for o, d, t in table.batches(batch_rays):
                 fit.accumulate_rays(o, d, t)
-                fit.step(lr * 2.0 / (3.0 * int(o.shape[0])))  # (no ray of the table is masked: stats counts the batch)
+                step(int(o.shape[0]))  # (no ray of the table is masked: stats counts the batch)
         else:
             for b in range(0, len(cams), k):
                 bc, bt = cams[b:b + k], targets[b:b + k]
                 fit.accumulate(bc, bt)
                 rays = sum(int(c.width) * int(c.height) for c in bc)
-                fit.step(lr * 2.0 / (3.0 * rays))
+                step(rays)
         loss = fit.loss()
         if losses is not None:
             losses.append(loss)
@@ -244,19 +270,33 @@ def optimize_rounds(z, fit, to_device, cams, targets, options, backend, lr, epoc
     return z, fit
 
 
+# what --sparse_step's help says about when it pays (profiles/fit_sparse_bench.txt)
+SPARSE_HELP = ("Measured on a 2.1 M node tree: a batch's time falls to 0.36x at 2^14 rays, 0.49x at 2^16, 0.72x at 2^18 and 0.94x at 2^20; "
+               "at 2^22 rays (half of all leaves touched) the two steps are within 1 %%: the sparse path stops winning there and never "
+               "loses below.  Marking the leaves costs 1 %% of the gradient's time at 2^20 rays (0.24 ms, beside the 3.8 ms dense step)")
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(prog="python -m rt_octree_amd.optimize_octree", description=__doc__.split("\n\n")[0])
     parser.add_argument("input", type=str, nargs="+", help="Input npz(s)")
     parser.add_argument("--poses", type=str, required=True, help="transforms_train.json (blender) or the pose directory (tt)")
     parser.add_argument("--dataset", type=str, default="blender", help="blender|tt")
     parser.add_argument("--scale", type=float, default=1.0, help="The images are this fraction of the dataset's size")
-    parser.add_argument("--lr", type=float, default=1000.0, help="SGD rate on the mean squared error")
+    parser.add_argument("--lr", type=float, default=None,
+                        help="SGD rate on the mean squared error (default 1000); with --optimizer rmsprop|adam the rate per parameter, no default")
     parser.add_argument("--epochs", type=int, default=1)
     parser.add_argument("--batch_imgs", type=int, default=4, help="Images per SGD step")
     parser.add_argument("--batch_rays", type=int, default=0,
                         help="Rays per SGD step, shuffled over all images; 0 (default): steps on batches of --batch_imgs images.  "
                              "The full-array step is 14 %% of a step's time at 2^20 rays and 4 %% at 2^22 on a 2.1 M node tree")
     parser.add_argument("--seed", type=int, default=0, help="Seed of the shuffles of --batch_rays (epoch e draws from seed + e)")
+    parser.add_argument("--optimizer", choices=("sgd", "rmsprop", "adam"), default="sgd",
+                        help="sgd (default), or rmsprop / adam with lazily updated moments (they imply --sparse_step and need --lr)")
+    parser.add_argument("--sparse_step", action="store_true",
+                        help="Step only the leaves a batch reached; the same bytes as the dense step.  " + SPARSE_HELP)
+    parser.add_argument("--beta1", type=float, default=0.9, help="adam: decay of the first moment")
+    parser.add_argument("--beta2", type=float, default=0.999, help="rmsprop, adam: decay of the second moment")
+    parser.add_argument("--eps", type=float, default=1e-8, help="rmsprop, adam: added to the root of the second moment")
     parser.add_argument("--max_imgs", type=int, default=0, help="Use the first N poses only")
     parser.add_argument("--val_poses", type=str, default="", help="Pose file of a validation set, scored after every epoch")
     parser.add_argument("--stop_thresh", type=float, default=1e-2)
@@ -271,6 +311,17 @@ def main(argv=None):
     parser.add_argument("--refine_weight_thresh", type=float, default=0.01, help="A refinement splits leaves seen with at least this weight")
     parser.add_argument("--refine_max_level", type=int, default=31, help="A refinement never makes a node below this level")
     args = parser.parse_args(argv)
+    if args.lr is None:
+        if args.optimizer != "sgd":
+            print("optimize_octree: --optimizer %s needs an explicit --lr: the default of 1000 is an SGD rate on a mean squared error, and a "
+                  "step of rmsprop / adam has the size of lr itself (try 1e-2)" % args.optimizer, file=sys.stderr)
+            return 2
+        args.lr = 1000.0
+    if not (0 <= args.beta1 < 1 and 0 <= args.beta2 < 1 and args.eps >= 0):
+        print("optimize_octree: --beta1 and --beta2 must be in [0, 1), --eps >= 0", file=sys.stderr)
+        return 2
+    fit_kw = {"optimizer": args.optimizer, "sparse": args.sparse_step or args.optimizer != "sgd", "beta1": args.beta1, "beta2": args.beta2,
+              "eps": args.eps}
     if not (args.lr >= 0 and args.epochs >= 0):
         print("optimize_octree: --lr and --epochs must be numbers >= 0", file=sys.stderr)
         return 2
@@ -308,7 +359,7 @@ def main(argv=None):
                 if "child" not in f.files or "data" not in f.files:
                     raise ValueError("no child / data arrays: not a dense tree.npz")
                 z = {k: f[k] for k in f.files}
-            fit, to_device = make_fit(z, options, args.backend)
+            fit, to_device = make_fit(z, options, args.backend, fit_kw)
             if args.batch_rays > 0:
                 if table is None:
                     table = RayTable(cams, targets, args.seed, fit.params.device if args.backend == "hip" else None, say=say)
